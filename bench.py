@@ -11,6 +11,11 @@ tracker logic.  State is resident in HBM when the timed region starts (after `en
 One JSON line on stdout (rank 0).  With N>1 every step starts the RCCL all-gather of its observation
 rows over xGMI (the only exchange the path has); it overlaps with the next step and is awaited before the
 following one is started, the last one inside the timed region.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else the line can
+carry: the CPU baseline, the >= 2 s continuation of the headline rollout and the shortened runs of every other built
+config under "secondary".  `--dump-outputs DIR` writes what the last timed env.step returned (observation dict,
+reward, done, info) as DIR/<name>.npy in float32; the inputs are seeded, so two builds can be compared array by array.
 """
 import argparse
 import json
@@ -52,6 +57,34 @@ def cpu_baseline(seconds=3.0):
     out = cb.run(seconds)
     out["oracle_counters"] = cb.oracle_newton_iterations()
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, step_result, limit=DUMP_LIMIT_BYTES):
+    """`--dump-outputs`: the (obs, reward, done, info) of one env.step as <path>/<name>.npy, float32, nested dict keys joined
+    with '_' (obs_qpos, info_goal_dist_cube_quat, ...).  Past `limit` bytes in all, the same fixed, seeded subset of env rows
+    is kept in every array."""
+    flat = {}
+
+    def walk(name, v):
+        if isinstance(v, dict):
+            for k, x in v.items():
+                walk(name + "_" + k, x)
+        elif torch.is_tensor(v):
+            flat[name] = v.detach().to(torch.float32).cpu().numpy()
+
+    for name, v in zip(("obs", "reward", "done", "info"), step_result):
+        walk(name, v)
+    total = sum(a.nbytes for a in flat.values())
+    if total > limit:
+        B = max(a.shape[0] for a in flat.values() if a.ndim)
+        rows = np.sort(np.random.RandomState(0).choice(B, max(1, int(B * limit / total)), replace=False))
+        flat = {k: (a[rows] if a.ndim and a.shape[0] == B else a) for k, a in flat.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in flat.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def relaunch_with_ranks(n):
@@ -186,8 +219,9 @@ def bench_rearrange_blocks(args, emit=True, ycb=False, joint=False):
     gather = ShardedObservationGather(B, env.packed.shape[1], dev)
 
     def step():
-        env.step(torch.rand((B, env.action_dim), generator=gen, device=dev) * 2 - 1)
+        r = env.step(torch.rand((B, env.action_dim), generator=gen, device=dev) * 2 - 1)
         gather.start(env.packed)      # the packed row: observation + reward (3) + done
+        return r
 
     for _ in range(args.warmup):
         step()
@@ -213,13 +247,15 @@ def bench_rearrange_blocks(args, emit=True, ycb=False, joint=False):
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     gather.finish()
     if distributed:
         dist.barrier()
     sync()
     elapsed = time.perf_counter() - t0
     env._physics = orig
+    if emit and rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -256,7 +292,7 @@ def bench_rearrange_blocks(args, emit=True, ycb=False, joint=False):
                      "algorithmic_bytes_per_env_step": res["main"]["algorithmic_bytes_dense"], "frac_sparse_J": B * res["main"]["algorithmic_bytes_sparse_J"] / (ms_main * 1e-3) / HBM_PEAK,
                      "note": "dominant kernel = the main world's launch; SURVEY 8(d) dense byte model with the run's ncon / nefc / iterations; frac_sparse_J counts a constraint row at <= 16 dofs and M tree-sparse (what the stepper stores)"},
     }
-    if not args.no_cpu_baseline and world == 1 and not emul_path:
+    if args.full and not args.no_cpu_baseline and world == 1 and not emul_path:
         from oracle import cpu_baseline as cb
 
         out["cpu_baseline"] = cb.run_rearrange_blocks(4.0, ycb=ycb, joint=joint)
@@ -365,10 +401,12 @@ def bench_full_perpendicular(args, emit=True):
     t0 = time.perf_counter()
     for pair in ev:
         env._physics_events = pair
-        step()
+        last = step()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
     env._physics_events = None
+    if emit and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     on_palm = float((sim.scratch("site_xpos")[:, 3 * sim.center_site + 2] > 0.04).float().mean().item())
     st = sim.stats.sum(0).cpu().numpy()
@@ -393,7 +431,7 @@ def bench_full_perpendicular(args, emit=True):
                      "frac_sparse_J": B * algorithmic_bytes_sparse(_M, sim.info["nM"], ncon, nefc, iters, sim.n_substeps, sim.nq + sim.nv)[0] / (kern_ms * 1e-3) / HBM_PEAK,
                      "note": "frac = SURVEY 8(d) DENSE byte model (nefc x nv Jacobian, 2 nv^2 solver terms) with this model's dimensions (nM 1193) and the run's measured ncon / nefc / iterations; frac_sparse_J = the same model with a constraint row counted at <= 16 dofs and M tree-sparse, which is what the stepper stores: the dense figure overstates the bytes of a kernel whose Jacobians are sparse"},
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import cpu_baseline as cb
 
         out["cpu_baseline"] = cb.run_full_perpendicular(2.0)
@@ -477,8 +515,10 @@ def compact_secondary(e):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="locked", choices=["locked", "full_perpendicular", "rearrange_blocks", "ycb"], help="locked = BASELINE.json configs[1] (the headline); full_perpendicular = configs[2]; rearrange_blocks = configs[3]")
-    ap.add_argument("--verbose-secondary", action="store_true", help="keep every field of the secondary entries (the default line carries their numbers only: it stays under ~10 kB; tools/final_cycle.sh passes this for profiles/)")
-    ap.add_argument("--no-secondary", action="store_true", help="headline only: skip the shortened runs of the other built configs that the default line carries under 'secondary'")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the CPU baseline, the long window and (locked) the shortened runs of every other built config under 'secondary'")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the arrays the last timed env.step returned (obs / reward / done / info) as DIR/<name>.npy, float32, <= 64 MB in all")
+    ap.add_argument("--verbose-secondary", action="store_true", help="with --full: keep every field of the secondary entries (the line carries their numbers only: it stays under ~10 kB; tools/final_cycle.sh passes this for profiles/)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the shortened runs of the other built configs that the line carries under 'secondary', and the long window")
     ap.add_argument("--control-mode", default="tcp+roll+yaw", choices=["tcp+roll+yaw", "joint"], help="rearrange workloads: robot_control_params.control_mode")
     ap.add_argument("--quick-reset", action="store_true", help="rearrange_blocks: a shortened reset recipe (20 / 2 / 20 steps instead of 100 / 10 / 100)")
     ap.add_argument("--gpus", type=int, default=1)
@@ -487,9 +527,9 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=8192, help="envs per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-per-env-params", action="store_true", help="rearrange workloads: without the per-env model parameter rows (what the simulation randomizers and stabilize_objects write); default: with")
-    ap.add_argument("--no-long-window", action="store_true", help="skip the >= 2 s continuation of the headline rollout (config.long_window)")
+    ap.add_argument("--no-long-window", action="store_true", help="with --full: skip the >= 2 s continuation of the headline rollout (config.long_window)")
     ap.add_argument("--long-steps", type=int, default=300)
     ap.add_argument("--pipelined-reset", action="store_true", help="finished episodes run the reset recipe inside the step launches")
     ap.add_argument("--launch-flags", type=int, default=0, help="diagnostic: extra rg_step_args.flags of the step launches (4: no per-pair collision cache)")
@@ -553,7 +593,7 @@ def main():
         # the only exchange of the path: the full observation (166 scalars) with reward and done riding in
         # the same buffer, all-gathered over RCCL/xGMI when N > 1, overlapped with the next step
         gather.start(env.packed_observation(reward, done))
-        return done
+        return obs, reward, done, info
 
     for _ in range(args.warmup):
         one_step()
@@ -584,13 +624,15 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_step()
+        last = one_step()
     gather.finish()
     if distributed:
         dist.barrier()
     sync()
     elapsed = time.perf_counter() - t0
     sim.env_step = orig_env_step
+    if rank == 0 and args.dump_outputs:      # (before the long window: the step's outputs are views of buffers the next step rewrites)
+        dump_outputs(args.dump_outputs, last)
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -603,7 +645,7 @@ def main():
     status = int(sim.status.max().item())
     # the same rollout carried on over a window of >= 2 s (the driver's --steps 20 is 0.12 s of GPU time): reported next to the contract's K-step value, not as it
     long_window = None
-    if not emul_path and not args.no_long_window and not args.no_secondary:      # (profiling runs pass --no-secondary: their kernel statistics then hold the K timed launches only)
+    if args.full and not emul_path and not args.no_long_window and not args.no_secondary:      # (profiling runs pass --no-secondary: their kernel statistics then hold the K timed launches only)
         sync()
         tl = time.perf_counter()
         for _ in range(args.long_steps):
@@ -661,9 +703,9 @@ def main():
                          "kernel": kernel_name, "kernel_ms": kern_ms, "algorithmic_bytes_per_env_step": b_step, "algorithmic_bytes_per_substep": b_sub,
                          "note": "algorithmic bytes = SURVEY 8(d) stage-boundary model with measured ncon/nefc/iters; the fused kernel keeps stage arrays in LDS, so real HBM traffic is far below the algorithmic figure" + tnote},
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
-        if world == 1 and not emul_path and not args.no_secondary:
+        if args.full and world == 1 and not emul_path and not args.no_secondary:
             # every other built config in the one line: shortened runs, each with its own roofline and cpu_baseline
             del env, sim, gather
             torch.cuda.empty_cache()

@@ -1,8 +1,8 @@
 """SURVEY 8(b) `rg_compile_mjcf`: an MJCF STRING crosses the C ABI, as `MujocoXML.build` hands one to `mujoco_py.load_model_from_xml`
 (/root/reference/robogym/mujoco/mujoco_xml.py:249-260).  A C program that includes nothing but include/rgstep.h (tests/c/compile_mjcf_step.c) builds
 dactyl/locked from its merged document, steps it and prints qpos; the same document through the Python host gives the same numbers bit for bit.
-CPU: the emulation-harness build of the library source; `-m gpu`: the product library.  Needs the robogym asset tree (the XML / STL files are not
-redistributed with this repo), so the tests skip where it is absent (the GPU box)."""
+CPU: the emulation-harness build of the library source; `-m gpu`: the product library.  The documents are the merged ones as stored under tests/golden
+(tools/gen_golden_mjcf.py: the robogym asset tree is not redistributed with this repo), each mesh file they name written out as its convex hull."""
 import ctypes
 import os
 import subprocess
@@ -12,10 +12,29 @@ import numpy as np
 import pytest
 
 from robogym_amd import _native
-from robogym_amd.mujoco.mujoco_xml import assets_dir
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-needs_assets = pytest.mark.skipif(not os.path.isdir(os.path.join(assets_dir(), "xmls")), reason="robogym asset tree not present")
+G = os.path.join(ROOT, "tests", "golden")
+
+
+@pytest.fixture(scope="module")
+def mjcf_docs(tmp_path_factory):
+    """name -> merged MJCF document ("locked", "solver").  The hulls of tests/golden/mjcf_meshes.npz are written as binary STL files into an asset tree
+    that ROBOGYM_ASSETS_DIR names while the module runs (the compiler takes mesh files from there, in this process and in the helper process of the C ABI)."""
+    assets = tmp_path_factory.mktemp("assets")
+    meshdir = assets / "stls"
+    g = np.load(os.path.join(G, "mjcf_meshes.npz"))
+    for i, name in enumerate(g["names"]):
+        v, f = g["v%d" % i], g["f%d" % i]
+        rec = np.zeros(len(f), dtype=[("n", "<f4", 3), ("v", "<f4", (3, 3)), ("a", "<u2")])
+        rec["v"] = v[f]
+        path = meshdir / str(name)
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_bytes(b"\0" * 80 + np.uint32(len(f)).tobytes() + rec.tobytes())
+    mp = pytest.MonkeyPatch()
+    mp.setenv("ROBOGYM_ASSETS_DIR", str(assets))
+    yield {k: open(os.path.join(G, "mjcf_%s.xml" % k)).read().replace('meshdir="MESHDIR"', 'meshdir="%s"' % meshdir) for k in ("locked", "solver")}
+    mp.undo()
 
 
 @pytest.fixture(scope="module")
@@ -26,11 +45,9 @@ def c_program(tmp_path_factory):
 
 
 @pytest.fixture(scope="module")
-def locked_xml(tmp_path_factory):
-    from robogym_amd.envs.dactyl.locked import build_locked_xml
-
+def locked_xml(tmp_path_factory, mjcf_docs):
     path = str(tmp_path_factory.mktemp("xml") / "locked.xml")
-    doc = build_locked_xml().xml_string()
+    doc = mjcf_docs["locked"]
     open(path, "w").write(doc)
     return path, doc
 
@@ -53,7 +70,6 @@ def _run_c(exe, libpath, xml_path, nsteps, extra=()):
     return out.returncode, out.stdout, out.stderr
 
 
-@needs_assets
 def test_c_host_builds_locked_from_mjcf_and_steps_it_emul(c_program, locked_xml, emul_lib):
     path, doc = locked_xml
     libpath = os.path.join(ROOT, "tests", "emul", "librgstep_emul.so")
@@ -68,7 +84,6 @@ def test_c_host_builds_locked_from_mjcf_and_steps_it_emul(c_program, locked_xml,
     assert np.abs(q_c - load_locked_model().arrays["qpos0"]).max() > 1e-3     # (it moved: the cube fell towards the hand)
 
 
-@needs_assets
 def test_compile_mjcf_reports_the_compilers_error(c_program, tmp_path, emul_lib):
     bad = tmp_path / "bad.xml"
     bad.write_text('<mujoco><compiler angle="degree"/><worldbody/></mujoco>')
@@ -77,13 +92,10 @@ def test_compile_mjcf_reports_the_compilers_error(c_program, tmp_path, emul_lib)
     assert rc == 0 and "compile failed" in out and "degree" in out, (out, err)
 
 
-@needs_assets
-def test_compile_mjcf_blob_and_rb_kind_through_ctypes(emul_lib):
+def test_compile_mjcf_blob_and_rb_kind_through_ctypes(emul_lib, mjcf_docs):
     """the blob-only entry (compile once, create on several devices) and the large-model kind: the TCP solver's world from its document"""
-    from robogym_amd.envs.rearrange.xml import build_solver_xml
-
     L = emul_lib
-    doc = build_solver_xml().xml_string().encode()
+    doc = mjcf_docs["solver"].encode()
     blob, n, err = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.create_string_buffer(600)
     os.environ["RGSTEP_PYTHON"] = sys.executable
     assert L.rg_compile_mjcf_blob(doc, None, 1, ctypes.byref(blob), ctypes.byref(n), err, 600) == 0, err.value
@@ -102,7 +114,6 @@ def test_compile_mjcf_blob_and_rb_kind_through_ctypes(emul_lib):
     assert not L.rg_compile_mjcf(b"", None, err, 600) and b"empty" in err.value
 
 
-@needs_assets
 @pytest.mark.gpu
 def test_c_host_builds_locked_from_mjcf_and_steps_it_gpu(c_program, locked_xml):
     path, doc = locked_xml

@@ -70,12 +70,13 @@ def test_pendulum_forward_kinematics_matches_reference_fk(oracle_lib):
     """A second model through MJCF compiler -> oracle kinematics, against the reference's own numpy forward kinematics on its double-pendulum test model
     (tests/golden/pendulum_fk.npz from tools/gen_golden_pendulum_fk.py; the reference pins that FK to MuJoCo's site_xpos at 1e-6 on this very model,
     mujoco/test/test_mujoco_utils.py:148-179): site positions and the hinge2 joint anchor for 64 joint configurations, 1e-9.  (The XML's `integrator="RK4"` is
-    taken out before compiling -- this stepper is Euler only, as every robogym world is -- which kinematics do not see.)"""
+    taken out before compiling -- this stepper is Euler only, as every robogym world is -- which kinematics do not see.)  The model file is kept with the
+    fixture (tests/golden/inverted_double_pendulum.xml, robogym's test/inverted_pendulum/inverted_double_pendulum.xml unchanged)."""
     from oracle.rg_oracle import OracleSim
     from robogym_amd.mujoco.model_blob import pack_model
     from robogym_amd.mujoco.mujoco_xml import MujocoXML
 
-    x = MujocoXML.parse("test/inverted_pendulum/inverted_double_pendulum.xml").add_name_prefix("ivp:").add_default_compiler_directive()
+    x = MujocoXML.parse(os.path.join(G, "inverted_double_pendulum.xml")).add_name_prefix("ivp:").add_default_compiler_directive()
     for opt in x.root_element.iter("option"):
         opt.attrib.pop("integrator", None)
     m = x.build()

@@ -3,6 +3,8 @@
 # passes of the headline and of the three rb_step_kernel workloads (FETCH_SIZE / WRITE_SIZE in separate passes), per-world kernel stats of the rearrange workloads,
 # stage profiles, parity reports.  python tools/summarize_profile.py r05 afterwards stamps profiles/.
 R=${1:-r06}
+# OUT: where the bench line with every secondary entry (bench.py --full) goes, next to the other outputs of this script
+OUT=${OUT:?set OUT to the output directory}
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
@@ -21,8 +23,8 @@ done
 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary > gpurun_out/bench_$R.json 2> /dev/null      # (a short line for the summariser to read the batch size from)
 python tools/summarize_profile.py $R > /dev/null 2>&1
 python tests/tools/parity_json.py $R > gpurun_out/parity_json_$R.log 2>&1; cp profiles/parity.json gpurun_out/parity.json
-( time python bench.py --steps 20 --warmup 5 --verbose-secondary ) > gpurun_out/bench_$R.json 2> gpurun_out/bench_$R.err      # (profiles/ keeps the secondary entries' text; the default line carries their numbers only)
-tail -3 gpurun_out/bench_$R.err; tail -1 gpurun_out/bench_$R.json | cut -c1-200
+( time python bench.py --full --steps 20 --warmup 5 --verbose-secondary ) > "$OUT/bench_$R.json" 2> "$OUT/bench_$R.err"      # (profiles/ keeps the secondary entries' text; the --full line carries their numbers only)
+tail -3 "$OUT/bench_$R.err"; tail -1 "$OUT/bench_$R.json" | cut -c1-200
 python tests/tools/rearrange_parity_report.py 150 60 > gpurun_out/parity_rearrange_$R.txt 2>&1
 python tools/stage_profile.py 8192 > gpurun_out/stage_$R.txt 2>&1
 # (round 6) the parity block of the bench line, measured on this build; the Newton sub-stage profile of the analysis build (-DRG_FINE_PROF, ab_libs/librgstep_fine.so); the FETCH / WRITE calibration
