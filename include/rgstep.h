@@ -418,6 +418,12 @@ typedef struct ra_post_args {
                                                     row and gripper hand-over only: no reward, no tracker step, done = 0.  2: the env is skipped altogether.  3: the observation entries only (a live env
                                                     whose goal was just replaced): reward / done / flags / counters of the step stay */
   float reward_clip;                             /* ClipRewardWrapper (wrappers/util.py:115-126; 100 in RearrangeEnv.apply_wrappers): every reward entry clipped to +- this; 0 = off */
+  /* goal kinds (appended; zero-filled = the object-state task above).  0 ObjectStateGoal, 1 PickAndPlaceGoal (scored as 0), 2 ObjectStackGoal (goals/object_stack_goal.py:
+   * + per object |obj_pos - grip site| and the two finger contacts, summed into goal_dist_extra), 3 ObjectReachGoal / 4 DeterministicReachGoal (goals/object_reach_goal.py:
+   * the achieved position is the grip site, the achieved rotation zero; blocks_reach.py: the goal reward is the decrease of the summed obj_pos distance) */
+  int goal_kind;
+  int grip_site;                                 /* site robot0:grip (kinds 2-4) */
+  float* goal_dist_extra;                        /* [B][2] kind 2: sums of the gripper_pos distances and of `grasped`; NULL otherwise */
 } ra_post_args;
 int ra_env_post_step(rb_batch* main, rb_batch* solver, const ra_post_args* args, void* stream);
 int ra_post_args_size(void);
@@ -450,6 +456,16 @@ typedef struct ra_recipe_args {
   float area_offset[2], area_size[2], table_pos[3], table_size[3];   /* get_placement_area (simulation/base.py:980-1010), offset from the table's low corner */
   int stabilize_steps, n_random_initial_steps, settle_steps;
   unsigned seed, step;
+  /* goal kinds (appended; zero-filled = ObjectStateGoal), as ra_post_args.goal_kind.  1: one object's goal raised by uniform(height_range) (pickandplace.py
+   * move_one_object_to_the_air); 2: object 0's box placed without the grid, the others stacked on it at + i * 2 * object_size in a shuffled order unless fixed_order
+   * (object_stack_goal.py); 3: the object itself moved to an unconstrained placement (set_object_pos: position only), the goal target_height above it
+   * (object_reach_goal.py); 4: as 3 at det_points[goal_index], goal_index stepping 0 -> 1 -> 0 per goal and env (DeterministicReachGoal) */
+  int goal_kind;
+  float height_range[2], object_size;
+  int fixed_order;
+  float target_height;
+  float det_points[2][3];
+  int* goal_index;                               /* [B] kind 4 */
 } ra_recipe_args;
 int ra_env_recipe_step(rb_batch* main, rb_batch* solver, const ra_recipe_args* args, void* stream);
 int ra_recipe_args_size(void);

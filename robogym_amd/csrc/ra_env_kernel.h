@@ -43,7 +43,9 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
   const float* tcp = xpos + 3 * a.tcp_body;
   // ---- per object (lane k < N): pose, velocities, relative goal, distances, finger contacts, off-table test
   int ok_obj = 0, off_obj = 0;
-  float dpos = 0.f, drot = 0.f;
+  float dpos = 0.f, drot = 0.f, dgrip = 0.f, grasp = 0.f;
+  const int reach = a.goal_kind >= 3;
+  const float* grip = S + m.off[RB_O_SPOS] + 3 * a.grip_site;      // (kinds 2-4 only)
   if (lane < N) {
     const int b = a.obj_body[lane];
     float M[9], eul[3], vp[3], vr[3];
@@ -53,10 +55,12 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
     body_vel(b, vp, vr);
     const float* gp = a.goal + ((size_t)e * N + lane) * 7;
     float qc[4] = {xquat[4 * b], -xquat[4 * b + 1], -xquat[4 * b + 2], -xquat[4 * b + 3]}, qd[4], Md[9], rel[3];
+    if (reach) { qc[0] = 1.f; qc[1] = qc[2] = qc[3] = 0.f; }      // ObjectReachGoal.current_state: the achieved rotation is zero
     rbc_qmul(gp + 3, qc, qd);                 // subtract_euler(goal, current) = quat2euler(q_goal conj(q_obj))
     rbc_quat2mat(qd, Md); rbc_mat2euler(Md, rel);
     for (int k = 0; k < 3; k++) rel[k] = rbc_wrap(rel[k]);
-    const float rx = gp[0] - xpos[3 * b], ry = gp[1] - xpos[3 * b + 1], rz = gp[2] - xpos[3 * b + 2];
+    const float* ach = reach ? grip : xpos + 3 * b;                // ... and the achieved position the grip site's
+    const float rx = gp[0] - ach[0], ry = gp[1] - ach[1], rz = gp[2] - ach[2];
     dpos = fmaxf(sqrtf(rx * rx + ry * ry + rz * rz) + a.goal_pos_offset, 0.f);
     rbc_qsign(qd);
     { const float n = sqrtf(qd[0] * qd[0] + qd[1] * qd[1] + qd[2] * qd[2] + qd[3] * qd[3]); for (int k = 0; k < 4; k++) qd[k] /= n; }
@@ -87,6 +91,10 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
       }
     }
     o[g0 + 12 * N + 1 + 2 * lane] = cl; o[g0 + 12 * N + 1 + 2 * lane + 1] = cr;
+    if (a.goal_kind == 2) {      // ObjectStackGoal.goal_distance: |obj_pos - gripper_pos| per object, grasped = the two finger contacts (is_object_grasped)
+      const float gx = xpos[3 * b] - grip[0], gy = xpos[3 * b + 1] - grip[1], gz = xpos[3 * b + 2] - grip[2];
+      dgrip = sqrtf(gx * gx + gy * gy + gz * gz); grasp = cl + cr;
+    }
     const float* so = a.static_obs + ((size_t)e * N + lane) * 7;
     for (int k = 0; k < 3; k++) o[g0 + 14 * N + 1 + 3 * lane + k] = so[k];
     for (int k = 0; k < 4; k++) o[g0 + 17 * N + 1 + 4 * lane + k] = so[3 + k];
@@ -96,6 +104,10 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
   // sums of the distances over the objects (goal_info["goal_dist"])
   float sp = dpos, sr = drot;
   for (int o = 32; o > 0; o >>= 1) { sp += __shfl_xor(sp, o); sr += __shfl_xor(sr, o); }
+  if (a.goal_kind == 2) for (int o = 32; o > 0; o >>= 1) { dgrip += __shfl_xor(dgrip, o); grasp += __shfl_xor(grasp, o); }
+  // what the goal-distance reward is measured from: the count of objects within both thresholds (RearrangeEnv._calculate_num_success), for reach the summed obj_pos
+  // distance (BlocksReachEnv._calculate_goal_distance_reward: its decrease)
+  const float gscore = reach ? sp : (float)nsucc * a.goal_reward_per_object;
   // ---- robot read-outs and the copied blocks
   {
     float* o = row + 15 * N;
@@ -130,7 +142,7 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
     row[g0 + 6 * N] = (float)(!crash && nsucc == N);
     // reset_goal -> _observe_sync -> update_goal_info (robot_env.py:893-909, 586-593): the re-observation under the new goal is what the next step's
     // goal-distance reward is measured from
-    a.prev_nsucc[e] = (float)nsucc * a.goal_reward_per_object; a.prev_valid[e] = 1;
+    a.prev_nsucc[e] = gscore; a.prev_valid[e] = 1;
     float* o = row + g0 + 21 * N + 1;
     o[0] = (float)safety;
     for (int k = 0; k < 3; k++) { o[1 + k] = sens[a.force_adr + k]; o[4 + k] = sens[a.torque_adr + k]; }
@@ -139,11 +151,12 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
     float* rw = a.reward + 3 * (size_t)e;
     rw[0] = rw[1] = rw[2] = 0.f;
     a.goal_dist[2 * e] = sp; a.goal_dist[2 * e + 1] = sr;
+    if (a.goal_kind == 2) { a.goal_dist_extra[2 * e] = dgrip; a.goal_dist_extra[2 * e + 1] = grasp; }
     a.done[e] = 0; a.goal_reset[e] = 0; a.trial_success[e] = 0; a.sub_goal_ok[e] = 0; a.env_crash[e] = crash; a.objects_off_table[e] = any_off;
     a.info_ssl[e] = a.steps_since_last_goal[e];
     // RobotEnv.reset -> reset_goal_generation -> _observe_sync -> update_goal_info (robot_env.py:757-792, 586-593): the observation that ends a reset
     // establishes the success count the first step's goal-distance reward is measured from
-    if (frozen == 1) { a.prev_nsucc[e] = (float)nsucc * a.goal_reward_per_object; a.prev_valid[e] = 1; }
+    if (frozen == 1) { a.prev_nsucc[e] = gscore; a.prev_valid[e] = 1; }
     const int g0 = 15 * N + 15 + 2 * nq;
     row[g0 + 6 * N] = 0.f;
     float* o = row + g0 + 21 * N + 1;
@@ -165,9 +178,8 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
     if (safety) env_reward -= a.penalty_safety_stop;
     // ---- _get_goal_info: reward = change of the number of objects within both thresholds (common/base.py:824-848)
     a.t[e] += 1;
-    const float ns = (float)nsucc * a.goal_reward_per_object;
-    const float gdr = (a.prev_valid[e] && !crash) ? ns - a.prev_nsucc[e] : 0.f;
-    a.prev_nsucc[e] = ns; a.prev_valid[e] = 1;
+    const float gdr = (a.prev_valid[e] && !crash) ? (reach ? a.prev_nsucc[e] - gscore : gscore - a.prev_nsucc[e]) : 0.f;
+    a.prev_nsucc[e] = gscore; a.prev_valid[e] = 1;
     const int succ = !crash && nsucc == N;
     // ---- MultiGoalTracker.process (multi_goal_tracker.py:157-241)
     a.steps[e] += 1;
@@ -185,6 +197,7 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
     rw[0] = env_reward; rw[1] = a.use_goal_distance_reward ? gdr : 0.f; rw[2] = got ? a.success_reward : 0.f;
     if (a.reward_clip > 0.f) for (int k = 0; k < 3; k++) rw[k] = fminf(fmaxf(rw[k], -a.reward_clip), a.reward_clip);   // ClipRewardWrapper
     a.goal_dist[2 * e] = sp; a.goal_dist[2 * e + 1] = sr;
+    if (a.goal_kind == 2) { a.goal_dist_extra[2 * e] = dgrip; a.goal_dist_extra[2 * e + 1] = grasp; }
     done = done || timeout || trial || crash;
     a.done[e] = done; a.goal_reset[e] = newgoal; a.trial_success[e] = trial; a.sub_goal_ok[e] = got; a.env_crash[e] = crash;
     a.objects_off_table[e] = any_off; a.info_ssl[e] = ssl;
@@ -210,12 +223,12 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
 //   place_objects_in_grid / place_objects_with_no_constraint       envs/rearrange/common/utils.py:719-829 / 829-880 (_place_objects :623-716)
 //   get_placement_area                                             envs/rearrange/simulation/base.py:980-1010
 //   ObjectStateGoal.next_goal                                      envs/rearrange/goals/object_state.py:355-418
-struct RaRecipeLds { int started, ended, regoal; float pos[RA_MAXOBJ][3], gpos[RA_MAXOBJ][3], gyaw[RA_MAXOBJ]; };
+struct RaRecipeLds { int started, ended, regoal, moved; float pos[RA_MAXOBJ][3], gpos[RA_MAXOBJ][3], gyaw[RA_MAXOBJ], opos[3]; };
 
-// One placement of the N objects (rotated about z by yaw[i]) inside the placement area: body origins in world coordinates.  Returns false when the rejection
-// sampling ran out of restarts (out = its last proposal).  `k`: this env's running draw index.
-__device__ inline bool ra_place(const RaRecipeArgs& a, const float* yaw, int ystride, unsigned seed, unsigned step, unsigned e, unsigned& k, float (*out)[3]) {
-  const int N = a.num_objects;
+// One placement of the first N objects (rotated about z by yaw[i]) inside the placement area: body origins in world coordinates.  Returns false when the rejection
+// sampling ran out of restarts (out = its last proposal).  `k`: this env's running draw index.  `no_grid`: place_objects_with_no_constraint even where the grid
+// has cells enough (the stack and reach goals' own placement).
+__device__ inline bool ra_place(const RaRecipeArgs& a, int N, bool no_grid, const float* yaw, int ystride, unsigned seed, unsigned step, unsigned e, unsigned& k, float (*out)[3]) {
   auto U = [&]() -> float { return (float)(rbp_hash(seed, step, e, k++) >> 8) * (1.0f / 16777216.0f); };
   float hx[RA_MAXOBJ], hy[RA_MAXOBJ], xy[RA_MAXOBJ][2];
   float mx = 0.f, my = 0.f;
@@ -228,7 +241,7 @@ __device__ inline bool ra_place(const RaRecipeArgs& a, const float* yaw, int yst
   const int ncol = (int)floorf(width / (2.f * mx)), nrow = (int)floorf(height / (2.f * my));
   const int M = ncol * nrow;
   bool ok = true;
-  if (M >= N) {
+  if (M >= N && !no_grid) {
     // N distinct cells in random order = the first N of a random permutation of the M cells: a uniform random subset (Floyd), then shuffled
     int cell[RA_MAXOBJ];
     for (int idx = 0, j = M - N; j < M; j++, idx++) {
@@ -326,7 +339,37 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
     }
     if (gy) {
       k = 0u;     // (the goal's placement draws from its own stream: an env can get a new goal and end its episode on the same step)
-      if (!ra_place(a, gy, gstride, a.seed ^ 0x9E3779B9u, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
+      const unsigned gseed = a.seed ^ 0x9E3779B9u;
+      auto UG = [&]() -> float { return (float)(rbp_hash(gseed, a.step, (unsigned)e, k++) >> 8) * (1.0f / 16777216.0f); };
+      const int kind = a.goal_kind;
+      F.moved = 0;
+      if (kind <= 1) {
+        if (!ra_place(a, N, false, gy, gstride, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
+        if (kind == 1) {                                               // move_one_object_to_the_air: height first, then the object
+          const float h = a.height_range[0] + UG() * (a.height_range[1] - a.height_range[0]);
+          int i = (int)(UG() * (float)N); i = i > N - 1 ? N - 1 : i;
+          F.gpos[i][2] += h;
+        }
+      } else if (kind == 2) {                                          // ObjectStackGoal: object 0's box placed, the others on top of it in block order
+        float bot[1][3];
+        if (!ra_place(a, 1, true, gy, gstride, gseed, a.step, (unsigned)e, k, bot)) a.placement_failed[e] += 1;
+        int order[RA_MAXOBJ];
+        for (int i = 0; i < N; i++) order[i] = i;
+        if (!a.fixed_order)
+          for (int i = N - 1; i > 0; i--) { int j = (int)(UG() * (float)(i + 1)); j = j > i ? i : j; const int tmp = order[i]; order[i] = order[j]; order[j] = tmp; }
+        for (int i = 0; i < N; i++) { F.gpos[order[i]][0] = bot[0][0]; F.gpos[order[i]][1] = bot[0][1]; F.gpos[order[i]][2] = bot[0][2] + (float)i * 2.f * a.object_size; }
+      } else {                                                         // reach: the object goes to the placement, the goal target_height above it
+        if (kind == 3) {
+          if (!ra_place(a, 1, true, gy, gstride, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
+        } else {
+          const int gi = (a.goal_index[e] + 1) & 1;
+          a.goal_index[e] = gi;
+          for (int c = 0; c < 3; c++) F.gpos[0][c] = a.det_points[gi][c];
+        }
+        for (int c = 0; c < 3; c++) F.opos[c] = F.gpos[0][c];
+        F.gpos[0][2] += a.target_height;
+        F.moved = 1;
+      }
       for (int i = 0; i < N; i++) F.gyaw[i] = gy[i * gstride];
     }
     // ---- an episode that ended on this step: its recipe begins (the returned observation / reward / done are the terminal ones)
@@ -335,14 +378,15 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
       k = 1000u;
       float* yw = a.yaw + (size_t)e * N;
       for (int i = 0; i < N; i++) yw[i] = 2.f * RBC_PI * U();
-      if (!ra_place(a, yw, 1, a.seed, a.step, (unsigned)e, k, F.pos)) a.placement_failed[e] += 1;
+      if (!ra_place(a, N, false, yw, 1, a.seed, a.step, (unsigned)e, k, F.pos)) a.placement_failed[e] += 1;
       st = 1; lf = a.stabilize_steps > 0 ? a.stabilize_steps : 1;
       a.hold[e] = 1; a.hold_ctrl[e] = 1; a.frozen[e] = 4; a.solver_active[e] = 0; a.resetting[e] = 1;
       for (int d = 0; d < AD; d++) a.scripted[(size_t)e * AD + d] = 0.f;
     }
     // controller ticks of the NEXT step's main-world launch: two for live envs, one inside the recipe, two on the recipe's last step
+    // (reach: one on the recipe's last step -- the goal moves the object, the forward of _observe_sync follows it: the host's launch over the reobserve codes)
     const int last_stage = a.n_random_initial_steps >= 1 ? 3 : 1;
-    a.nticks[e] = st > 0 ? ((st == last_stage && lf <= 1) ? 2 : 1) : 2;
+    a.nticks[e] = st > 0 ? ((st == last_stage && lf <= 1 && a.goal_kind < 3) ? 2 : 1) : 2;
     a.stage[e] = st; a.left[e] = lf;
     a.reobserve[e] = started ? 1 : (regoal ? 3 : 2);
     a.ended[e] = (unsigned char)ended; a.stabilised[e] = (unsigned char)stabilised;
@@ -352,6 +396,7 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
   // ---- goal rows (goals/object_state.py:381-418): position, orientation (a z rotation, as Euler angles and as a quaternion), qpos_goal = the current qpos with
   // the objects at their goals; the previous success count is void
   if (F.started || F.regoal) {
+    if (F.moved && lane < 3) bt.qpos[(size_t)e * nq + a.obj_qposadr[0] + lane] = F.opos[lane];      // set_object_pos: the position only
     if (lane < N) {
       const float ez = rbc_wrap(F.gyaw[lane]);        // mat2euler of a z rotation, normalised
       float* g = a.goal + ((size_t)e * N + lane) * 7;

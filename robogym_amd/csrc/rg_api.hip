@@ -1577,6 +1577,10 @@ int ra_env_post_step(rb_batch* b, rb_batch* solver, const ra_post_args* args, vo
   for (int k = 0; k < 2; k++) if (a.finger_geom[k] < 0 || a.finger_geom[k] >= d.ngeom) return fail("ra_env_post_step: finger pad geom id out of range");
   if (a.table_plane_geom < 0 || a.table_plane_geom >= d.ngeom) return fail("ra_env_post_step: table plane geom id out of range");
   if (d.ngeom < 64 && (a.gripper_geom_mask >> d.ngeom) != 0) return fail("ra_env_post_step: gripper_geom_mask names a geom the model does not have (bit g = geom g, g < 64)");
+  if (a.goal_kind < 0 || a.goal_kind > 4) return fail("ra_env_post_step: goal_kind out of range (0 object state, 1 pick-and-place, 2 stack, 3 reach, 4 deterministic reach)");
+  if (a.goal_kind >= 2 && (a.grip_site < 0 || a.grip_site >= d.nsite)) return fail("ra_env_post_step: grip site id out of range");
+  if (a.goal_kind == 2 && !a.goal_dist_extra) return fail("ra_env_post_step: the stack goal needs goal_dist_extra");
+  if (a.goal_kind >= 3 && a.num_objects != 1) return fail("ra_env_post_step: the reach goals take exactly one object");
   if (solver) {
     if (solver->dev.B != b->dev.B || solver->device != b->device) return fail("ra_env_post_step: the two batches must have the same size and device");
     const RbModelDev& ds = solver->model->dev;
@@ -1617,6 +1621,10 @@ int ra_env_recipe_step(rb_batch* b, rb_batch* solver, const ra_recipe_args* args
   for (int k = 0; k < 6; k++) if (a.arm_qposadr[k] < 0 || a.arm_qposadr[k] >= d.nq) return fail("ra_env_recipe_step: arm joint address out of range");
   if (!(a.area_size[0] > 0.f) || !(a.area_size[1] > 0.f)) return fail("ra_env_recipe_step: empty placement area");
   if (a.stabilize_steps < 0 || a.n_random_initial_steps < 0 || a.settle_steps < 0) return fail("ra_env_recipe_step: negative step count");
+  if (a.goal_kind < 0 || a.goal_kind > 4) return fail("ra_env_recipe_step: goal_kind out of range (0 object state, 1 pick-and-place, 2 stack, 3 reach, 4 deterministic reach)");
+  if (a.goal_kind == 1 && !(a.height_range[0] <= a.height_range[1])) return fail("ra_env_recipe_step: empty height_range");
+  if (a.goal_kind >= 3 && a.num_objects != 1) return fail("ra_env_recipe_step: the reach goals take exactly one object");
+  if (a.goal_kind == 4 && !a.goal_index) return fail("ra_env_recipe_step: the deterministic reach goal needs goal_index");
   RbBatchDev sb; memset(&sb, 0, sizeof sb);
   const RbModelDev* ms = nullptr;
   if (solver) {

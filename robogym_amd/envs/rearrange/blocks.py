@@ -43,6 +43,11 @@ TABLETOP_EXPERIMENT_INITIAL_POS = np.deg2rad(np.array([135.0, -90, 135, -100, -2
 SPEED_ROLL, SPEED_PITCH = float(np.deg2rad(200)), float(np.deg2rad(600))                      # free_dof_tcp_arm.py:13-17
 JOINT_DRIFT_THRESHOLD = float(np.deg2rad(1))
 FLAG_FULL_FORWARD = 32
+#: the goal generators of the rearrange block tasks (ra_post_args.goal_kind): ObjectStateGoal (goals/object_state.py), PickAndPlaceGoal (goals/pickandplace.py),
+#: ObjectStackGoal (goals/object_stack_goal.py), ObjectReachGoal / DeterministicReachGoal (goals/object_reach_goal.py)
+GOAL_KINDS = {"object_state": 0, "pickandplace": 1, "stack": 2, "reach": 3, "det-reach": 4}
+#: DeterministicReachGoal's two object positions (goals/object_reach_goal.py:65-66)
+DET_REACH_POINTS = np.array([[1.50253879, 0.36960144, 0.5170952], [1.32253879, 0.53960144, 0.5170952]])
 
 OBS_KEYS = [("obj_pos", "N3"), ("obj_rel_pos", "N3"), ("obj_vel_pos", "N3"), ("obj_rot", "N3"), ("obj_vel_rot", "N3"), ("robot_joint_pos", 6), ("gripper_pos", 3),
             ("gripper_velp", 3), ("gripper_controls", 1), ("gripper_qpos", 1), ("gripper_vel", 1), ("qpos", "nq"), ("qpos_goal", "nq"), ("goal_obj_pos", "N3"),
@@ -65,14 +70,26 @@ class BatchedBlockRearrangeEnv:
                  use_goal_distance_reward: bool = True, goal_reward_per_object: float = 1.0, used_table_portion: float = 1.0, lib=None, n_substeps: int = 40,
                  main_model=None, wrappers: bool = False, n_action_bins: int = 11, smooth_alpha: float = 0.3, reward_clip: float = 100.0,
                  pipelined_reset: bool = False, action_spacing: str = "linear", per_env_parameters: bool = True, randomizer_params: Optional[dict] = None,
-                 stabilize_object_damping: float = 1.0e-3, control_mode: str = "tcp+roll+yaw", device_reset: bool = False, tcp_solver_mode: str = "mocap_ik"):
+                 stabilize_object_damping: float = 1.0e-3, control_mode: str = "tcp+roll+yaw", device_reset: bool = False, tcp_solver_mode: str = "mocap_ik",
+                 goal_kind: str = "object_state", height_range=(0.05, 0.25), object_size: float = 0.0254, fixed_order: bool = False, target_height: float = 0.1):
         """`per_env_parameters`: every env carries its own copy of the randomisable model fields (`self.sim.params`, LargeModelSimulation(env_params=True)) -- what
         the reference's simulation randomizers and `stabilize_objects` write into `sim.model`.  On by default (measured cost: 0.7 % of the step,
         profiles/r05_ab_rb_env_params.txt); off: the model's own arrays, no randomizers, no damping change while the objects stabilise.
         `device_reset` (with `pipelined_reset`): the recipe's stage machine, the begin-of-episode state and the placement / goal sampling run in ONE more launch after the
         env kernel (ra_env_recipe_step, include/rgstep.h) instead of host numpy behind a readback of the done / goal flags: a step call never waits for the GPU.
-        `randomizer_params`: name -> parameter of `build_simulation_randomizers` (the reference's ADR-controlled values; all zero by default = identity)."""
+        `randomizer_params`: name -> parameter of `build_simulation_randomizers` (the reference's ADR-controlled values; all zero by default = identity).
+        `goal_kind` (GOAL_KINDS): the task's goal generator -- "object_state" (this env's own), "pickandplace" (`height_range`), "stack" (`object_size`, `fixed_order`),
+        "reach" / "det-reach" (one object, `target_height`); envs/rearrange/blocks_pickandplace.py, blocks_stack.py, blocks_reach.py and ycb_pickandplace.py set it."""
         self.B, self.N = int(batch_size), int(num_objects)
+        if goal_kind not in GOAL_KINDS:
+            raise ValueError("goal_kind %r is not one of %s" % (goal_kind, ", ".join(GOAL_KINDS)))
+        self.goal_kind_name, self.goal_kind = goal_kind, GOAL_KINDS[goal_kind]
+        self.reach = self.goal_kind >= 3
+        if self.reach and self.N != 1:
+            raise ValueError("the reach goals take exactly one object (ObjectReachGoal: \"reach only supports one objects\"), got num_objects=%d" % self.N)
+        self.height_range, self.object_size, self.fixed_order, self.target_height = (float(height_range[0]), float(height_range[1])), float(object_size), bool(fixed_order), float(target_height)
+        if not self.height_range[0] <= self.height_range[1]:
+            raise ValueError("height_range %r is empty" % (height_range,))
         self._L = lib if lib is not None else _native.lib()
         self.control_mode = _control_mode_name(control_mode)
         self.joint_control = self.control_mode == "joint"      # ControlMode.JOINT: no TCP solver world (RobotControlParameters.requires_solver_sim, robot_interface.py:83-91)
@@ -158,7 +175,8 @@ class BatchedBlockRearrangeEnv:
         self.t, self.steps, self.ssl, self.successes, self.consecutive = (z(B, dt=torch.int32) for _ in range(5))
         self.prev_nsucc, self.prev_valid = z(B), z(B, dt=torch.int32)
         self.goal, self.goal_rot, self.qpos_goal, self.static_obs = z(B, N, 7), z(B, N, 3), z(B, self.nq), z(B, N, 7)
-        self.reward, self.goal_dist = z(B, 3), z(B, 2)
+        self.reward, self.goal_dist, self.goal_dist_extra = z(B, 3), z(B, 2), z(B, 2)
+        self.goal_index = z(B, dt=torch.int32)                  # DeterministicReachGoal.idx, per env
         self.done, self.goal_reset, self.trial_success, self.sub_goal_ok, self.env_crash, self.objects_off_table = (z(B, dt=torch.bool) for _ in range(6))
         self.info_ssl = z(B, dt=torch.int32)
         self.goal[:, :, 3] = 1.0
@@ -200,6 +218,8 @@ class BatchedBlockRearrangeEnv:
         a.safety_stop_force = 150.0                                      # robot/ur16e/arm_interface.py:46
         a.max_timesteps_per_goal, a.successes_needed, a.use_goal_distance_reward = max_timesteps_per_goal_per_obj * N, successes_needed, int(use_goal_distance_reward)
         a.solver_grip_qposadr, a.solver_grip_act = self.solver_grip_q, self.solver_grip_act
+        a.goal_kind, a.grip_site, a.goal_dist_extra = self.goal_kind, main.names["site"].index("robot0:grip"), P(self.goal_dist_extra)
+        self._grip_site = int(a.grip_site)
         self.action_shape = (self.B, self.action_dim)
         self._zero_action = z(B, AD)
         # ---- per-env model parameters: the reference's simulation randomizers (applied after _reset, robot_env.py:779-783) and stabilize_objects' damping change
@@ -268,6 +288,11 @@ class BatchedBlockRearrangeEnv:
                 r.table_pos[k], r.table_size[k] = float(self.table_pos[k]), float(self.table_size[k])
             r.stabilize_steps, r.n_random_initial_steps, r.settle_steps = int(stabilize_steps), int(n_random_initial_steps), int(settle_steps)
             r.seed, r.step = (int(starting_seed) * 2654435761 + 40503) & 0xFFFFFFFF, 0
+            r.goal_kind, r.height_range[0], r.height_range[1], r.object_size = self.goal_kind, self.height_range[0], self.height_range[1], self.object_size
+            r.fixed_order, r.target_height, r.goal_index = int(self.fixed_order), self.target_height, P(self.goal_index)
+            for j in range(2):
+                for k in range(3):
+                    r.det_points[j][k] = float(DET_REACH_POINTS[j, k])
 
     # ------------------------------------------------------------------ launches
     def _stream(self):
@@ -374,9 +399,12 @@ class BatchedBlockRearrangeEnv:
         return self.observe(), self.reward, self.done, self.info()
 
     def info(self):
-        return {"goal_dist_obj_pos": self.goal_dist[:, 0], "goal_dist_obj_rot": self.goal_dist[:, 1], "goal_reset": self.goal_reset, "trial_success": self.trial_success,
-                "sub_goal_is_successful": self.sub_goal_ok, "env_crash": self.env_crash, "objects_off_table": self.objects_off_table, "successes_so_far": self.successes,
-                "steps_since_last_goal": self.info_ssl, "resetting": self.resetting, "episode_started": self.episode_started}
+        out = {"goal_dist_obj_pos": self.goal_dist[:, 0], "goal_dist_obj_rot": self.goal_dist[:, 1], "goal_reset": self.goal_reset, "trial_success": self.trial_success,
+               "sub_goal_is_successful": self.sub_goal_ok, "env_crash": self.env_crash, "objects_off_table": self.objects_off_table, "successes_so_far": self.successes,
+               "steps_since_last_goal": self.info_ssl, "resetting": self.resetting, "episode_started": self.episode_started}
+        if self.goal_kind == 2:      # ObjectStackGoal.goal_distance's two more keys, summed as goal_info["goal_dist"] sums every key (robot_env.py:611)
+            out["goal_dist_gripper_pos"], out["goal_dist_grasped"] = self.goal_dist_extra[:, 0], self.goal_dist_extra[:, 1]
+        return out
 
     def observe(self, packed=None, action_ema=None):
         """Views into the packed row, keys / shapes of `RearrangeEnv._observe_simple` (common/base.py:376-421).  (`packed` / `action_ema`: rows of several envs
@@ -462,6 +490,56 @@ class BatchedBlockRearrangeEnv:
         portion = float(np.clip(self.used_table_portion, self.N * 0.1, 1.0))
         width, height = 0.5 * tsx * portion, 0.38 * tsy * portion
         return (0.5 * tsx - width / 2.0, 0.44 * tsy - height / 2.0, 2 * self.table_size[2]), (width, height, 0.26)
+
+    def _goal_positions(self, rows, yaw):
+        """`_sample_next_goal_positions` of the env's goal generator for the envs `rows` (host numpy; ra_recipe_kernel does the same on the device): [len(rows), N, 3].
+        Reach also moves the object itself (`set_object_pos`: position only) -- the caller's forward makes the observation see it."""
+        R, N, kind = len(rows), self.N, self.goal_kind
+        if kind <= 1:
+            pos = self._grid_placement(yaw, rows)
+            if kind == 1:      # move_one_object_to_the_air (goals/pickandplace.py:30-52): a height, then the object it raises
+                h = self._rng.uniform(self.height_range[0], self.height_range[1], R)
+                pos[np.arange(R), self._rng.randint(N, size=R), 2] += h
+            return pos
+        if kind == 4:          # DeterministicReachGoal: the next of its two points, per env
+            idx = torch.as_tensor(rows, device=self.device, dtype=torch.long)
+            gi = (self.goal_index[idx] + 1) % 2
+            self.goal_index[idx] = gi
+            bottom = DET_REACH_POINTS[gi.cpu().numpy()]
+        else:                  # place_objects_with_no_constraint on object 0's box alone
+            bottom = self._free_placement_of_object0(yaw[:, 0])
+        if kind == 2:          # ObjectStackGoal: the others on top of object 0's placement, in a shuffled block order unless fixed_order
+            pos = np.repeat(bottom[:, None, :], N, 1)
+            for r in range(R):
+                order = np.arange(N) if self.fixed_order else self._rng.permutation(N)
+                pos[r, order, 2] += np.arange(N) * 2 * self.object_size
+            return pos
+        idx = torch.as_tensor(rows, device=self.device, dtype=torch.long)      # reach
+        qa = self.obj_q[0]
+        self.sim.qpos[idx, qa:qa + 3] = torch.tensor(bottom.astype(np.float32), device=self.device)
+        pos = bottom[:, None, :].copy()
+        pos[:, 0, 2] += self.target_height
+        return pos
+
+    def _free_placement_of_object0(self, yaw0):
+        """place_objects_with_no_constraint (common/utils.py:829-880) for object 0 alone: a uniform proposal inside the placement area (one object: always free);
+        the body origin in world coordinates, as _grid_placement gives it.  `yaw0` [R]."""
+        (off_x, off_y, _), (width, height, _) = self.placement_area()
+        sx, sy = self.obj_half[0, 0], self.obj_half[0, 1]
+        c, s_ = np.cos(yaw0), np.sin(yaw0)
+        hx, hy = np.abs(c) * sx + np.abs(s_) * sy, np.abs(s_) * sx + np.abs(c) * sy
+        x, y = self._rng.uniform(hx, width - hx), self._rng.uniform(hy, height - hy)
+        centre = np.stack([c * self.obj_center[0, 0] - s_ * self.obj_center[0, 1], s_ * self.obj_center[0, 0] + c * self.obj_center[0, 1], np.full_like(yaw0, self.obj_center[0, 2])], -1)
+        p = np.stack([x, y, np.full_like(yaw0, self.obj_half[0, 2] + 2 * self.table_size[2])], -1)
+        return p + [off_x, off_y, 0.0] - self.table_size + self.table_pos - centre
+
+    def _forward_rows(self, rows):
+        """_observe_sync's forward (one controller tick, the full stage arrays) for the envs `rows` only."""
+        if len(rows) == 0:
+            return
+        active = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        active[torch.as_tensor(rows, device=self.device, dtype=torch.long)] = 1
+        self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=active)
 
     def _write_goal(self, rows, goal_pos, yaw):
         dev = self.device
@@ -567,7 +645,7 @@ class BatchedBlockRearrangeEnv:
             f[idx] = 0
         self.ema_value[idx] = 0; self.action_ema[idx] = 0          # SmoothActionWrapper.reset: a fresh filter, action_ema = 0
         self._randomize_simulation(idx)                               # simulation_randomizer.randomize AFTER _reset (robot_env.py:779-783)
-        self._write_goal(rows, self._grid_placement(yaw, rows), yaw)
+        self._write_goal(rows, self._goal_positions(rows, yaw), yaw)
         self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=active)       # the forward of _observe_sync
         # the first observation of the new episodes: the env kernel for exactly those rows (observation + gripper hand-over, zeroed reward / done, the success count
         # the first step's goal reward is measured from); the rows of everybody else -- and the reward / done / info tensors their last step() returned -- stay
@@ -631,12 +709,14 @@ class BatchedBlockRearrangeEnv:
             self.resetting[idx] = False; self.episode_started[idx] = True
             self._randomize_simulation(idx)
             yaw = self._yaw[rows]
-            self._write_goal(rows, self._grid_placement(yaw, rows), yaw)
+            self._write_goal(rows, self._goal_positions(rows, yaw), yaw)
         # ---- live envs with a reached goal: ObjectStateGoal.next_goal (what reset_goals() does on request)
         grows = np.nonzero(newgoal.astype(bool) & (st == 0) & ~done.astype(bool))[0]     # (an episode that ends on the same step keeps the reached goal's entries in its terminal observation: ra_recipe_kernel)
         if len(grows):
             yaw = self.goal_rot[torch.as_tensor(grows, device=dev, dtype=torch.long), :, 2].cpu().numpy().astype(np.float64)
-            self._write_goal(grows, self._grid_placement(yaw, grows), yaw)
+            self._write_goal(grows, self._goal_positions(grows, yaw), yaw)
+        if self.reach:
+            self._forward_rows(np.concatenate(started + [grows]))
         self._reobserve(np.concatenate(started) if started else np.zeros(0, dtype=np.int64), grows)
         # ---- episodes that ended on this step: their recipe begins (the returned observation / reward / done are the terminal ones)
         rows = np.nonzero(done.astype(bool) & (st == 0))[0]
@@ -652,7 +732,8 @@ class BatchedBlockRearrangeEnv:
                 left[rows] = 1
         # controller ticks of the NEXT step's main-world launch: two for live envs, one inside the recipe, two on the recipe's last step (see _physics)
         last_stage = 3 if self.n_random_initial_steps >= 1 else 1
-        want = np.where(st > 0, np.where((st == last_stage) & (left <= 1), 2, 1), 2).astype(np.int32)
+        # (reach: one on the recipe's last step -- its goal moves the object, the forward of _observe_sync comes after that, _forward_rows)
+        want = np.where(st > 0, np.where((st == last_stage) & (left <= 1) & (not self.reach), 2, 1), 2).astype(np.int32)
         if not np.array_equal(want, getattr(self, "_nticks_host", None)):
             self._nticks_host = want
             self.nticks.copy_(torch.as_tensor(want, device=dev))
@@ -673,6 +754,8 @@ class BatchedBlockRearrangeEnv:
                                      torch.where(self.stabilised[:, None], self._param_defaults["dof_damping"][cols][None, :].expand_as(cur), cur))
             for rz in self.randomizers:
                 rz.randomize(self.sim, self._rand_gen, self.episode_started)
+        if self.reach:      # the object the goal moved: _observe_sync's forward for the envs with a new goal (no readback: every env, masked by the reobserve codes)
+            self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=(self.reobserve != 2).to(torch.int32))
         had = self.post.frozen
         self.post.frozen = self.reobserve.data_ptr()
         self._post()
@@ -712,7 +795,9 @@ class BatchedBlockRearrangeEnv:
         if len(rows) == 0:
             return
         yaw = self.goal_rot[torch.as_tensor(rows, device=self.device, dtype=torch.long), :, 2].cpu().numpy().astype(np.float64)
-        self._write_goal(rows, self._grid_placement(yaw, rows), yaw)
+        self._write_goal(rows, self._goal_positions(rows, yaw), yaw)
+        if self.reach:
+            self._forward_rows(rows)
         self._reobserve(np.zeros(0, dtype=np.int64), rows)      # robot_env.py:893-909: the observation returned after a goal reset carries the new goal
 
     def sync(self):

@@ -187,7 +187,38 @@ def load_blocks_model(num_objects: int = 5, recompile: bool = False, mocap_arm: 
     path = os.path.join(MODEL_DIR, "rearrange_blocks%d%s.npz" % (num_objects, "_mocap" if mocap_arm else ""))
     if not recompile and os.path.exists(path):
         return CompiledModel.load(path)
+    if not recompile and not mocap_arm and 1 <= num_objects < 5:
+        return blocks_world_subset(load_blocks_model(5), num_objects)
     return build_blocks_xml(num_objects, joint_actuated=not mocap_arm).build()
+
+
+def blocks_world_subset(model: CompiledModel, num_objects: int) -> CompiledModel:
+    """The blocks world with the first `num_objects` blocks, cut out of a compiled world with more.  make_blocks_and_targets appends the (object, target) bodies
+    last and in object order, so every body / joint / dof / geom / qpos table of the smaller world is a prefix of the larger one's; the constants that depend on
+    the whole tree (subtree masses, inverse weights, acc0, mean inertia) are recomputed by set_constants.  The result is the world compile_mjcf builds from the
+    MJCF with `num_objects` blocks, array for array (tests/golden/rearrange_blocks_worlds.json, tools/gen_golden_blocks_worlds.py)."""
+    from robogym_amd.mujoco.setconst import set_constants
+
+    A, names = model.arrays, model.names
+    if "target:object%d" % (num_objects - 1) not in names["body"]:
+        raise ValueError("the model has fewer than %d blocks" % num_objects)
+    nbody = names["body"].index("target:object%d" % (num_objects - 1)) + 1
+    assert names["body"][nbody - 2:nbody] == ["object%d" % (num_objects - 1), "target:object%d" % (num_objects - 1)], "the blocks are not the model's last bodies"
+    njnt = names["joint"].index("object%d:joint" % (num_objects - 1)) + 1
+    ngeom = int(A["body_geomadr"][nbody - 1] + A["body_geomnum"][nbody - 1])
+    nq, nv = int(A["jnt_qposadr"][njnt - 1]) + 7, int(A["jnt_dofadr"][njnt - 1]) + 6          # (a free joint: 7 positions, 6 dofs)
+    cut = {"body_": nbody, "jnt_": njnt, "geom_": ngeom, "dof_": nv, "qpos0": nq, "qpos_spring": nq}
+    m = CompiledModel()
+    for k, v in A.items():
+        n = next((c for prefix, c in cut.items() if k.startswith(prefix)), None)
+        m.arrays[k] = (v if n is None else v[:n]).copy()
+    m.names = {k: list(v) for k, v in names.items()}
+    m.names["body"], m.names["joint"], m.names["geom"] = names["body"][:nbody], names["joint"][:njnt], names["geom"][:ngeom]
+    dims = m.arrays["dims"].copy()
+    dims[0], dims[1], dims[3], dims[4], dims[5] = nq, nv, nbody, njnt, ngeom       # (nq, nv, nu, nbody, njnt, ngeom, ...)
+    m.arrays["dims"] = dims
+    set_constants(m)
+    return m
 
 
 def load_solver_model(recompile: bool = False) -> CompiledModel:
