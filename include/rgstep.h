@@ -303,7 +303,16 @@ rb_model* rb_compile_mjcf(const char* xml, const char* meshdir, char* err, int e
  * range, body_pos / mass / inertia / invweight0, actuator_gainprm / forcerange / ctrlrange, geom_pos / margin / gap / friction / solref / solimp (a contact mixes its
  * two geoms' values as mj_contactParam does), tendon_range / invweight0.  The *_invweight0 rows are mj_setConst outputs: the reference's rearrange envs never call
  * set_constants after randomizing (only dactyl's cube_env.py:349 does), so they stay at the compiled model's values unless the host writes them.
- * rb_prm_layout: out[0] = 1 if enabled, out[1] = words per block, then per field (order above) its word offset in the scratch row and its length. */
+ * Appended after those 23 fields (which keep their indices), what the dactyl randomization stack writes per step or per episode:
+ *   timestep      1 word, seconds: opt.timestep of the env -- integrator, implicit damping M + h B, the solref clamp, the controllers' ticks, mjData.time;
+ *   xfrc_applied  [nbody][6], mjData.xfrc_applied: force (N) then torque (N m), world frame, applied at the body's centre of mass; enters the smooth forces
+ *                 (mj_xfrcAccumulate) and the F/T sensors (mj_rnePostConstraint); starts at zero and rb_batch_reset clears it (mj_resetData); envs whose rows are all
+ *                 zero skip the stage;
+ *   site_pos      [nsite][3], metres, in the frame of the site's body;
+ *   geom_scale    1 word, dimensionless: ONE size factor for the geoms the model flags in the optional blob array b_geom_scaled (int per geom; meshes and boxes only,
+ *                 no tendon wrap object -- rb_model_create refuses anything else): mesh vertices / box half extents, bounding radius and oriented box scale about
+ *                 the geom's origin.  Starts at 1.
+ * rb_prm_layout: out[0] = 1 if enabled, out[1] = words per block, then per field (order above, 27 fields) its word offset in the scratch row and its length. */
 int rb_model_enable_env_params(rb_model* m);
 int rb_prm_layout(const rb_model* m, int* out, int n);
 int rb_model_blob_keys(const rb_model* m, char* out, int outlen);   /* the blob arrays rb_model_create read (see rg_blob_entry) */

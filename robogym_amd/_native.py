@@ -252,7 +252,7 @@ RG_FLAG_RESUME = 256           # bit 8: active_dev is a redo array: entry - 1 = 
 
 RB_PRM_NAMES = ["gravity", "dof_damping", "dof_armature", "dof_frictionloss", "dof_invweight0", "jnt_stiffness", "jnt_margin", "jnt_range", "body_pos", "body_mass", "body_inertia",
                 "body_invweight0", "actuator_gainprm", "actuator_forcerange", "actuator_ctrlrange", "geom_pos", "geom_margin", "geom_gap", "geom_friction", "geom_solref", "geom_solimp",
-                "tendon_range", "tendon_invweight0"]      # rb_types.h RB_P_* order (rb_prm_layout)
+                "tendon_range", "tendon_invweight0", "timestep", "xfrc_applied", "site_pos", "geom_scale"]      # rb_types.h RB_P_* order (rb_prm_layout)
 PRM_NAMES = ["row", "gravity", "timestep", "dof_damping", "dof_armature", "dof_frictionloss", "dof_invweight0", "body_mass", "body_inertia", "body_invweight0",
              "jnt_range", "tendon_range", "tendon_invweight0", "actuator_gainprm", "actuator_ctrlrange", "actuator_forcerange", "geom_friction", "xfrc_applied", "site_pos", "geom_scale", "jnt_margin", "geom_solref", "geom_solimp"]
 

@@ -348,7 +348,8 @@ __global__ void __launch_bounds__(64) rb_post_step_kernel(const RbModelDev* mp, 
       // (the env's own gains when the model carries per-env parameter rows, rb_types.h RB_P_*)
       const float* gainprm = m.prm_on ? S + m.prm_off[RB_P_ACT_GAINPRM] : m.actuator_gainprm;
       const float* forcerange = m.prm_on ? S + m.prm_off[RB_P_ACT_FORCERANGE] : m.actuator_forcerange;
-      for (int k = 0; k < 2; k++) rb_pid_tick(m, gainprm, forcerange, u, bt.ctrl[(size_t)e * nu + u], len, st);
+      const float dt = m.prm_on ? S[m.prm_off[RB_P_TIMESTEP]] : m.timestep;   // (and the env's own step length)
+      for (int k = 0; k < 2; k++) rb_pid_tick(m, dt, gainprm, forcerange, u, bt.ctrl[(size_t)e * nu + u], len, st);
     }
   }
   // ---- state part of the observation row: cube_pos 3 | cube_quat 4 (w >= 0) | cube_face_angle 6 (wrapped) | hand_angle | fingertip_pos 15 (| goal_pos 3 |

@@ -77,6 +77,11 @@ struct RbLds {
   int env;               // this workgroup's env in its batch (= blockIdx.x in a one-batch launch; a multi-batch launch, rb_step_multi_kernel, splits blockIdx.x into batch and env)
   float mocap[14];       // pose of the mocap bodies (mjData.mocap_pos / mocap_quat), at most two
   float time;            // mjData.time (the cascaded-PI controller warm-starts its smoothed set-point at time 0)
+  // read once per launch from the env's parameter block (rb_types.h RB_P_TIMESTEP / RB_P_GEOM_SCALE / RB_P_XFRC), or the model's values without blocks
+  float timestep;        // opt.timestep of this env
+  float gscale;          // size factor of the geoms flagged in b_geom_scaled (1 without blocks)
+  int has_xfrc;          // any non-zero entry in the env's xfrc_applied rows: envs without one skip mj_xfrcAccumulate altogether
+  int mass_default;      // the env's body_mass row holds the model's own values (rb_com_pos then takes the model's body_subtreemass)
   unsigned status;
 };
 
@@ -226,7 +231,7 @@ __device__ __forceinline__ void rb_kinematics(RbM m, RbLds& s, float* S) {
   }
   BFOR(i, m.nsite) {
     const int b = m.site_bodyid[i];
-    st3(SC(SPOS) + 3 * i, ld3(xpos + 3 * b) + qrot(ldq(xquat + 4 * b), ld3(m.site_pos + 3 * i)));
+    st3(SC(SPOS) + 3 * i, ld3(xpos + 3 * b) + qrot(ldq(xquat + 4 * b), ld3(PRM(site_pos, RB_P_SITE_POS) + 3 * i)));
   }
   BSYNC();
 }
@@ -250,7 +255,12 @@ __device__ __forceinline__ void rb_com_pos(RbM m, RbLds& s, float* S) {
 #pragma unroll
       for (int u = 0; u < 4; u++) if (q + u < q1) { acc = acc + xx[u] * mm[u]; msum += mm[u]; }
     }
-    const float sm = m.prm_on ? msum : m.body_subtreemass[root];
+    // (Large configuration: an env whose body_mass row holds the model's values takes the model's number -- the fp32 sum differs from the host's fp64 one in the
+    //  last bit, and a block of default rows must compute what a batch without blocks computes: the full cube's touching cubelets amplify that bit to 4e-5 in qpos
+    //  within four mj_steps.  The one-wave configurations keep the sum for every env with blocks, as they always have: the rearrange worlds run with blocks by
+    //  default and stay bit for bit what they were; their resting objects do not amplify the bit, tests/test_rearrange_env_params.py.)
+    const bool summed = m.prm_on && (RB_NWAVE == 1 || !s.mass_default);
+    const float sm = summed ? msum : m.body_subtreemass[root];
     st3(rootcom + 3 * root, sm < RB_MINVAL ? ld3(xipos + 3 * root) : acc * (1.0f / sm));
   }
   BSYNC();
@@ -1133,10 +1143,9 @@ __device__ __forceinline__ void rb_velocity(RbM m, RbLds& s, float* S) {
 // ------------------------------------------------------------------------------------------------- actuation
 // mujoco-py's PID callback (mjpid.pyx semantics as restated by oracle ro_fwd_actuation); `apply`: also qfrc_actuator
 // one tick of one actuator's controller: st = {integral, previous error, smoothed derivative}; returns the clamped force
-// (gainprm / forcerange: the model's arrays or the env's own rows)
+// (gainprm / forcerange: the model's arrays or the env's own rows; dt: the env's timestep)
 template <class Model>
-__device__ __forceinline__ float rb_pid_tick(const Model& m, const float* gainprm, const float* forcerange, int u, float ctrl, float length, float* st) {
-  const float dt = m.timestep;
+__device__ __forceinline__ float rb_pid_tick(const Model& m, float dt, const float* gainprm, const float* forcerange, int u, float ctrl, float length, float* st) {
   const float* gp = gainprm + 10 * u;
   const float kp = gp[0], ti = gp[1], iclamp = gp[2], td = gp[3], smooth = gp[4], deadband = gp[5];
   float err = ctrl - length;
@@ -1156,8 +1165,7 @@ __device__ __forceinline__ float rb_pid_tick(const Model& m, const float* gainpr
 // +- max_vel -> PI on actuator_velocity -> plus `bias_ff`, the bias force (gravity + Coriolis) of the actuated dof over the gear -> clamped to forcerange.
 // (The feed-forward is inferred from the reference's impulse-response pins, oracle/rg_oracle.c ro_cascade_bias_ff: the wrist joints' velocity loops are P-only.)
 template <class Model>
-__device__ __forceinline__ float rb_cascade_tick(const Model& m, const float* gainprm, const float* forcerange, int u, float ctrl, float length, float velocity, float bias_ff, bool time0, float* st) {
-  const float dt = m.timestep;
+__device__ __forceinline__ float rb_cascade_tick(const Model& m, float dt, const float* gainprm, const float* forcerange, int u, float ctrl, float length, float velocity, float bias_ff, bool time0, float* st) {
   const float* gp = gainprm + 10 * u;
   const float setp = time0 ? ctrl : gp[8] * st[2] + (1.f - gp[8]) * ctrl;
   st[2] = setp;
@@ -1188,8 +1196,8 @@ __device__ __forceinline__ void rb_pid(RbM m, RbLds& s, float* S, bool apply) {
       // (a state-less tick, apply == false, keeps only the controller state, which the feed-forward never enters: it is not read there — the TCP
       // hook's sync tick runs before any stage of the launch has written qfrc_bias)
       const float ff = (apply && joint) ? s.qfrc_bias[m.jnt_dofadr[id]] / m.actuator_gear[u] : 0.f;
-      s.actfrc[u] = rb_cascade_tick(m, gainprm, forcerange, u, s.ctrl[u], s.actlen[u], vel, ff, s.time == 0.f, s.pid + 3 * u);
-    } else s.actfrc[u] = rb_pid_tick(m, gainprm, forcerange, u, s.ctrl[u], s.actlen[u], s.pid + 3 * u);
+      s.actfrc[u] = rb_cascade_tick(m, s.timestep, gainprm, forcerange, u, s.ctrl[u], s.actlen[u], vel, ff, s.time == 0.f, s.pid + 3 * u);
+    } else s.actfrc[u] = rb_pid_tick(m, s.timestep, gainprm, forcerange, u, s.ctrl[u], s.actlen[u], s.pid + 3 * u);
   }
   BSYNC();
   if (!apply) return;
@@ -1201,15 +1209,35 @@ __device__ __forceinline__ void rb_pid(RbM m, RbLds& s, float* S, bool apply) {
       else for (int e = 0; e < RB_TENW; e++) if (m.b_ten_dofs[RB_TENW * id + e] == i) f += g * SC(TENJ)[RB_TENW * id + e] * s.actfrc[u];
     }
     s.qfrc_act[i] = f;
-    s.qfrc_smooth[i] = s.qfrc_passive[i] - s.qfrc_bias[i] + f;
+    float fs = s.qfrc_passive[i] - s.qfrc_bias[i] + f;
+    if (s.has_xfrc) {
+      // mj_xfrcAccumulate (oracle ro_fwd_acceleration): J(com of body)' force + J_rot' torque of every body with a wrench whose chain holds dof i = the bodies of
+      // the subtree of the dof's body.  cdof is expressed in the com-based frame of the tree: J_point = cdof_lin + cdof_ang x (point - rootcom).
+      const float* xf = S + m.prm_off[RB_P_XFRC];
+      const int bd = m.dof_bodyid[i];
+      const v3 ang = ld3(SC(CDOF) + 6 * i), lin = ld3(SC(CDOF) + 6 * i + 3), org = ld3(SC(ROOTCOM) + 3 * m.body_rootid[bd]);
+      float acc = 0.f;
+      for (int q = m.b_subtree_adr[bd]; q < m.b_subtree_adr[bd + 1]; q++) {
+        const int b = m.b_subtree[q]; const float* w = xf + 6 * b;
+        if (w[0] == 0.f && w[1] == 0.f && w[2] == 0.f && w[3] == 0.f && w[4] == 0.f && w[5] == 0.f) continue;
+        acc += dot(ld3(w), lin + cross(ang, ld3(SC(XIPOS) + 3 * b) - org)) + dot(ld3(w + 3), ang);
+      }
+      fs += acc;
+    }
+    s.qfrc_smooth[i] = fs;
   }
   BSYNC();
 }
 
 // ------------------------------------------------------------------------------------------------- collision
-__device__ __forceinline__ void rb_geom(RbM m, const float* S, int g, MprGeom& G) {
-  G.type = m.geom_type[g]; G.quat = SC(GQUAT) + 4 * g; G.size = ld3(m.geom_size + 3 * g); G.mesh = -1; G.vertadr = 0; G.nvert = 0;
-  if (G.type == RG_GEOM_MESH) { G.mesh = m.geom_dataid[g]; G.vertadr = m.mesh_vertadr[G.mesh]; G.nvert = m.mesh_vertnum[G.mesh]; }
+// size factor of geom g in this env: the env's RB_P_GEOM_SCALE for the geoms the model flags (b_geom_scaled: meshes and boxes), 1 for all others and without blocks
+__device__ __forceinline__ float rb_geom_scale(RbM m, const RbLds& s, int g) { return (m.prm_on && m.ngeom_scaled > 0 && m.b_geom_scaled[g]) ? s.gscale : 1.f; }
+// (a scaled mesh keeps its vertex table: the support point is scale * vertex, and a uniform positive scale keeps the arg-max of every direction, so the
+//  support-cell tables stay valid -- MprGeom::vscale, rg_kernel.h)
+__device__ __forceinline__ void rb_geom(RbM m, const RbLds& s, const float* S, int g, MprGeom& G) {
+  const float gs = rb_geom_scale(m, s, g);
+  G.type = m.geom_type[g]; G.quat = SC(GQUAT) + 4 * g; G.size = ld3(m.geom_size + 3 * g) * gs; G.mesh = -1; G.vertadr = 0; G.nvert = 0; G.vscale = 1.f;
+  if (G.type == RG_GEOM_MESH) { G.mesh = m.geom_dataid[g]; G.vertadr = m.mesh_vertadr[G.mesh]; G.nvert = m.mesh_vertnum[G.mesh]; G.vscale = gs; }
 }
 __device__ __forceinline__ void rb_make_frame(float* f) {   // mju_makeFrame: f[0..2] given, tangents completed (as oracle make_frame)
   make_frame(f);
@@ -1336,21 +1364,23 @@ __device__ __forceinline__ void rb_broadphase(RbM m, RbLds& s, float* S, int fla
       const float margin = rb_pair_margin(m, S, p);
       const v3 P1 = ld3(gpos + 3 * g1), P2 = ld3(gpos + 3 * g2), dif = P2 - P1;
       const float* bb = m.b_geom_aabb + 6 * g2;
+      // (per-env geom scale: the bounding radius and the oriented box of a flagged geom scale with it, both about the geom's origin)
+      const float s1 = rb_geom_scale(m, s, g1), s2 = rb_geom_scale(m, s, g2);
       if (t1 == RG_GEOM_PLANE) {
         const v3 pn = qrot(ldq(gquat + 4 * g1), mk3(0, 0, 1));
-        keep = dot(dif, pn) <= m.geom_rbound[g2] + margin;
+        keep = dot(dif, pn) <= m.geom_rbound[g2] * s2 + margin;
         if (keep && obb) {
           const q4 q2 = ldq(gquat + 4 * g2);
-          const v3 c2 = dif + qrot(q2, ld3(bb)), nl = qrotT(q2, pn);
-          keep = dot(c2, pn) - (bb[3] * fabsf(nl.x) + bb[4] * fabsf(nl.y) + bb[5] * fabsf(nl.z)) <= margin + 1e-5f;
+          const v3 c2 = dif + qrot(q2, ld3(bb) * s2), nl = qrotT(q2, pn);
+          keep = dot(c2, pn) - s2 * (bb[3] * fabsf(nl.x) + bb[4] * fabsf(nl.y) + bb[5] * fabsf(nl.z)) <= margin + 1e-5f;
         }
       } else {
-        const float bound = m.geom_rbound[g1] + m.geom_rbound[g2] + margin;
+        const float bound = m.geom_rbound[g1] * s1 + m.geom_rbound[g2] * s2 + margin;
         keep = dot(dif, dif) <= bound * bound;
         if (keep && obb) {
           const float* ba = m.b_geom_aabb + 6 * g1;
           const q4 q1 = ldq(gquat + 4 * g1), q2 = ldq(gquat + 4 * g2);
-          keep = !rb_obb_apart(qrot(q1, ld3(ba)), q1, ld3(ba + 3), dif + qrot(q2, ld3(bb)), q2, ld3(bb + 3), margin);
+          keep = !rb_obb_apart(qrot(q1, ld3(ba) * s1), q1, ld3(ba + 3) * s1, dif + qrot(q2, ld3(bb) * s2), q2, ld3(bb + 3) * s2, margin);
         }
       }
       special = multipoint && m.geom_type[g2] == RG_GEOM_BOX && (t1 == RG_GEOM_BOX || t1 == RG_GEOM_PLANE);
@@ -1384,7 +1414,7 @@ __device__ __forceinline__ void rb_narrow_convex(RbM m, RbLds& s, float* S, int 
       p = cand[ci];
       const int g1 = m.b_pair_geom[3 * p], g2 = m.b_pair_geom[3 * p + 1];
       margin = rb_pair_margin(m, S, p);
-      rb_geom(m, S, g1, A); rb_geom(m, S, g2, B);
+      rb_geom(m, s, S, g1, A); rb_geom(m, s, S, g2, B);
       p1 = ld3(gpos + 3 * g1);
       A.pos = mk3(0, 0, 0); B.pos = ld3(gpos + 3 * g2) - p1;
       plane = A.type == RG_GEOM_PLANE;
@@ -1440,12 +1470,14 @@ __device__ __forceinline__ void rb_narrow_box(RbM m, RbLds& s, float* S, int fla
         if (m.geom_type[g2] == RG_GEOM_BOX && (t1 == RG_GEOM_BOX || t1 == RG_GEOM_PLANE)) {
           const float margin = rb_pair_margin(m, S, p);
           const v3 P1 = ld3(gpos + 3 * g1), t = ld3(gpos + 3 * g2) - P1;
+          const float s2 = rb_geom_scale(m, s, g2);   // (per-env size factor of flagged boxes)
           if (t1 == RG_GEOM_BOX) {
-            const float A[3] = {m.geom_size[3 * g1], m.geom_size[3 * g1 + 1], m.geom_size[3 * g1 + 2]}, B[3] = {m.geom_size[3 * g2], m.geom_size[3 * g2 + 1], m.geom_size[3 * g2 + 2]};
+            const float s1 = rb_geom_scale(m, s, g1);
+            const float A[3] = {m.geom_size[3 * g1] * s1, m.geom_size[3 * g1 + 1] * s1, m.geom_size[3 * g1 + 2] * s1}, B[3] = {m.geom_size[3 * g2] * s2, m.geom_size[3 * g2 + 1] * s2, m.geom_size[3 * g2 + 2] * s2};
             hit = box_box_lane(A, B, ldq(gquat + 4 * g1), ldq(gquat + 4 * g2), P1, t, margin, l, dist, pos, nrm);
           } else {
             nrm = qrot(ldq(gquat + 4 * g1), mk3(0, 0, 1));
-            hit = rb_plane_box_lane(nrm, t, ldq(gquat + 4 * g2), ld3(m.geom_size + 3 * g2), margin, l, dist, pos);
+            hit = rb_plane_box_lane(nrm, t, ldq(gquat + 4 * g2), ld3(m.geom_size + 3 * g2) * s2, margin, l, dist, pos);
             pos = pos + P1; planebox = true;
           }
         }
@@ -1508,7 +1540,7 @@ __device__ __forceinline__ void rb_make_constraint(RbM m, RbLds& s, float* S, co
     const float diag = ten ? tiw[id] : diw[id], floss = ten ? m.tendon_frictionloss[id] : PRM(dof_frictionloss, RB_P_DOF_FRICTIONLOSS)[id];
     const float imp = rb_impedance(solimp, 0.f, 0.f);
     const float Rr = fmaxf(RB_MINVAL, (1.f - imp) * diag / imp);
-    float K, B; rb_KB(m.timestep, solref, solimp, K, B);
+    float K, B; rb_KB(s.timestep, solref, solimp, K, B);
     R[RB_RR_TYPE] = ten ? 1.f : 0.f; R[RB_RR_ID] = (float)id; R[RB_RR_AUX] = 1.f; R[RB_RR_FLOSS] = floss; R[RB_RR_D] = 1.f / Rr;
     R[RB_RR_AREF] = -B * rb_srow_dot(m, S, ten ? 1 : 0, id, 1.f, s.qvel);
   }
@@ -1539,7 +1571,7 @@ __device__ __forceinline__ void rb_make_constraint(RbM m, RbLds& s, float* S, co
         const float diag = ten ? tiw[id] : diw[m.jnt_dofadr[id]];
         const float imp = rb_impedance(solimp, dist, margin);
         const float Rr = fmaxf(RB_MINVAL, (1.f - imp) * diag / imp);
-        float K, B; rb_KB(m.timestep, solref, solimp, K, B);
+        float K, B; rb_KB(s.timestep, solref, solimp, K, B);
         R[RB_RR_TYPE] = ten ? 3.f : 2.f; R[RB_RR_ID] = (float)id; R[RB_RR_AUX] = (float)(-side); R[RB_RR_FLOSS] = 0.f; R[RB_RR_D] = 1.f / Rr;
         R[RB_RR_AREF] = -B * rb_srow_dot(m, S, ten ? 3 : 2, id, (float)(-side), s.qvel) - K * imp * (dist - margin);
       }
@@ -1565,7 +1597,7 @@ __device__ __forceinline__ void rb_make_constraint(RbM m, RbLds& s, float* S, co
           const float diag = ten ? tiw[id] : diw[m.jnt_dofadr[id]];
           const float imp = rb_impedance(solimp, dist, margin);
           const float Rr = fmaxf(RB_MINVAL, (1.f - imp) * diag / imp);
-          float K, B; rb_KB(m.timestep, solref, solimp, K, B);
+          float K, B; rb_KB(s.timestep, solref, solimp, K, B);
           R[RB_RR_TYPE] = ten ? 3.f : 2.f; R[RB_RR_ID] = (float)id; R[RB_RR_AUX] = (float)(-side); R[RB_RR_FLOSS] = 0.f; R[RB_RR_D] = 1.f / Rr;
           R[RB_RR_AREF] = -B * rb_srow_dot(m, S, ten ? 3 : 2, id, (float)(-side), s.qvel) - K * imp * (dist - margin);
           n++;
@@ -1680,7 +1712,7 @@ __device__ __forceinline__ void rb_make_constraint(RbM m, RbLds& s, float* S, co
       for (int q = nnz; q < RB_CONW; q++) idx[q] = -1;
       const int adr = (int)C[RB_CR_ADR];
       if (adr < 0) continue;
-      float K, B; rb_KB(m.timestep, C + RB_CR_SOLREF, C + RB_CR_SOLIMP, K, B);
+      float K, B; rb_KB(s.timestep, C + RB_CR_SOLREF, C + RB_CR_SOLIMP, K, B);
       for (int k = 0; k < dim; k++) {
         const float pos = C[RB_CR_FRAME + (dim == 1 ? 0 : k)];
         const float imp = rb_impedance(C + RB_CR_SOLIMP, pos, 0.f);
@@ -1753,7 +1785,7 @@ __device__ __forceinline__ void rb_make_constraint(RbM m, RbLds& s, float* S, co
     const float tran = biw[2 * b1] + biw[2 * b2], rot = biw[2 * b1 + 1] + biw[2 * b2 + 1];
     const float dist = C[RB_CR_DIST], incl = C[RB_CR_INCL];
     const float imp = rb_impedance(C + RB_CR_SOLIMP, dist, incl);
-    float K, B; rb_KB(m.timestep, C + RB_CR_SOLREF, C + RB_CR_SOLIMP, K, B);
+    float K, B; rb_KB(s.timestep, C + RB_CR_SOLREF, C + RB_CR_SOLIMP, K, B);
     if (!bd_done) for (int r = 0; r < 6; r++) { float v = 0; for (int e = 0; e < nnz; e++) v += J[r * RB_CONW + e] * s.qvel[idx[e]]; bd[r] = v; }
     if (dim == 1) {
       float* R = row + RB_ROWREC * adr;
@@ -2516,7 +2548,7 @@ RB_STAGE float sv_line_search(RbCtx c, float gauss, float q1, float q2, float gt
 // dst = inv(M + h B) src of every group: mode 0 qacc_smooth = inv(M) qfrc_smooth (h = 0), mode 1 search = inv(M + h B) grad (the Euler step)
 RB_STAGE void sv_M_solve(RbCtx c, int mode, int flags) {
   RB_STAGE_ENTER();
-  const float* diag = mode ? PRM(dof_damping, RB_P_DOF_DAMPING) : (const float*)0; const float h = mode ? m.timestep : 0.f;
+  const float* diag = mode ? PRM(dof_damping, RB_P_DOF_DAMPING) : (const float*)0; const float h = mode ? s.timestep : 0.f;
   const float* src = mode ? s.grad : s.qfrc_smooth; float* dst = mode ? s.search : s.qacc_smooth;
   if (m.b_tree8[0] > 0 && !(flags & 4)) { rb_trees8_solve(m, s, SC(MSP), diag, h, src, dst, 1.f); return; }
   for (int grp = 0; grp < m.ngroup; grp++) {
@@ -2615,7 +2647,7 @@ __device__ __forceinline__ int rb_solve(RbCtx cx, RbM m, RbLds& s, float* S, int
 // ------------------------------------------------------------------------------------------------- integration
 // mj_Euler: implicit in joint damping, quaternion integration
 __device__ __forceinline__ void rb_euler(RbCtx cx, RbM m, RbLds& s, float* S, int flags) {
-  const float h = m.timestep;
+  const float h = s.timestep;
   BFOR(i, m.nv) s.grad[i] = s.qfrc_smooth[i] + s.qfrc_con[i];
   BSYNC();
   sv_M_solve(cx, 1, flags);
@@ -2664,6 +2696,11 @@ __device__ __forceinline__ void rb_sensors(RbM m, RbLds& s, float* S, float* out
       const v3 tq = t + cross(off, f);
       const float sg = (b == b2 ? 1.f : 0.f) - (b == b1 ? 1.f : 0.f);
       acc[0] += sg * tq.x; acc[1] += sg * tq.y; acc[2] += sg * tq.z; acc[3] += sg * f.x; acc[4] += sg * f.y; acc[5] += sg * f.z;
+    }
+    if (s.has_xfrc && b > 0) {   // xfrc_applied: force / torque at the body's com, moved to the com-frame origin of its tree (oracle ro_rne_post_constraint)
+      const float* w = S + m.prm_off[RB_P_XFRC] + 6 * b;
+      const v3 f = ld3(w), tq = ld3(w + 3) + cross(ld3(SC(XIPOS) + 3 * b) - ld3(rootcom + 3 * m.body_rootid[b]), f);
+      acc[0] += tq.x; acc[1] += tq.y; acc[2] += tq.z; acc[3] += f.x; acc[4] += f.y; acc[5] += f.z;
     }
     for (int k = 0; k < 6; k++) cext[6 * b + k] = acc[k];
   }
@@ -2743,12 +2780,26 @@ __device__ __forceinline__ void rb_step_body(const RbModelDev* mp, RbKlp klp, co
   BFOR(i, nq) s.qpos[i] = L.bt.qpos[(size_t)e * nq + i];
   BFOR(i, nv) { s.qvel[i] = L.bt.qvel[(size_t)e * nv + i]; s.warm[i] = L.bt.qacc_warmstart[(size_t)e * nv + i]; }
   BFOR(i, 3 * nu) s.pid[i] = L.bt.pid[(size_t)e * 3 * nu + i];
-  if (TID == 0) { s.status = L.bt.status[e]; s.stop = 0; s.neqcon = 0; s.time = L.bt.time[e]; s.env = e; }
+  if (TID == 0) {
+    s.status = L.bt.status[e]; s.stop = 0; s.neqcon = 0; s.time = L.bt.time[e]; s.env = e;
+    s.timestep = m.prm_on ? S[m.prm_off[RB_P_TIMESTEP]] : m.timestep; s.gscale = m.prm_on ? S[m.prm_off[RB_P_GEOM_SCALE]] : 1.f; s.has_xfrc = 0; s.mass_default = 1;
+  }
   if (TID < 16) s.prof[TID] = 0.f;
   if (TID < 7 * m.nmocap && TID < 14) s.mocap[TID] = L.bt.mocap[(size_t)e * 7 * m.nmocap + TID];
   const float* eqd = m.neq > 0 ? L.bt.eq_data + (size_t)e * 7 * m.neq : (const float*)0;
   const int* eqa = m.neq > 0 ? L.bt.eq_active + (size_t)e * m.neq : (const int*)0;
   BSYNC();
+  if (m.prm_on) {   // "any external wrench?", once per launch: an env whose xfrc_applied rows are all zero executes what a model without them executes
+    float nz = 0; BFOR(i, 6 * m.nbody) nz += S[m.prm_off[RB_P_XFRC] + i] != 0.f ? 1.f : 0.f;
+    nz = rb_sum(s, nz);
+    if (TID == 0) s.has_xfrc = nz > 0.f;
+    if (RB_NWAVE != 1) {   // (only the large configuration reads it, rb_com_pos)
+      float nm = 0; BFOR(b, m.nbody) nm += S[m.prm_off[RB_P_BODY_MASS] + b] != m.body_mass[b] ? 1.f : 0.f;
+      nm = rb_sum(s, nm);
+      if (TID == 0) s.mass_default = !(nm > 0.f);
+    }
+    BSYNC();
+  }
   // ---- action -> ctrl (robot_interface.py:247-278 with the hand's position -> control matrix)
   bool use_action = L.bt.action != 0 && !(L.bt.hold && L.bt.hold[e]);
   if (use_action) {
@@ -2869,7 +2920,7 @@ __device__ __forceinline__ void rb_step_body(const RbModelDev* mp, RbKlp klp, co
     if (rb_sum(s, bd) > 0) { if (TID == 0) s.status |= RG_STATUS_BAD_STATE; break; }
     BFOR(i, nv) s.warm[i] = s.qa[i];
     sb_euler(c, flags); RB_PROF(7);
-    if (TID == 0) s.time += m.timestep;
+    if (TID == 0) s.time += s.timestep;
     BSYNC();
   }
   if ((flags & 2) && TID < 16) SC(DBG)[8 + 5 * nv + TID] = s.prof[TID];   // stage cycle counters: frames+com, tendon+crb, velocity, collision, rows, smooth, Newton, Euler
@@ -2915,7 +2966,7 @@ __device__ __forceinline__ void rb_step_body(const RbModelDev* mp, RbKlp klp, co
   BFOR(i, 3 * nu) L.bt.pid[(size_t)e * 3 * nu + i] = s.pid[i];
   BFOR(u, nu) L.bt.ctrl[(size_t)e * nu + u] = s.ctrl[u];
   if (TID == 0) {
-    L.bt.status[e] = s.status; L.bt.time[e] += nsub_done * m.timestep;
+    L.bt.status[e] = s.status; L.bt.time[e] += nsub_done * s.timestep;
     float* st = L.bt.stats + 4 * (size_t)e; st[0] += st_ncon; st[1] += st_nefc; st[2] += st_iter; st[3] += nsub_done;
   }
 }

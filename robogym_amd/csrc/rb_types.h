@@ -67,7 +67,11 @@ enum {
 enum {
   RB_P_GRAVITY, RB_P_DOF_DAMPING, RB_P_DOF_ARMATURE, RB_P_DOF_FRICTIONLOSS, RB_P_DOF_INVWEIGHT0, RB_P_JNT_STIFFNESS, RB_P_JNT_MARGIN, RB_P_JNT_RANGE,
   RB_P_BODY_POS, RB_P_BODY_MASS, RB_P_BODY_INERTIA, RB_P_BODY_INVWEIGHT0, RB_P_ACT_GAINPRM, RB_P_ACT_FORCERANGE, RB_P_ACT_CTRLRANGE,
-  RB_P_GEOM_POS, RB_P_GEOM_MARGIN, RB_P_GEOM_GAP, RB_P_GEOM_FRICTION, RB_P_GEOM_SOLREF, RB_P_GEOM_SOLIMP, RB_P_TENDON_RANGE, RB_P_TENDON_INVWEIGHT0, RB_NPRMF
+  RB_P_GEOM_POS, RB_P_GEOM_MARGIN, RB_P_GEOM_GAP, RB_P_GEOM_FRICTION, RB_P_GEOM_SOLREF, RB_P_GEOM_SOLIMP, RB_P_TENDON_RANGE, RB_P_TENDON_INVWEIGHT0,
+  // what the dactyl randomization stack writes per step or per episode (as rg_types.h RG_PRM_TIMESTEP / XFRC / SITE_POS / GEOM_SCALE on the hand stepper), appended
+  // so that the fields above keep their indices: opt.timestep (1 word), mjData.xfrc_applied ([nbody][6]: force then torque, world frame, at the body's com),
+  // site_pos ([nsite][3]) and ONE size factor for the geoms the model flags in b_geom_scaled (meshes and boxes)
+  RB_P_TIMESTEP, RB_P_XFRC, RB_P_SITE_POS, RB_P_GEOM_SCALE, RB_NPRMF
 };
 // per contact record (floats): dist, pos3, frame9, includemargin, friction5, solref2, solimp5, dim, geom1, geom2, efc_address, nnz, kind
 // kind: 0 pyramidal contact, 1 elliptic contact (ur16e/base.xml:3), 2 equality constraint (weld: dim 6, joint coupling: dim 1) — an
@@ -124,6 +128,8 @@ struct RbModelDev {
   int prm_on;                        // per-env parameter blocks in the scratch rows (rb_model_enable_env_params)
   int prm_off[RB_NPRMF];             // word offset of each field from the start of the scratch row
   int prm_words;
+  const int* b_geom_scaled;          // [ngeom] geoms whose size follows the env's RB_P_GEOM_SCALE (optional blob key; absent: none)
+  int ngeom_scaled;                  // how many it flags (0: the kernel never looks at the table)
 #define X(n) const int* n;
   RB_INT_ARRAYS(X)
 #undef X

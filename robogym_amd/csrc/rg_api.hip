@@ -89,6 +89,7 @@ static hipError_t hipFree(void* p) { free(p); return 0; }
 enum { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice };
 static hipError_t hipMemcpy(void* d, const void* s, size_t n, int) { memcpy(d, s, n); return 0; }
 static hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return 0; }
+static hipError_t hipMemset2D(void* d, size_t pitch, int v, size_t w, size_t h) { for (size_t r = 0; r < h; r++) memset((char*)d + r * pitch, v, w); return 0; }
 static hipError_t hipSetDevice(int) { return 0; }
 static hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
 static hipError_t hipDeviceSynchronize() { return 0; }
@@ -1039,6 +1040,19 @@ rb_model* rb_model_create(const void* blob, size_t nbytes, char* err, int errlen
 #define X(n) if (!get_f(B, #n, fv, e)) return bail(e, m); if (!rb_upload_bytes(m, fv.data(), fv.size() * 4, (const void**)&d.n)) return bail("hipMalloc failed", m);
   RB_FLT_ARRAYS(X)
 #undef X
+  {  // optional: the geoms whose size follows the env's RB_P_GEOM_SCALE.  Meshes and boxes only (vertices / half extents, bounding radius and oriented box all scale
+     // exactly about the geom's origin), and no tendon wrap object (rb_tendon reads the model's own sizes)
+    std::vector<int> gsc(d.ngeom, 0), gt, wt, wo;
+    if (B.find("b_geom_scaled")) {
+      if (!get_i(B, "b_geom_scaled", gsc, e) || !get_i(B, "geom_type", gt, e) || !get_i(B, "wrap_type", wt, e) || !get_i(B, "wrap_objid", wo, e)) return bail(e, m);
+      if ((int)gsc.size() != d.ngeom || (int)gt.size() != d.ngeom) return bail("b_geom_scaled: one flag per geom expected", m);
+      for (size_t w = 0; w < wt.size() && w < wo.size(); w++)   // (sphere / cylinder wraps: the object is a geom; named before the type check, which it would fail as well)
+        if ((wt[w] == RG_WRAP_SPHERE || wt[w] == RG_WRAP_CYLINDER) && wo[w] >= 0 && wo[w] < d.ngeom && gsc[wo[w]]) return bail("b_geom_scaled flags a geom that a tendon wraps around", m);
+      for (int g = 0; g < d.ngeom; g++) if (gsc[g] && gt[g] != RG_GEOM_MESH && gt[g] != RG_GEOM_BOX) return bail("b_geom_scaled flags a geom that is neither a mesh nor a box", m);
+    }
+    d.ngeom_scaled = 0; for (int v : gsc) d.ngeom_scaled += v != 0;
+    if (!rb_upload_bytes(m, gsc.data(), gsc.size() * 4, (const void**)&d.b_geom_scaled)) return bail("hipMalloc failed", m);
+  }
   if (!get_i(B, "b_fric_dof", iv, e)) return bail(e, m); d.nfric_dof = (int)iv.size();
   if (!get_i(B, "b_fric_ten", iv, e)) return bail(e, m); d.nfric_ten = (int)iv.size();
   if (!get_i(B, "b_lim_jnt", iv, e)) return bail(e, m); d.nlim_jnt = (int)iv.size();
@@ -1076,11 +1090,22 @@ rb_model* rb_model_create(const void* blob, size_t nbytes, char* err, int errlen
     for (int bb = 0; bb < d.nbody; bb++) if (mid[bb] >= 0 && mid[bb] < d.nmocap) { for (int k = 0; k < 3; k++) m->mocap0[7 * mid[bb] + k] = bp[3 * bb + k]; for (int k = 0; k < 4; k++) m->mocap0[7 * mid[bb] + 3 + k] = bq[4 * bb + k]; }
   }
   {  // the model's own values of the per-env parameter fields, in block order (rb_types.h RB_P_*)
-    static const char* fields[RB_NPRMF] = {"opt_gravity", "dof_damping", "dof_armature", "dof_frictionloss", "dof_invweight0", "jnt_stiffness", "jnt_margin", "jnt_range",
-                                           "body_pos", "body_mass", "body_inertia", "body_invweight0", "actuator_gainprm", "actuator_forcerange", "actuator_ctrlrange",
-                                           "geom_pos", "geom_margin", "geom_gap", "geom_friction", "geom_solref", "geom_solimp", "tendon_range", "tendon_invweight0"};
+    // (xfrc_applied and geom_scale are not model arrays: zeros, [nbody][6], and one factor of 1)
+    static const char* fields[] = {"opt_gravity", "dof_damping", "dof_armature", "dof_frictionloss", "dof_invweight0", "jnt_stiffness", "jnt_margin", "jnt_range",
+                                   "body_pos", "body_mass", "body_inertia", "body_invweight0", "actuator_gainprm", "actuator_forcerange", "actuator_ctrlrange",
+                                   "geom_pos", "geom_margin", "geom_gap", "geom_friction", "geom_solref", "geom_solimp", "tendon_range", "tendon_invweight0",
+                                   "opt_timestep", nullptr, "site_pos", nullptr};
+    static_assert(sizeof fields / sizeof fields[0] == RB_NPRMF, "one blob key (or null) per RB_P_* field");
+    static_assert(sizeof m->prm_len / sizeof m->prm_len[0] == RB_NPRMF && sizeof d.prm_off / sizeof d.prm_off[0] == RB_NPRMF, "one length and one offset per RB_P_* field");
+    static_assert(RB_NPRMF == 27, "rb_prm_layout reports 27 fields: robogym_amd/_native.py RB_PRM_NAMES and include/rgstep.h name them in this order");
     std::vector<std::vector<float>> vals(RB_NPRMF);
-    for (int k = 0; k < RB_NPRMF; k++) { if (!get_f(B, fields[k], vals[k], e)) return bail(e, m); m->prm_len[k] = (int)vals[k].size(); }
+    for (int k = 0; k < RB_NPRMF; k++) {
+      if (k == RB_P_XFRC) vals[k].assign((size_t)6 * d.nbody, 0.f);
+      else if (k == RB_P_GEOM_SCALE) vals[k].assign(1, 1.f);
+      else if (!get_f(B, fields[k], vals[k], e)) return bail(e, m);
+      m->prm_len[k] = (int)vals[k].size();
+    }
+    if (m->prm_len[RB_P_TIMESTEP] != 1 || m->prm_len[RB_P_SITE_POS] != 3 * d.nsite) return bail("rb_model_create: opt_timestep / site_pos have the wrong length", m);
     m->prm_default.clear();
     for (int k = 0; k < RB_NPRMF; k++) { m->prm_default.insert(m->prm_default.end(), vals[k].begin(), vals[k].end()); m->prm_default.resize((m->prm_default.size() + 3) & ~(size_t)3, 0.f); }
   }
@@ -1318,6 +1343,8 @@ int rb_batch_reset(rb_batch* b) {
     HIPCHK(hipMemcpy(s.mocap, mc.data(), mc.size() * 4, hipMemcpyHostToDevice));
   }
   if (d.nsensordata) HIPCHK(hipMemset(s.sensordata, 0, (size_t)s.B * d.nsensordata * 4));
+  // mj_resetData clears mjData.xfrc_applied (the other parameter rows are MODEL fields and survive a reset)
+  if (d.prm_on) HIPCHK(hipMemset2D(s.scratch + d.prm_off[RB_P_XFRC], (size_t)d.scratch_words * 4, 0, (size_t)6 * d.nbody * 4, (size_t)s.B));
   return 0;
 }
 rb_batch* rb_batch_create(const rb_model* m, int B) {

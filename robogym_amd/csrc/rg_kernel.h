@@ -758,7 +758,9 @@ __device__ __forceinline__ void rg_M_to_blocks(RgM m, RgLds& s) {
 struct SupPt { v3 v, s; };  // v = v1 - v2 (Minkowski difference), s = v1 + v2 (all the contact position needs)
 // per-query (lane-varying) description of one geom, and the wave-uniform tables every query shares: keeping the
 // 64-bit table pointers out of MprGeom keeps them in SGPRs (the narrowphase is the register-hungriest stage)
-struct MprGeom { int type; const float* quat; v3 pos; v3 size; int vertadr, nvert, mesh; float margin; };   // quat: the geom's orientation in LDS (16-byte aligned)   // mesh: id, -1 for primitives
+// vscale: uniform factor on a mesh's vertices (rb_kernel.h's per-env RB_P_GEOM_SCALE).  A positive uniform scale keeps the arg-max of every direction, so the scans
+// and the support-cell tables stay valid and only the winning vertex is scaled; callers that never set it (this kernel) multiply by a constant 1, which folds away.
+struct MprGeom { int type; const float* quat; v3 pos; v3 size; int vertadr, nvert, mesh; float margin; float vscale = 1.f; };   // quat: the geom's orientation in LDS (16-byte aligned)   // mesh: id, -1 for primitives
 struct MprEnv { const float* mesh_vert; const int* cell_adr; const rgf4 *cell_blk, *cell_ovf; float* prof; bool cells; bool plane_depth; };
 
 // per-lane scan of a hull's vertices: 16-byte records (one dwordx4 load per vertex), four independent
@@ -862,7 +864,7 @@ template <int G> __device__ __forceinline__ v3 rg_support(const MprEnv& E, const
   if (g.type == RG_GEOM_MESH) {
     float bv = -3.0e38f; int bi = 0x7fffffff; v3 bp = mk3(0, 0, 0);
     scan_hull<G>(E, g, ld, bv, bi, bp);
-    lr = pick_vert<G>(bv, bi, bp);
+    lr = pick_vert<G>(bv, bi, bp) * g.vscale;
   } else lr = support_primitive(g, ld);
   lr = lr + ld * g.margin;
   return qrot(gq, lr) + g.pos;
@@ -878,8 +880,8 @@ template <int G> __device__ __forceinline__ void mpr_support(const MprEnv& E, co
   if (am) scan_hull<G>(E, a, la, av, ai, ap);
   if (bm) scan_hull<G>(E, b, lb, bvv, bi, bp);
   long long tt1 = E.prof ? rg_clock() : 0;
-  ra = am ? pick_vert<G>(av, ai, ap) : support_primitive(a, la);
-  rb = bm ? pick_vert<G>(bvv, bi, bp) : support_primitive(b, lb);
+  ra = am ? pick_vert<G>(av, ai, ap) * a.vscale : support_primitive(a, la);
+  rb = bm ? pick_vert<G>(bvv, bi, bp) * b.vscale : support_primitive(b, lb);
   v3 w1 = qrot(qa, ra + la * a.margin) + a.pos;
   v3 w2 = qrot(qb, rb + lb * b.margin) + b.pos;
   p.v = w1 - w2; p.s = w1 + w2;

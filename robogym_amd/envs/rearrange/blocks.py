@@ -747,6 +747,7 @@ class BatchedBlockRearrangeEnv:
         _native.check(self._L, self._L.ra_env_recipe_step(self.sim._bh, None if self.solver_sim is None else self.solver_sim._bh, ctypes.byref(r), self._stream()), "ra_env_recipe_step")
         if self.per_env_parameters:
             P = self.sim.params
+            # (the block also holds mjData.xfrc_applied, whose default is zero: a re-created simulation starts without applied wrenches, as after mj_resetData)
             P.block.copy_(torch.where(self.ended[:, None], self._param_block_default[None, :], P.block))
             d, cols = P["dof_damping"], self.obj_dofs
             cur = d[:, cols]

@@ -186,6 +186,15 @@ def derive_big_tables(model):
         else:
             raise NotImplementedError("geom type %d" % t)
     A["b_geom_aabb"] = aabb.reshape(-1)
+    # geoms whose size follows the env's `geom_scale` parameter row (rb_types.h RB_P_GEOM_SCALE): the cubelets of the Rubik's cube, the set
+    # PerpendicularCubeSizeModifier("cube:") rescales -- geoms named cube:cubelet:* (their geom_rbound) and, because the modifier scales the VERTEX TABLE of their
+    # mesh, every other geom that shares that mesh (rubik_perpendicular.xml leaves the geom of cubelet pos_x_neg_y without a name: its hull grows with the others;
+    # the reference leaves that one geom's geom_rbound alone, here its bounding sphere scales with its hull).  The cubelets' body_pos is a row of its own.
+    # Compare kernel_tables.py k_geom_scaled.
+    gnames, gdata = model.names["geom"], A["geom_dataid"]
+    named = [g for g, n in enumerate(gnames) if n.startswith("cube:cubelet:") and int(gt[g]) in (C.GEOM_MESH, C.GEOM_BOX)]
+    meshes = {int(gdata[g]) for g in named if int(gt[g]) == C.GEOM_MESH}
+    A["b_geom_scaled"] = _i32([1 if (g in named or (int(gt[g]) == C.GEOM_MESH and int(gdata[g]) in meshes)) else 0 for g in range(len(gt))])
     # mesh vertices as 16-byte records (x, y, z, vertex index): what the hull scans of the collision code read
     mv = np.asarray(A["mesh_vert"], dtype=np.float32).reshape(-1, 3)
     rec = np.zeros((len(mv), 4), dtype=np.float32)

@@ -28,7 +28,7 @@ class LargeModelSimulation:
         self.device = torch.device("cpu") if self._emul else torch.device(device)
         if not self._emul and not torch.cuda.is_available():
             raise _native.NativeError("LargeModelSimulation needs an MI355X (no CPU fallback)")
-        if "b_dims" not in model.arrays or "b_tree_desc" not in model.arrays or "b_Mlong" not in model.arrays or "b_tree8" not in model.arrays or "b_geom_aabb" not in model.arrays or "b_body_level" not in model.arrays:
+        if "b_dims" not in model.arrays or "b_tree_desc" not in model.arrays or "b_Mlong" not in model.arrays or "b_tree8" not in model.arrays or "b_geom_aabb" not in model.arrays or "b_body_level" not in model.arrays or "b_geom_scaled" not in model.arrays:
             derive_big_tables(model)
         self.model, self.batch_size, self.n_substeps = model, int(batch_size), int(n_substeps)
         blob = pack_model(model)
@@ -130,8 +130,10 @@ class LargeModelSimulation:
     def params(self) -> "LargeEnvParams":
         """`sim.model.<field>` of the reference for a batch on this stepper: `[B, ...]` tensor views into the envs' parameter blocks (include/rgstep.h
         rb_model_enable_env_params): gravity, dof_damping / armature / frictionloss / invweight0, jnt_stiffness / margin / range, body_pos / mass / inertia /
-        invweight0, actuator_gainprm / forcerange / ctrlrange, geom_pos / margin / gap / friction / solref / solimp, tendon_range / invweight0.  The simulation
-        must have been created with `env_params=True`."""
+        invweight0, actuator_gainprm / forcerange / ctrlrange, geom_pos / margin / gap / friction / solref / solimp, tendon_range / invweight0, and what the dactyl
+        randomization stack writes: timestep [B, 1], xfrc_applied [B, nbody, 6] (`sim.data.xfrc_applied`: force then torque, world frame, at the body's com; cleared
+        by `reset`), site_pos [B, nsite, 3], geom_scale [B, 1] (one size factor for the geoms of `b_geom_scaled`).  The simulation must have been created with
+        `env_params=True`."""
         if not self._env_params:
             raise _native.NativeError("this simulation was created without per-env parameter rows (LargeModelSimulation(..., env_params=True))")
         if self._params is None:
@@ -191,7 +193,8 @@ class LargeEnvParams:
         assert n == len(buf) and buf[0] == 1, "rb_prm_layout and robogym_amd/_native.py disagree"
         rows = sim.view(_native.RG_F_DEBUG)          # the whole scratch row [B, scratch_words]
         shape_of = dict(gravity=(3,), jnt_range=(-1, 2), body_pos=(-1, 3), body_inertia=(-1, 3), body_invweight0=(-1, 2), actuator_gainprm=(-1, 10), actuator_forcerange=(-1, 2),
-                        actuator_ctrlrange=(-1, 2), geom_pos=(-1, 3), geom_friction=(-1, 3), geom_solref=(-1, 2), geom_solimp=(-1, 5), tendon_range=(-1, 2))
+                        actuator_ctrlrange=(-1, 2), geom_pos=(-1, 3), geom_friction=(-1, 3), geom_solref=(-1, 2), geom_solimp=(-1, 5), tendon_range=(-1, 2),
+                        xfrc_applied=(-1, 6), site_pos=(-1, 3))      # (timestep and geom_scale stay [B, 1], as on the hand stepper)
         self._views: Dict[str, torch.Tensor] = {}
         B = sim.batch_size
         lo = min(int(buf[2 + 2 * k]) for k in range(len(_native.RB_PRM_NAMES)))

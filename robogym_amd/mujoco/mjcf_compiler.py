@@ -274,6 +274,19 @@ class CompiledModel:
         m.names = self.names
         m.arrays = {k: v.copy() for k, v in self.arrays.items()}
         for k, v in overrides.items():
+            # The names of the per-env parameter rows that are not model arrays (LargeEnvParams).  Callers build an env's own model from EVERY row read back from
+            # `sim.params` (tests/test_rearrange_env.py does, key by key), so the three rows without a model array of their name must be accepted here: the timestep
+            # under its row name, and the two that no model array can carry only at their neutral values.
+            if k == "timestep":
+                k = "opt_timestep"
+            elif k == "xfrc_applied":      # mjData, not mjModel
+                if np.any(np.asarray(v) != 0):
+                    raise ValueError("copy_with(xfrc_applied=...): an applied wrench is simulation data, write it into the simulation")
+                continue
+            elif k == "geom_scale":        # scaling a model means new vertices, bounds AND derived tables: the caller writes those arrays (and re-derives)
+                if float(np.asarray(v).reshape(-1)[0]) != 1.0:
+                    raise ValueError("copy_with(geom_scale=...): pass the scaled mesh_vert / geom_size / geom_rbound themselves and re-derive the tables")
+                continue
             m.arrays[k] = np.asarray(v, dtype=self.arrays[k].dtype).reshape(self.arrays[k].shape).copy()
         return m
 
