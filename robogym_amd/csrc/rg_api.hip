@@ -80,20 +80,14 @@ extern char** environ;
 #include <vector>
 
 #ifdef RG_EMUL
-// CPU emulation harness (tests/emul): "device memory" is host memory
-typedef void* hipStream_t;
-typedef int hipError_t;
-#define hipSuccess 0
-static hipError_t hipMalloc(void** p, size_t n) { *p = calloc(1, n ? n : 1); return *p ? 0 : 1; }
-static hipError_t hipFree(void* p) { free(p); return 0; }
-enum { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice };
-static hipError_t hipMemcpy(void* d, const void* s, size_t n, int) { memcpy(d, s, n); return 0; }
-static hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return 0; }
-static hipError_t hipMemset2D(void* d, size_t pitch, int v, size_t w, size_t h) { for (size_t r = 0; r < h; r++) memset((char*)d + r * pitch, v, w); return 0; }
-static hipError_t hipSetDevice(int) { return 0; }
-static hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
-static hipError_t hipDeviceSynchronize() { return 0; }
-static const char* hipGetErrorString(hipError_t) { return "emul"; }
+#include "hip_runtime_emul.h"   // CPU emulation harness: the hip* calls below, DeviceGuard and the launch on the fibers of tests/emul
+#else
+// every entry point runs on the batch's device and leaves the caller's current device as it found it
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != dev) (void)hipSetDevice(dev); else prev = -1; }
+  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
 #endif
 
 #include "rg_env_kernel.h"
@@ -156,22 +150,22 @@ static const char* hipGetErrorString(hipError_t) { return "emul"; }
 #include "rb_env_kernel.h"
 #include "ra_env_kernel.h"
 #define RG_WAVES_PER_SIMD_HOST 3   /* = RG_WAVES_PER_SIMD of rg_kernel.h (its default) */
-struct rg_batch;
-extern "C" { static void rg_items_probe(rg_batch* b); }
 
 static thread_local std::string g_err;
-#ifdef RG_EMUL
-struct DeviceGuard { explicit DeviceGuard(int) {} };
-#else
-// every entry point runs on the batch's device and leaves the caller's current device as it found it
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != dev) (void)hipSetDevice(dev); else prev = -1; }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-#endif
 static int fail(const std::string& msg) { g_err = msg; return -1; }
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+// The one launch path of both builds.  `lds_bytes` is the dynamic LDS of the launch; `emul_static_bytes` is what the kernel declares as a static __shared__ object on
+// the GPU, where the emulation harness has to provide it with the workgroup's block (emul_lds()).
+template <class... KArgs, class... Args>
+static int launch(void (*kernel)(KArgs...), int grid, int threads, size_t lds_bytes, size_t emul_static_bytes, void* stream, const Args&... args) {
+#ifdef RG_EMUL
+  emul_launch_closure(grid, threads, lds_bytes + emul_static_bytes, [=] { kernel(args...); });
+#else
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds_bytes, (hipStream_t)stream, args...);
+#endif
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 
 struct blob_entry { char name[40]; uint32_t dtype, count; uint64_t offset; };
 
@@ -213,14 +207,23 @@ struct Blob {
   }
 };
 
-template <class T> bool upload(rg_model* m, const std::vector<T>& host, const T** dst) {
+// device allocations belong to an owner (rg_model / rb_model, rg_batch / rb_batch: each has `allocs`) and are freed with it
+template <class T, class Model> bool upload(Model* m, const std::vector<T>& host, const T** dst) {
   void* p = nullptr;
   if (hipMalloc(&p, (host.size() ? host.size() : 1) * sizeof(T)) != hipSuccess) return false;
-  m->allocs.push_back(p);   // owned by the model from here on (freed by rg_model_free also on a failed create)
+  m->allocs.push_back(p);   // owned by the model from here on (freed by its *_model_free also on a failed create)
   if (host.size() && hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return false;
   *dst = (const T*)p;
   return true;
 }
+template <class Batch> void* balloc(Batch* b, size_t n) {   // zeroed
+  void* p = nullptr;
+  if (hipMalloc(&p, n ? n : 1) != hipSuccess) return nullptr;
+  hipMemset(p, 0, n ? n : 1);
+  b->allocs.push_back(p);
+  return p;
+}
+void put_err(const std::string& e, char* err, int errlen) { g_err = e; if (err && errlen > 0) { strncpy(err, e.c_str(), errlen - 1); err[errlen - 1] = 0; } }
 // the arrays a model create asked the blob for, in order (rg_model_blob_keys / rb_model_blob_keys: the schema of that model kind, stated by the reader itself)
 thread_local std::vector<std::string>* g_key_log = nullptr;
 void log_key(const char* name) { if (g_key_log && std::find(g_key_log->begin(), g_key_log->end(), name) == g_key_log->end()) g_key_log->push_back(name); }
@@ -242,6 +245,21 @@ bool get_i(const Blob& b, const char* name, std::vector<int>& out, std::string& 
   out.assign((const int*)(b.base + e->offset), (const int*)(b.base + e->offset) + e->count);
   return true;
 }
+// a failed model create: the message goes to rg_last_error and the caller's buffer, the half-built model is released
+template <class Model> Model* create_failed(const std::string& msg, Model* m, void (*release)(Model*), char* err, int errlen) {
+  g_key_log = nullptr;
+  put_err(msg, err, errlen);
+  if (m) release(m);
+  return nullptr;
+}
+// the blob readers of both model creates (they expect B, iv / fv, e, m, d and `bail` in scope)
+#define GI(name) if (!get_i(B, name, iv, e)) return bail(e, m)
+#define GF(name) if (!get_f(B, name, fv, e)) return bail(e, m)
+#define UPI(field, name) do { GI(name); if (!upload<int>(m, iv, &d.field)) return bail("hipMalloc failed", m); } while (0)
+#define UPF(field, name) do { GF(name); if (!upload<float>(m, fv, &d.field)) return bail("hipMalloc failed", m); } while (0)
+int not_recordable(const char* fn) {
+  return fail(std::string(fn) + ": not recordable -- called between rb_multi_begin and rb_multi_launch it would run AHEAD of the recorded physics launches; issue it after rb_multi_launch");
+}
 }  // namespace
 
 extern "C" {
@@ -252,28 +270,16 @@ int rg_lds_bytes(void) { return (int)rgs::rg_lds_launch_bytes(false); }
 int rg_lds_bytes_cfg(int config) { return (int)(config == RG_CFG_LARGE ? rgl::rg_lds_launch_bytes(false) : rgs::rg_lds_launch_bytes(false)); }
 
 rg_model* rg_model_create(const void* blob, size_t nbytes, char* err, int errlen) {
-  auto bail = [&](const std::string& msg, rg_model* m) -> rg_model* {
-    g_key_log = nullptr;
-    g_err = msg;
-    if (err && errlen > 0) { strncpy(err, msg.c_str(), errlen - 1); err[errlen - 1] = 0; }
-    if (m) rg_model_free(m);
-    return nullptr;
-  };
+  auto bail = [&](const std::string& msg, rg_model* m) { return create_failed(msg, m, rg_model_free, err, errlen); };
   if (!blob || nbytes < 16 || memcmp(blob, "RGMODEL1", 8) != 0) return bail("not an RGMODEL1 blob", nullptr);
   Blob B{(const char*)blob, nbytes};
   rg_model* m = new rg_model();
   g_key_log = &m->blob_keys;
-#ifndef RG_EMUL
   if (hipGetDevice(&m->device) != hipSuccess) return bail("hipGetDevice failed", m);
-#endif
   RgModelDev& d = m->dev;
   memset(&d, 0, sizeof d);
   std::string e;
   std::vector<int> iv; std::vector<float> fv;
-#define GI(name) if (!get_i(B, name, iv, e)) return bail(e, m)
-#define GF(name) if (!get_f(B, name, fv, e)) return bail(e, m)
-#define UPI(field, name) do { GI(name); if (!upload<int>(m, iv, &d.field)) return bail("hipMalloc failed", m); } while (0)
-#define UPF(field, name) do { GF(name); if (!upload<float>(m, fv, &d.field)) return bail("hipMalloc failed", m); } while (0)
   GI("dims");
   d.nq = iv[0]; d.nv = iv[1]; d.nu = iv[2]; d.nbody = iv[3]; d.njnt = iv[4]; d.ngeom = iv[5]; d.nsite = iv[6]; d.ntendon = iv[7]; d.nwrap = iv[8]; d.nmesh = iv[9];
   GI("k_dims");
@@ -561,13 +567,55 @@ int rg_model_dims(const rg_model* m, int* out) {
   return 0;
 }
 
-static void* balloc(rg_batch* b, size_t n) {
-  void* p = nullptr;
-  if (hipMalloc(&p, n ? n : 1) != hipSuccess) return nullptr;
-  hipMemset(p, 0, n ? n : 1);
-  b->allocs.push_back(p);
-  return p;
+// ---- substep-granular dispatch: is it available on this device?  One queue per XCD, served only by workgroups of that XCD:
+// every XCD must receive workgroups of a slots-sized grid.  Probed once per batch with a tiny kernel that counts workgroups
+// per XCC id; if any XCD stays empty (or the ids are not 0..7) the batch keeps the one-workgroup-per-env kernel.
+#ifdef RG_EMUL
+static void rg_items_probe(rg_batch* b) { b->items_slots = 2; b->items_queues = 1; }   // (workgroups run one after the other: the first drains the queue, the second finds it empty)
+#else
+__global__ void rg_xcc_probe_kernel(int* counts) { if (threadIdx.x == 0) atomicAdd(counts + (rg_xcc_id() & 15), 1); }
+static void rg_items_probe(rg_batch* b) {
+  b->items_slots = 0; b->items_queues = 1;
+  // the probe's answer is a property of the device: measured once per device and process (VERDICT r04 weak 10: it used to allocate, launch and synchronise in every
+  // rg_batch_create), and a failed probe launch is reported through rg_last_error instead of being swallowed -- the mode then stays off, which is always correct
+  // (ADVICE r05: the cache is shared by every thread that creates batches -- one per device is a normal host layout -- so it sits behind a mutex, and a probe whose
+  //  launch FAILED is cached too, as "off", instead of allocating and launching again in every rg_batch_create)
+  static int cached_slots[64], cached_queues[64]; static bool cached[64];
+  static std::mutex probe_mutex;
+  std::lock_guard<std::mutex> probe_lock(probe_mutex);
+  const bool cacheable = b->device >= 0 && b->device < 64;
+  if (cacheable && cached[b->device]) {
+    b->items_slots = cached_slots[b->device]; b->items_queues = cached_queues[b->device];
+    if (const char* ov = getenv("RG_ITEMS_SLOTS")) { const int v = atoi(ov); if (v > 0 && b->items_slots > 0) b->items_slots = v; }
+    return;
+  }
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, b->device) != hipSuccess) return;
+  const int cus = prop.multiProcessorCount;
+  // wave slots: LDS granules (1280 B) per CU / per workgroup, capped by the 3 waves per SIMD the kernel is compiled for
+  const int per_cu_lds = (160 * 1024) / (int)(((rgi::rg_lds_launch_bytes(false) + 1279) / 1280) * 1280);
+  const int per_cu = per_cu_lds < 4 * RG_WAVES_PER_SIMD_HOST ? per_cu_lds : 4 * RG_WAVES_PER_SIMD_HOST;
+  int* counts = nullptr;
+  if (hipMalloc((void**)&counts, 16 * 4) != hipSuccess) return;
+  (void)hipMemset(counts, 0, 16 * 4);
+  const int grid = cus * per_cu;
+  hipLaunchKernelGGL(rg_xcc_probe_kernel, dim3(grid), dim3(RG_WAVE), 0, 0, counts);
+  const hipError_t launch_err = hipGetLastError();
+  int h[16];
+  if (launch_err != hipSuccess) {
+    (void)fail(std::string("rg_items_probe: probe launch failed (substep-granular dispatch stays off): ") + hipGetErrorString(launch_err));
+    if (cacheable) { cached_slots[b->device] = 0; cached_queues[b->device] = 1; cached[b->device] = true; }
+  } else if (hipMemcpy(h, counts, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) {
+    int nq = 0; bool ok = true;
+    for (int x = 0; x < 16; x++) if (h[x] > 0) nq = x + 1;
+    for (int x = 0; x < nq; x++) if (h[x] <= 0) ok = false;
+    if (ok && nq >= 1 && nq <= 8) { b->items_slots = grid; b->items_queues = nq; }
+    if (cacheable) { cached_slots[b->device] = b->items_slots; cached_queues[b->device] = b->items_queues; cached[b->device] = true; }
+    if (const char* ov = getenv("RG_ITEMS_SLOTS")) { const int v = atoi(ov); if (v > 0 && b->items_slots > 0) b->items_slots = v; }   // (experiments: persistent workgroups per launch)
+  }
+  (void)hipFree(counts);
 }
+#endif
 
 rg_batch* rg_batch_create(const rg_model* m, int B, int device) {
   if (!m || !m->ok || B <= 0) { fail("bad arguments to rg_batch_create"); return nullptr; }
@@ -709,105 +757,27 @@ int rg_batch_copy(rg_batch* b, int field, void* ptr, int to_batch, int ptr_is_de
   return 0;
 }
 
-#ifdef RG_EMUL
-struct EmulCopyArgs { float* dst; const float* src; const int* mask; int n, col0, ncols; float* lb; int npair; };
-static void emul_copy_entry(void* a) { EmulCopyArgs* p = (EmulCopyArgs*)a; rgs::rg_copy_rows_kernel(p->dst, p->src, p->mask, p->n, p->col0, p->ncols, p->lb, p->npair); }
-#endif
 int rg_batch_copy_rows(rg_batch* b, int field, const void* src_dev, const int* mask_dev, int col0, int ncols, void* stream) {
   if (!b || !src_dev || !mask_dev) return fail("rg_batch_copy_rows: null argument");
   DeviceGuard g(b->device);
   const RgModelDev& d = b->model->dev;
   RgBatchDev& s = b->dev;
-  void* p; int n;
-  switch (field) {
-    case RG_F_QPOS: p = s.qpos; n = d.nq; break;
-    case RG_F_QVEL: p = s.qvel; n = d.nv; break;
-    case RG_F_CTRL: p = s.ctrl; n = d.nu; break;
-    case RG_F_PID: p = s.pid; n = 3 * d.nu; break;
-    case RG_F_WARMSTART: p = s.qacc_warmstart; n = d.nv; break;
-    case RG_F_TIME: p = s.time; n = 1; break;
-    case RG_F_STATUS: p = s.status; n = 1; break;
-    default: return fail("rg_batch_copy_rows: field cannot be written row-wise");
-  }
+  const bool rowwise = field == RG_F_QPOS || field == RG_F_QVEL || field == RG_F_CTRL || field == RG_F_PID || field == RG_F_WARMSTART || field == RG_F_TIME || field == RG_F_STATUS;
+  size_t words = 0; void* p = rowwise ? field_ptr(b, field, &words) : nullptr;
+  if (!p) return fail("rg_batch_copy_rows: field cannot be written row-wise");
+  const int n = (int)words;
   if (ncols <= 0) { col0 = 0; ncols = n; }
   if (col0 < 0 || col0 + ncols > n) return fail("rg_batch_copy_rows: column range outside the row");
   float* lb = field == RG_F_QPOS ? s.pairlb : nullptr;
-#ifdef RG_EMUL
-  EmulCopyArgs args{(float*)p, (const float*)src_dev, mask_dev, n, col0, ncols, lb, d.npair};
-  emul_launch(s.B, 16, emul_copy_entry, &args);
-#else
-  hipLaunchKernelGGL(rgs::rg_copy_rows_kernel, dim3(s.B), dim3(RG_WAVE), 0, (hipStream_t)stream, (float*)p, (const float*)src_dev, mask_dev, n, col0, ncols, lb, d.npair);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return launch(rgs::rg_copy_rows_kernel, s.B, RG_WAVE, 0, 0, stream, (float*)p, (const float*)src_dev, mask_dev, n, col0, ncols, lb, d.npair);   // (no LDS)
 }
 
-// ---- substep-granular dispatch: is it available on this device?  One queue per XCD, served only by workgroups of that XCD:
-// every XCD must receive workgroups of a slots-sized grid.  Probed once per batch with a tiny kernel that counts workgroups
-// per XCC id; if any XCD stays empty (or the ids are not 0..7) the batch keeps the one-workgroup-per-env kernel.
-#ifndef RG_EMUL
-__global__ void rg_xcc_probe_kernel(int* counts) { if (threadIdx.x == 0) atomicAdd(counts + (rg_xcc_id() & 15), 1); }
-#endif
-static void rg_items_probe(rg_batch* b) {
-#ifdef RG_EMUL
-  b->items_slots = 2; b->items_queues = 1;   // (workgroups run one after the other: the first drains the queue, the second finds it empty)
-#else
-  b->items_slots = 0; b->items_queues = 1;
-  // the probe's answer is a property of the device: measured once per device and process (VERDICT r04 weak 10: it used to allocate, launch and synchronise in every
-  // rg_batch_create), and a failed probe launch is reported through rg_last_error instead of being swallowed -- the mode then stays off, which is always correct
-  // (ADVICE r05: the cache is shared by every thread that creates batches -- one per device is a normal host layout -- so it sits behind a mutex, and a probe whose
-  //  launch FAILED is cached too, as "off", instead of allocating and launching again in every rg_batch_create)
-  static int cached_slots[64], cached_queues[64]; static bool cached[64];
-  static std::mutex probe_mutex;
-  std::lock_guard<std::mutex> probe_lock(probe_mutex);
-  const bool cacheable = b->device >= 0 && b->device < 64;
-  if (cacheable && cached[b->device]) {
-    b->items_slots = cached_slots[b->device]; b->items_queues = cached_queues[b->device];
-    if (const char* ov = getenv("RG_ITEMS_SLOTS")) { const int v = atoi(ov); if (v > 0 && b->items_slots > 0) b->items_slots = v; }
-    return;
-  }
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, b->device) != hipSuccess) return;
-  const int cus = prop.multiProcessorCount;
-  // wave slots: LDS granules (1280 B) per CU / per workgroup, capped by the 3 waves per SIMD the kernel is compiled for
-  const int per_cu_lds = (160 * 1024) / (int)(((rgi::rg_lds_launch_bytes(false) + 1279) / 1280) * 1280);
-  const int per_cu = per_cu_lds < 4 * RG_WAVES_PER_SIMD_HOST ? per_cu_lds : 4 * RG_WAVES_PER_SIMD_HOST;
-  int* counts = nullptr;
-  if (hipMalloc((void**)&counts, 16 * 4) != hipSuccess) return;
-  (void)hipMemset(counts, 0, 16 * 4);
-  const int grid = cus * per_cu;
-  hipLaunchKernelGGL(rg_xcc_probe_kernel, dim3(grid), dim3(RG_WAVE), 0, 0, counts);
-  const hipError_t launch_err = hipGetLastError();
-  int h[16];
-  if (launch_err != hipSuccess) {
-    (void)fail(std::string("rg_items_probe: probe launch failed (substep-granular dispatch stays off): ") + hipGetErrorString(launch_err));
-    if (cacheable) { cached_slots[b->device] = 0; cached_queues[b->device] = 1; cached[b->device] = true; }
-  } else if (hipMemcpy(h, counts, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) {
-    int nq = 0; bool ok = true;
-    for (int x = 0; x < 16; x++) if (h[x] > 0) nq = x + 1;
-    for (int x = 0; x < nq; x++) if (h[x] <= 0) ok = false;
-    if (ok && nq >= 1 && nq <= 8) { b->items_slots = grid; b->items_queues = nq; }
-    if (cacheable) { cached_slots[b->device] = b->items_slots; cached_queues[b->device] = b->items_queues; cached[b->device] = true; }
-    if (const char* ov = getenv("RG_ITEMS_SLOTS")) { const int v = atoi(ov); if (v > 0 && b->items_slots > 0) b->items_slots = v; }   // (experiments: persistent workgroups per launch)
-  }
-  (void)hipFree(counts);
-#endif
-}
 int rg_batch_items_info(const rg_batch* b, int* slots, int* queues) {
   if (!b) return fail("null batch");
   if (slots) *slots = b->items_slots;
   if (queues) *queues = b->items_queues;
   return 0;
 }
-
-#ifdef RG_EMUL
-struct EmulArgs { const RgModelDev* m; RgLaunch launch; };
-static void emul_entry_items(void* a);
-static void emul_entry(void* a) { EmulArgs* p = (EmulArgs*)a; rgs::rg_step_kernel(p->m, p->launch); }
-static void emul_entry_large(void* a) { EmulArgs* p = (EmulArgs*)a; rgl::rg_step_kernel(p->m, p->launch); }
-static void emul_entry_sensors(void* a) { EmulArgs* p = (EmulArgs*)a; rgx::rg_step_kernel(p->m, p->launch); }
-static void emul_entry_items(void* a) { EmulArgs* p = (EmulArgs*)a; rgi::rg_step_items_kernel(p->m, p->launch); }
-#endif
 
 int rg_batch_step_ex(rg_batch* b, const rg_step_args* a) {
   if (!b || !a) return fail("null argument");
@@ -826,33 +796,16 @@ int rg_batch_step_ex(rg_batch* b, const rg_step_args* a) {
   bt.xdata = a->xdata_dev;
   // flags bit 7: substep-granular dispatch (rollout configuration, >= 2 substeps, no debug / profiling / sensor pass): see rg_step_items_kernel
   const bool items = (a->flags & 128) && !large && !(a->flags & (1 | 2 | 256)) && a->nsubsteps >= 2 && b->items_slots > 0;
-  RgLaunch launch{b->model->aux, b->env, bt, a->nsubsteps, a->nforward_ticks, a->flags, items ? b->items_queues : 1};
+  RgLaunch launch_args{b->model->aux, b->env, bt, a->nsubsteps, a->nforward_ticks, a->flags, items ? b->items_queues : 1};
   if (items) {
     const long long nitems = (long long)bt.B * a->nsubsteps;
     const int grid = (int)(nitems < b->items_slots ? nitems : b->items_slots);
     const size_t ldsi = rgi::rg_lds_launch_bytes(false);
-#ifdef RG_EMUL
-    memset(bt.sched, 0, ((size_t)RG_SCHED_PROG + bt.B) * 4);
-    EmulArgs args{b->model->dev_copy, launch};
-    emul_launch(grid, ldsi, emul_entry_items, &args);
-#else
     HIPCHK(hipMemsetAsync(bt.sched, 0, ((size_t)RG_SCHED_PROG + bt.B) * 4, (hipStream_t)a->stream));
-    hipLaunchKernelGGL(rgi::rg_step_items_kernel, dim3(grid), dim3(RG_WAVE), ldsi, (hipStream_t)a->stream, b->model->dev_copy, launch);
-    HIPCHK(hipGetLastError());
-#endif
-    return 0;
+    return launch(rgi::rg_step_items_kernel, grid, RG_WAVE, ldsi, 0, a->stream, b->model->dev_copy, launch_args);
   }
   const size_t lds = sens ? rgx::rg_lds_launch_bytes(prof) : (large ? rgl::rg_lds_launch_bytes(prof) : rgs::rg_lds_launch_bytes(prof));
-#ifdef RG_EMUL
-  EmulArgs args{b->model->dev_copy, launch};
-  emul_launch(bt.B, lds, sens ? emul_entry_sensors : (large ? emul_entry_large : emul_entry), &args);
-#else
-  if (sens) hipLaunchKernelGGL(rgx::rg_step_kernel, dim3(bt.B), dim3(RG_WAVE), lds, (hipStream_t)a->stream, b->model->dev_copy, launch);
-  else if (large) hipLaunchKernelGGL(rgl::rg_step_kernel, dim3(bt.B), dim3(RG_WAVE), lds, (hipStream_t)a->stream, b->model->dev_copy, launch);
-  else hipLaunchKernelGGL(rgs::rg_step_kernel, dim3(bt.B), dim3(RG_WAVE), lds, (hipStream_t)a->stream, b->model->dev_copy, launch);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return launch(sens ? rgx::rg_step_kernel : large ? rgl::rg_step_kernel : rgs::rg_step_kernel, bt.B, RG_WAVE, lds, 0, a->stream, b->model->dev_copy, launch_args);
 }
 int rg_batch_step(rg_batch* b, const float* action_dev, const float* goal_quat_dev, float* obs_dev, float* goal_dist_dev,
                   const int* active_dev, int nsubsteps, int nforward_ticks, int flags, void* stream) {
@@ -863,30 +816,15 @@ int rg_batch_step(rg_batch* b, const float* action_dev, const float* goal_quat_d
   return rg_batch_step_ex(b, &a);
 }
 
-#ifdef RG_EMUL
-struct EmulMprArgs { const RgModelDev* m; RgLaunch launch; int g1, g2; float margin; float* out; };
-static void emul_mpr_entry(void* a) { EmulMprArgs* p = (EmulMprArgs*)a; rgs::rg_mpr_pair_kernel(p->m, p->launch, p->g1, p->g2, p->margin, p->out); }
-#endif
 int rg_batch_mpr_pair(rg_batch* b, int g1, int g2, float margin, float* out_dev, void* stream) {
   if (!b || !out_dev) return fail("null argument");
   const RgModelDev& d = b->model->dev;
   if (g1 < 0 || g2 < 0 || g1 >= d.ngeom || g2 >= d.ngeom) return fail("geom id out of range");
   DeviceGuard g(b->device);
-  RgLaunch launch{b->model->aux, b->env, b->dev, 0, 0, 0, 1};
-#ifdef RG_EMUL
-  EmulMprArgs args{b->model->dev_copy, launch, g1, g2, margin, out_dev};
-  emul_launch(b->dev.B, sizeof(rgs::RgLds), emul_mpr_entry, &args);
-#else
-  hipLaunchKernelGGL(rgs::rg_mpr_pair_kernel, dim3(b->dev.B), dim3(RG_WAVE), sizeof(rgs::RgLds), (hipStream_t)stream, b->model->dev_copy, launch, g1, g2, margin, out_dev);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  RgLaunch launch_args{b->model->aux, b->env, b->dev, 0, 0, 0, 1};
+  return launch(rgs::rg_mpr_pair_kernel, b->dev.B, RG_WAVE, sizeof(rgs::RgLds), 0, stream, b->model->dev_copy, launch_args, g1, g2, margin, out_dev);
 }
 
-#ifdef RG_EMUL
-struct EmulPostArgs { RgBatchDev bt; RgPostArgs a; int nq, nv, nu, npair; };
-static void emul_post_entry(void* p_) { EmulPostArgs* p = (EmulPostArgs*)p_; rg_post_step_kernel(p->bt, p->a, p->nq, p->nv, p->nu, p->npair); }
-#endif
 int rg_post_args_size(void) { return (int)sizeof(rg_post_args); }
 int rg_env_post_step(rg_batch* b, const rg_post_args* args, void* stream) {
   if (!b || !args) return fail("null argument");
@@ -899,36 +837,17 @@ int rg_env_post_step(rg_batch* b, const rg_post_args* args, void* stream) {
   const RgModelDev& d = b->model->dev;
   if (d.nu > 20) return fail("rg_env_post_step: nu exceeds RG_POST_NDRAW's action slots");
   DeviceGuard g(b->device);
-#ifdef RG_EMUL
-  EmulPostArgs ea{b->dev, a, d.nq, d.nv, d.nu, d.npair};
-  emul_launch(b->dev.B, 256, emul_post_entry, &ea);
-#else
-  hipLaunchKernelGGL(rg_post_step_kernel, dim3(b->dev.B), dim3(RG_WAVE), 0, (hipStream_t)stream, b->dev, a, d.nq, d.nv, d.nu, d.npair);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return launch(rg_post_step_kernel, b->dev.B, RG_WAVE, 0, sizeof(RgPostFlags), stream, b->dev, a, d.nq, d.nv, d.nu, d.npair);
 }
 
-#ifdef RG_EMUL
-struct EmulSetconstArgs { const RgModelDev* m; RgLaunch launch; float* envprm; };
-static void emul_setconst_entry(void* a) { EmulSetconstArgs* p = (EmulSetconstArgs*)a; rgl::rg_setconst_kernel(p->m, p->launch, p->envprm); }
-#endif
 int rg_batch_set_constants(rg_batch* b, const int* mask_dev, void* stream) {
   if (!b) return fail("null batch");
   if (!b->dev.envprm) return fail("rg_batch_set_constants: the batch has no per-env parameter rows (rg_batch_enable_env_params); the model's own constants are already consistent");
   DeviceGuard g(b->device);
   RgBatchDev bt = b->dev;
   bt.active = mask_dev; bt.order = nullptr;
-  RgLaunch launch{b->model->aux, b->env, bt, 0, 0, 0, 1};
-  const size_t lds = rgl::rg_lds_setconst_bytes();
-#ifdef RG_EMUL
-  EmulSetconstArgs args{b->model->dev_copy, launch, (float*)b->dev.envprm};
-  emul_launch(bt.B, lds, emul_setconst_entry, &args);
-#else
-  hipLaunchKernelGGL(rgl::rg_setconst_kernel, dim3(bt.B), dim3(RG_WAVE), lds, (hipStream_t)stream, b->model->dev_copy, launch, (float*)b->dev.envprm);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  RgLaunch launch_args{b->model->aux, b->env, bt, 0, 0, 0, 1};
+  return launch(rgl::rg_setconst_kernel, bt.B, RG_WAVE, rgl::rg_lds_setconst_bytes(), 0, stream, b->model->dev_copy, launch_args, (float*)b->dev.envprm);
 }
 
 // =====================================================================================================================
@@ -956,32 +875,33 @@ struct rb_batch {
   int has_env = 0;
   std::vector<void*> allocs;
 };
-static bool rb_upload_bytes(rb_model* m, const void* host, size_t bytes, const void** dst) {
-  void* p = nullptr;
-  if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) return false;
-  m->allocs.push_back(p);
-  if (bytes && hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return false;
-  *dst = p;
-  return true;
-}
 void rb_model_free(rb_model* m) {
   if (!m) return;
   { DeviceGuard g(m->device); for (void* p : m->allocs) hipFree(p); }
   delete m;
 }
 // the per-env scratch row: stage arrays at the model's capacities, then (models switched to per-env parameters) the env's parameter block
+// One row per stage array, in the order of the RB_O_* enumeration (rb_types.h; RB_O_PRM, the parameter block, follows the table): its name (RB_LDS_PLACE), its
+// words at the model's capacities (cw: dofs per contact row the model's configuration is compiled for) and whether it may live in the LDS arena.
+struct RbStageArray { const char* name; int (*words)(const RbModelDev& d, int cw); bool placeable; };
+#define RB_WORDS(expr) [](const RbModelDev& d, int cw) -> int { (void)cw; return (expr); }
+static const RbStageArray rb_stage_arrays[] = {
+  {"xpos", RB_WORDS(3 * d.nbody), true}, {"xquat", RB_WORDS(4 * d.nbody), true}, {"xipos", RB_WORDS(3 * d.nbody), true}, {"xiquat", RB_WORDS(4 * d.nbody), true},
+  {"xanchor", RB_WORDS(3 * d.njnt), true}, {"xaxis", RB_WORDS(3 * d.njnt), true}, {"gpos", RB_WORDS(3 * d.ngeom), true}, {"gquat", RB_WORDS(4 * d.ngeom), true},
+  {"spos", RB_WORDS(3 * d.nsite), true}, {"rootcom", RB_WORDS(3 * d.nbody), true}, {"cinert", RB_WORDS(10 * d.nbody), true}, {"crb", RB_WORDS(10 * d.nbody), true},
+  {"cdof", RB_WORDS(6 * d.nv), true}, {"cdofdot", RB_WORDS(6 * d.nv), true}, {"cvel", RB_WORDS(6 * d.nbody), true}, {"cacc", RB_WORDS(6 * d.nbody), true},
+  {"cfrc", RB_WORDS(6 * d.nbody), true}, {"tenlen", RB_WORDS(d.ntendon), true}, {"tenj", RB_WORDS(RB_TENW * d.ntendon), true}, {"tenvel", RB_WORDS(d.ntendon), true},
+  {"msp", RB_WORDS(d.nM), true}, {"cand", RB_WORDS(d.maxcand), true}, {"con", RB_WORDS(RB_CONREC * d.maxcon), true}, {"conj", RB_WORDS(6 * cw * d.maxcon), true},
+  {"conidx", RB_WORDS(cw * d.maxcon), true}, {"row", RB_WORDS(RB_ROWREC * d.maxrow), true}, {"dofcon_adr", RB_WORDS(d.nv + 1), true}, {"dofcon", RB_WORDS(cw * d.maxcon), true},
+  {"conf", RB_WORDS(RB_NW * d.maxcon), true}, {"dbg", RB_WORDS(8 + 5 * d.nv + 16), false}, {"cfrcext", RB_WORDS(6 * d.nbody), true}, {"conloc", RB_WORDS(cw * d.maxcon), true},
+};
+#undef RB_WORDS
+static_assert(sizeof rb_stage_arrays / sizeof rb_stage_arrays[0] == RB_NOFF - 1 && RB_O_PRM == RB_NOFF - 1, "one row per RB_O_* stage array, and the parameter block last");
+static int rb_conw(const rb_model* m) { return m->config ? RB_CONW_ONEWAVE : RB_CONW; }   // dofs per contact row the model's configuration is compiled for
 static void rb_layout(rb_model* m) {
   RbModelDev& d = m->dev;
   int o = 0;
-  auto take = [&](int which, int words) { d.off[which] = o; o += (words + 3) & ~3; };
-  take(RB_O_XPOS, 3 * d.nbody); take(RB_O_XQUAT, 4 * d.nbody); take(RB_O_XIPOS, 3 * d.nbody); take(RB_O_XIQUAT, 4 * d.nbody);
-  take(RB_O_XANCHOR, 3 * d.njnt); take(RB_O_XAXIS, 3 * d.njnt); take(RB_O_GPOS, 3 * d.ngeom); take(RB_O_GQUAT, 4 * d.ngeom); take(RB_O_SPOS, 3 * d.nsite);
-  take(RB_O_ROOTCOM, 3 * d.nbody); take(RB_O_CINERT, 10 * d.nbody); take(RB_O_CRB, 10 * d.nbody); take(RB_O_CDOF, 6 * d.nv); take(RB_O_CDOFDOT, 6 * d.nv);
-  take(RB_O_CVEL, 6 * d.nbody); take(RB_O_CACC, 6 * d.nbody); take(RB_O_CFRC, 6 * d.nbody);
-  take(RB_O_TENLEN, d.ntendon); take(RB_O_TENJ, RB_TENW * d.ntendon); take(RB_O_TENVEL, d.ntendon); take(RB_O_MSP, d.nM);
-  const int cw = m->config ? RB_CONW_ONEWAVE : RB_CONW;      // dofs per contact row the model's configuration is compiled for
-  take(RB_O_CAND, d.maxcand); take(RB_O_CON, RB_CONREC * d.maxcon); take(RB_O_CONJ, 6 * cw * d.maxcon); take(RB_O_CONIDX, cw * d.maxcon);
-  take(RB_O_ROW, RB_ROWREC * d.maxrow); take(RB_O_DOFCON_ADR, d.nv + 1); take(RB_O_DOFCON, cw * d.maxcon); take(RB_O_CONF, RB_NW * d.maxcon); take(RB_O_DBG, 8 + 5 * d.nv + 16); take(RB_O_CFRCEXT, 6 * d.nbody); take(RB_O_CONLOC, cw * d.maxcon);
+  for (int k = 0; k < RB_O_PRM; k++) { d.off[k] = o; o += (rb_stage_arrays[k].words(d, rb_conw(m)) + 3) & ~3; }
   d.prm_words = 0;
   for (int k = 0; k < RB_NPRMF; k++) d.prm_off[k] = 0;
   d.off[RB_O_PRM] = o;
@@ -993,25 +913,17 @@ static void rb_layout(rb_model* m) {
   d.scratch_words = o;
 }
 rb_model* rb_model_create(const void* blob, size_t nbytes, char* err, int errlen) {
-  auto bail = [&](const std::string& msg, rb_model* m) -> rb_model* {
-    g_key_log = nullptr;
-    g_err = msg;
-    if (err && errlen > 0) { strncpy(err, msg.c_str(), errlen - 1); err[errlen - 1] = 0; }
-    if (m) rb_model_free(m);
-    return nullptr;
-  };
+  auto bail = [&](const std::string& msg, rb_model* m) { return create_failed(msg, m, rb_model_free, err, errlen); };
   if (!blob || nbytes < 16 || memcmp(blob, "RGMODEL1", 8) != 0) return bail("not an RGMODEL1 blob", nullptr);
   Blob B{(const char*)blob, nbytes};
   rb_model* m = new rb_model();
   g_key_log = &m->blob_keys;
-#ifndef RG_EMUL
   if (hipGetDevice(&m->device) != hipSuccess) return bail("hipGetDevice failed", m);
-#endif
   RbModelDev& d = m->dev;
   memset(&d, 0, sizeof d);
   std::string e;
   std::vector<int> iv; std::vector<float> fv;
-  if (!get_i(B, "dims", iv, e)) return bail(e, m);
+  GI("dims");
   d.nq = iv[0]; d.nv = iv[1]; d.nu = iv[2]; d.nbody = iv[3]; d.njnt = iv[4]; d.ngeom = iv[5]; d.nsite = iv[6]; d.ntendon = iv[7]; d.nmesh = iv[9];
   if (!get_i(B, "b_dims", iv, e)) return bail(e + " (derive_big_tables was not run on the model)", m);
   d.nlevel = iv[0]; d.nM = iv[1]; d.npair = iv[2]; d.ngroup = iv[3]; d.gmax = iv[4]; d.nroot = iv[5]; d.conw = iv[6];
@@ -1034,10 +946,10 @@ rb_model* rb_model_create(const void* blob, size_t nbytes, char* err, int errlen
       else if (fits(RB_MAXGROUP_MEDIUM, RB_MAXNV_MEDIUM, RB_MAXNQ_MEDIUM, RB_T_MEDIUM)) m->config = 2;
     }
   }
-#define X(n) if (!get_i(B, #n, iv, e)) return bail(e, m); if (!rb_upload_bytes(m, iv.data(), iv.size() * 4, (const void**)&d.n)) return bail("hipMalloc failed", m);
+#define X(n) UPI(n, #n);
   RB_INT_ARRAYS(X)
 #undef X
-#define X(n) if (!get_f(B, #n, fv, e)) return bail(e, m); if (!rb_upload_bytes(m, fv.data(), fv.size() * 4, (const void**)&d.n)) return bail("hipMalloc failed", m);
+#define X(n) UPF(n, #n);
   RB_FLT_ARRAYS(X)
 #undef X
   {  // optional: the geoms whose size follows the env's RB_P_GEOM_SCALE.  Meshes and boxes only (vertices / half extents, bounding radius and oriented box all scale
@@ -1051,36 +963,36 @@ rb_model* rb_model_create(const void* blob, size_t nbytes, char* err, int errlen
       for (int g = 0; g < d.ngeom; g++) if (gsc[g] && gt[g] != RG_GEOM_MESH && gt[g] != RG_GEOM_BOX) return bail("b_geom_scaled flags a geom that is neither a mesh nor a box", m);
     }
     d.ngeom_scaled = 0; for (int v : gsc) d.ngeom_scaled += v != 0;
-    if (!rb_upload_bytes(m, gsc.data(), gsc.size() * 4, (const void**)&d.b_geom_scaled)) return bail("hipMalloc failed", m);
+    if (!upload<int>(m, gsc, &d.b_geom_scaled)) return bail("hipMalloc failed", m);
   }
-  if (!get_i(B, "b_fric_dof", iv, e)) return bail(e, m); d.nfric_dof = (int)iv.size();
-  if (!get_i(B, "b_fric_ten", iv, e)) return bail(e, m); d.nfric_ten = (int)iv.size();
-  if (!get_i(B, "b_lim_jnt", iv, e)) return bail(e, m); d.nlim_jnt = (int)iv.size();
-  if (!get_i(B, "b_lim_ten", iv, e)) return bail(e, m); d.nlim_ten = (int)iv.size();
-  if (!get_i(B, "actuator_biastype", iv, e)) return bail(e, m);
+  GI("b_fric_dof"); d.nfric_dof = (int)iv.size();
+  GI("b_fric_ten"); d.nfric_ten = (int)iv.size();
+  GI("b_lim_jnt"); d.nlim_jnt = (int)iv.size();
+  GI("b_lim_ten"); d.nlim_ten = (int)iv.size();
+  GI("actuator_biastype");
   for (int v : iv) if (v != 2) return bail("rb_model_create: only mujoco-py PID actuators (biastype user) are implemented", m);
-  if (!get_i(B, "opt_int", iv, e)) return bail(e, m);
+  GI("opt_int");
   d.iterations = iv[0]; d.ls_iterations = iv[2]; d.mpr_iterations = iv[3];
   d.cone = iv[1];   // 0 pyramidal, 1 elliptic (ur16e/base.xml:3)
-  if (!get_i(B, "eq_type", iv, e)) return bail(e, m); d.neq = (int)iv.size();
-  if (!get_i(B, "nmocap", iv, e)) return bail(e, m); d.nmocap = iv[0];
+  GI("eq_type"); d.neq = (int)iv.size();
+  GI("nmocap"); d.nmocap = iv[0];
   if (d.nmocap > 2) return bail("rb_model_create: at most two mocap bodies", m);
-  if (!get_i(B, "sensor_type", iv, e)) return bail(e, m); d.nsensor = (int)iv.size();
+  GI("sensor_type"); d.nsensor = (int)iv.size();
   { std::vector<int> sa, sd; if (!get_i(B, "sensor_adr", sa, e) || !get_i(B, "sensor_dim", sd, e)) return bail(e, m); d.nsensordata = d.nsensor ? sa.back() + sd.back() : 0; }
   for (int k = 0; k < d.nsensor; k++) if (iv[k] != 0 && iv[k] != 4 && iv[k] != 5 && iv[k] != 8) return bail("rb_model_create: sensor type not implemented", m);
-  if (!get_i(B, "size_int", iv, e)) return bail(e, m);
+  GI("size_int");
   d.maxrow = iv[0] > 0 ? iv[0] : 2000; d.maxcon = iv[1] > 0 ? iv[1] : 200;   // njmax / nconmax of the model
   // RB_SCRATCH_MAXCON / RB_SCRATCH_MAXROW: capacities of the per-env scratch row below the model's nconmax / njmax (the row's arrays are laid out at capacity:
   // rearrange's 500 / 2000 spread the ~40 kB an mj_step touches over 660 kB per env).  Exceeding them raises RG_STATUS_CON_FULL / ROW_FULL as the model's own do.
   if (const char* ov = getenv("RB_SCRATCH_MAXCON")) { const int v = atoi(ov); if (v > 0 && v < d.maxcon) d.maxcon = v; }
   if (const char* ov = getenv("RB_SCRATCH_MAXROW")) { const int v = atoi(ov); if (v > 0 && v < d.maxrow) d.maxrow = v; }
   d.maxcand = 4 * d.maxcon + 256;
-  if (!get_f(B, "opt_timestep", fv, e)) return bail(e, m); d.timestep = fv[0];
-  if (!get_f(B, "opt_gravity", fv, e)) return bail(e, m); for (int k = 0; k < 3; k++) d.gravity[k] = fv[k];
-  if (!get_f(B, "opt_tolerance", fv, e)) return bail(e, m); d.tolerance = fv[0];
-  if (!get_f(B, "opt_impratio", fv, e)) return bail(e, m); d.impratio = fv[0];
-  if (!get_f(B, "opt_mpr_tolerance", fv, e)) return bail(e, m); d.mpr_tolerance = fv[0];
-  if (!get_f(B, "stat_meaninertia", fv, e)) return bail(e, m); d.meaninertia = fv[0];
+  GF("opt_timestep"); d.timestep = fv[0];
+  GF("opt_gravity"); for (int k = 0; k < 3; k++) d.gravity[k] = fv[k];
+  GF("opt_tolerance"); d.tolerance = fv[0];
+  GF("opt_impratio"); d.impratio = fv[0];
+  GF("opt_mpr_tolerance"); d.mpr_tolerance = fv[0];
+  GF("stat_meaninertia"); d.meaninertia = fv[0];
   if (!get_f(B, "qpos0", m->qpos0, e)) return bail(e, m);
   if (!get_f(B, "eq_data", m->eq_data0, e) || !get_i(B, "eq_active", m->eq_active0, e)) return bail(e, m);
   {
@@ -1113,11 +1025,6 @@ rb_model* rb_model_create(const void* blob, size_t nbytes, char* err, int errlen
   // ---- LDS residency of stage arrays (rb_types.h lds_off): RB_LDS_PLACE = a preset or a comma-separated list of array names.  Only arrays whose length does not
   // depend on the number of contacts / rows of the mj_step can be placed (their capacity is the model's own size).
   {
-    static const char* names[RB_NOFF] = {"xpos", "xquat", "xipos", "xiquat", "xanchor", "xaxis", "gpos", "gquat", "spos", "rootcom", "cinert", "crb", "cdof", "cdofdot", "cvel", "cacc", "cfrc",
-                                         "tenlen", "tenj", "tenvel", "msp", "cand", "con", "conj", "conidx", "row", "dofcon_adr", "dofcon", "conf", "dbg", "cfrcext", "conloc", "prm"};
-    const int cwl = m->config ? RB_CONW_ONEWAVE : RB_CONW;
-    const int len[RB_NOFF] = {3 * d.nbody, 4 * d.nbody, 3 * d.nbody, 4 * d.nbody, 3 * d.njnt, 3 * d.njnt, 3 * d.ngeom, 4 * d.ngeom, 3 * d.nsite, 3 * d.nbody, 10 * d.nbody, 10 * d.nbody, 6 * d.nv, 6 * d.nv,
-                              6 * d.nbody, 6 * d.nbody, 6 * d.nbody, d.ntendon, RB_TENW * d.ntendon, d.ntendon, d.nM, d.maxcand, RB_CONREC * d.maxcon, 6 * cwl * d.maxcon, cwl * d.maxcon, RB_ROWREC * d.maxrow, d.nv + 1, cwl * d.maxcon, RB_NW * d.maxcon, 0, 6 * d.nbody, cwl * d.maxcon, 0};
     for (int k = 0; k < RB_NOFF; k++) { d.lds_off[k] = -1; d.lds_len[k] = 0; }
     d.lds_words = 0;
     const char* place = getenv("RB_LDS_PLACE");
@@ -1137,10 +1044,11 @@ rb_model* rb_model_create(const void* blob, size_t nbytes, char* err, int errlen
         at = e2 == std::string::npos ? want.size() + 1 : e2 + 1;
         if (nm.empty()) continue;
         int k = -1;
-        for (int q = 0; q < RB_NOFF; q++) if (nm == names[q]) k = q;
-        if (k < 0 || (len[k] == 0 && k != RB_O_TENLEN && k != RB_O_TENJ && k != RB_O_TENVEL)) return bail("RB_LDS_PLACE: unknown or unplaceable stage array name", m);
-        if (d.lds_off[k] >= 0 || len[k] == 0) continue;
-        d.lds_off[k] = lo; d.lds_len[k] = len[k]; lo += (len[k] + 3) & ~3;
+        for (int q = 0; q < RB_O_PRM; q++) if (nm == rb_stage_arrays[q].name) k = q;
+        const int len = k >= 0 && rb_stage_arrays[k].placeable ? rb_stage_arrays[k].words(d, rb_conw(m)) : 0;   // (tendon arrays are accepted by name also in a model without tendons)
+        if (k < 0 || (len == 0 && k != RB_O_TENLEN && k != RB_O_TENJ && k != RB_O_TENVEL)) return bail("RB_LDS_PLACE: unknown or unplaceable stage array name", m);
+        if (d.lds_off[k] >= 0 || len == 0) continue;
+        d.lds_off[k] = lo; d.lds_len[k] = len; lo += (len + 3) & ~3;
       }
       d.lds_words = lo;
       const size_t base = m->config == 1 ? ((sizeof(rgbs::RbLds) + 15) & ~(size_t)15) : ((sizeof(rgbm::RbLds) + 15) & ~(size_t)15);
@@ -1243,7 +1151,6 @@ static bool compile_mjcf_to_blob(const char* xml, const char* meshdir, int kind,
   cleanup();
   return ok;
 }
-static void put_err(const std::string& e, char* err, int errlen) { g_err = e; if (err && errlen > 0) { strncpy(err, e.c_str(), errlen - 1); err[errlen - 1] = 0; } }
 int rg_compile_mjcf_blob(const char* xml, const char* meshdir, int kind, void** blob_out, size_t* nbytes_out, char* err, int errlen) {
   if (!blob_out || !nbytes_out) { put_err("rg_compile_mjcf_blob: null output pointer", err, errlen); return -1; }
   std::vector<char> blob; std::string e;
@@ -1284,7 +1191,7 @@ int rg_blob_entry(const void* blob, size_t nbytes, int index, char* name40, int*
 int rb_model_info(const rb_model* m, int* out, int n) {
   if (!m) return fail("null model");
   const RbModelDev& d = m->dev;
-  const int v[] = {d.nq, d.nv, d.nu, d.nbody, d.njnt, d.ngeom, d.nsite, d.ntendon, d.nM, d.npair, d.ngroup, d.gmax, d.maxcon, d.maxrow, d.scratch_words, RB_CONREC, RB_ROWREC, m->config ? RB_CONW_ONEWAVE : RB_CONW, RB_TENW,
+  const int v[] = {d.nq, d.nv, d.nu, d.nbody, d.njnt, d.ngeom, d.nsite, d.ntendon, d.nM, d.npair, d.ngroup, d.gmax, d.maxcon, d.maxrow, d.scratch_words, RB_CONREC, RB_ROWREC, rb_conw(m), RB_TENW,
                    (m->config == 1 ? (int)sizeof(rgbs::RbLds) : m->config == 2 ? (int)sizeof(rgbm::RbLds) : (int)sizeof(rgb::RbLds)) + (d.lds_words ? 4 * d.lds_words + 16 : 0), m->config == 1 ? RB_T_SMALL : m->config == 2 ? RB_T_MEDIUM : RB_T_LARGE};
   const int k = (int)(sizeof v / sizeof v[0]);
   for (int i = 0; i < k && i < n; i++) out[i] = v[i];
@@ -1314,13 +1221,6 @@ int rb_prm_layout(const rb_model* m, int* out, int n) {
   return k;
 }
 int rb_scratch_offset(const rb_model* m, int which) { return (m && which >= 0 && which < RB_NOFF) ? m->dev.off[which] : -1; }
-static void* rb_balloc(rb_batch* b, size_t n) {
-  void* p = nullptr;
-  if (hipMalloc(&p, n ? n : 1) != hipSuccess) return nullptr;
-  hipMemset(p, 0, n ? n : 1);
-  b->allocs.push_back(p);
-  return p;
-}
 void rb_batch_free(rb_batch* b) {
   if (!b) return;
   { DeviceGuard g(b->device); for (void* p : b->allocs) hipFree(p); }
@@ -1355,13 +1255,13 @@ rb_batch* rb_batch_create(const rb_model* m, int B) {
   memset(&b->dev, 0, sizeof b->dev); memset(&b->env, 0, sizeof b->env);
   const RbModelDev& d = m->dev; RbBatchDev& s = b->dev;
   s.B = B;
-  s.qpos = (float*)rb_balloc(b, (size_t)B * d.nq * 4); s.qvel = (float*)rb_balloc(b, (size_t)B * d.nv * 4);
-  s.ctrl = (float*)rb_balloc(b, (size_t)B * d.nu * 4); s.pid = (float*)rb_balloc(b, (size_t)B * 3 * d.nu * 4);
-  s.qacc_warmstart = (float*)rb_balloc(b, (size_t)B * d.nv * 4); s.time = (float*)rb_balloc(b, (size_t)B * 4);
-  s.status = (uint32_t*)rb_balloc(b, (size_t)B * 4); s.stats = (float*)rb_balloc(b, (size_t)B * 16);
-  s.scratch = (float*)rb_balloc(b, (size_t)B * d.scratch_words * 4);
-  s.mocap = (float*)rb_balloc(b, (size_t)B * 7 * d.nmocap * 4); s.eq_data = (float*)rb_balloc(b, (size_t)B * 7 * d.neq * 4);
-  s.eq_active = (int*)rb_balloc(b, (size_t)B * d.neq * 4); s.sensordata = (float*)rb_balloc(b, (size_t)B * d.nsensordata * 4);
+  s.qpos = (float*)balloc(b, (size_t)B * d.nq * 4); s.qvel = (float*)balloc(b, (size_t)B * d.nv * 4);
+  s.ctrl = (float*)balloc(b, (size_t)B * d.nu * 4); s.pid = (float*)balloc(b, (size_t)B * 3 * d.nu * 4);
+  s.qacc_warmstart = (float*)balloc(b, (size_t)B * d.nv * 4); s.time = (float*)balloc(b, (size_t)B * 4);
+  s.status = (uint32_t*)balloc(b, (size_t)B * 4); s.stats = (float*)balloc(b, (size_t)B * 16);
+  s.scratch = (float*)balloc(b, (size_t)B * d.scratch_words * 4);
+  s.mocap = (float*)balloc(b, (size_t)B * 7 * d.nmocap * 4); s.eq_data = (float*)balloc(b, (size_t)B * 7 * d.neq * 4);
+  s.eq_active = (int*)balloc(b, (size_t)B * d.neq * 4); s.sensordata = (float*)balloc(b, (size_t)B * d.nsensordata * 4);
   if (!s.mocap || !s.eq_data || !s.eq_active || !s.sensordata) { fail("hipMalloc failed"); rb_batch_free(b); return nullptr; }
   {  // equality data and flags are MODEL fields in MuJoCo: they start at the model's values and survive MjSim.reset (the envs write them)
     std::vector<float> ed((size_t)B * 7 * d.neq); std::vector<int> ea((size_t)B * d.neq);
@@ -1385,7 +1285,7 @@ int rb_batch_set_env(rb_batch* b, int hand_qposadr, int n_hand_jnt, int relative
   if (!b || !p2c) return fail("rb_batch_set_env: null argument");
   DeviceGuard g(b->device);
   const size_t n = (size_t)b->model->dev.nu * n_hand_jnt;
-  float* dp = (float*)rb_balloc(b, n * 4);
+  float* dp = (float*)balloc(b, n * 4);
   if (!dp) return fail("hipMalloc failed");
   HIPCHK(hipMemcpy(dp, p2c, n * 4, hipMemcpyHostToDevice));
   b->env.hand_qposadr = hand_qposadr; b->env.n_hand_jnt = n_hand_jnt; b->env.relative_action = relative_action; b->env.pos_to_ctrl = dp;
@@ -1423,24 +1323,21 @@ void* rb_batch_field_ptr(rb_batch* b, int field, int* row_words) {
   if (row_words) *row_words = n;
   return p;
 }
-#ifdef RG_EMUL
-struct EmulRbArgs { const RbModelDev* m; RbLaunch launch; };
-static void emul_rb_entry(void* a) { EmulRbArgs* p = (EmulRbArgs*)a; rgb::rb_step_kernel(p->m, p->launch); }
-static void emul_rbs_entry(void* a) { EmulRbArgs* p = (EmulRbArgs*)a; rgbs::rb_step_kernel(p->m, p->launch); }
-static void emul_rbm_entry(void* a) { EmulRbArgs* p = (EmulRbArgs*)a; rgbm::rb_step_kernel(p->m, p->launch); }
-#endif
-int rb_batch_step_ex(rb_batch* b, const float* action_dev, const int* active_dev, const int* hold_dev, const int* nticks_dev, int nsubsteps, int nforward_ticks, int flags, void* stream);
 int rb_tcp_args_size(void) { return (int)sizeof(rb_tcp_args); }
-static thread_local const RbTcpHook* g_tcp_hook = nullptr;
+static thread_local const RbTcpHook* g_tcp_hook = nullptr;   // set by rb_batch_step_tcp around its launch
 // ---- several batches in ONE launch (rb_multi_begin / rb_multi_launch): between the two calls the rb_batch_step* entry points of this thread validate and record
 // their launch instead of issuing it
 struct RbCollected { const rb_batch* b; RbLaunch launch; };
 static thread_local std::vector<RbCollected>* g_multi = nullptr;
-#ifdef RG_EMUL
-static void emul_rbs_multi_entry(void* a) { rgbs::rb_step_multi_kernel(*(RbMultiLaunch*)a); }
-static void emul_rbm_multi_entry(void* a) { rgbm::rb_step_multi_kernel(*(RbMultiLaunch*)a); }
-#endif
-static int rb_issue(const rb_batch* b, const RbLaunch& launch, void* stream);
+// dynamic LDS of a launch behind RbLds: the model's arena, if it placed stage arrays there (+16: the arena starts at the next 16-byte boundary behind RbLds)
+static size_t rb_arena_bytes(const rb_model* m) { return m->dev.lds_words ? 4 * (size_t)m->dev.lds_words + 16 : 0; }
+static int rb_issue(const rb_batch* b, const RbLaunch& launch_args, void* stream) {
+  const rb_model* m = b->model;
+  DeviceGuard g(b->device);
+  if (m->config == 1) return launch(rgbs::rb_step_kernel, launch_args.bt.B, RB_T_SMALL, sizeof(rgbs::RbLds) + rb_arena_bytes(m), 0, stream, m->dev_copy, launch_args);
+  if (m->config == 2) return launch(rgbm::rb_step_kernel, launch_args.bt.B, RB_T_MEDIUM, sizeof(rgbm::RbLds) + rb_arena_bytes(m), 0, stream, m->dev_copy, launch_args);
+  return launch(rgb::rb_step_kernel, launch_args.bt.B, RB_T_LARGE, sizeof(rgb::RbLds), 0, stream, m->dev_copy, launch_args);
+}
 int rb_multi_begin(void) {
   if (g_multi) return fail("rb_multi_begin: already collecting");
   g_multi = new std::vector<RbCollected>();
@@ -1466,18 +1363,22 @@ int rb_multi_launch(void* stream) {
   ml.n = (int)v.size(); ml.group_size = v[0].b->dev.B;
   for (size_t k = 0; k < v.size(); k++) { ml.m[k] = v[k].b->model->dev_copy; ml.L[k] = v[k].launch; }
   const int total = ml.n * ml.group_size, cfg = v[0].b->model->config;
-#ifdef RG_EMUL
-  const size_t arena = 4 * (size_t)v[0].b->model->dev.lds_words + 16;
-  if (cfg == 1) emul_launch_n(total, RB_T_SMALL, sizeof(rgbs::RbLds) + arena, emul_rbs_multi_entry, &ml);
-  else emul_launch_n(total, RB_T_MEDIUM, sizeof(rgbm::RbLds) + arena, emul_rbm_multi_entry, &ml);
-#else
-  const size_t arena = v[0].b->model->dev.lds_words ? 4 * (size_t)v[0].b->model->dev.lds_words + 16 : 0;
-  if (cfg == 1) hipLaunchKernelGGL(rgbs::rb_step_multi_kernel, dim3(total), dim3(RB_T_SMALL), sizeof(rgbs::RbLds) + arena, (hipStream_t)stream, ml);
-  else hipLaunchKernelGGL(rgbm::rb_step_multi_kernel, dim3(total), dim3(RB_T_MEDIUM), sizeof(rgbm::RbLds) + arena, (hipStream_t)stream, ml);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
-}   // set by rb_batch_step_tcp around its launch
+  const size_t arena = rb_arena_bytes(v[0].b->model);
+  if (cfg == 1) return launch(rgbs::rb_step_multi_kernel, total, RB_T_SMALL, sizeof(rgbs::RbLds) + arena, 0, stream, ml);
+  return launch(rgbm::rb_step_multi_kernel, total, RB_T_MEDIUM, sizeof(rgbm::RbLds) + arena, 0, stream, ml);
+}
+int rb_batch_step_ex(rb_batch* b, const float* action_dev, const int* active_dev, const int* hold_dev, const int* nticks_dev, int nsubsteps, int nforward_ticks, int flags, void* stream) {
+  if (!b) return fail("null batch");
+  if (action_dev && !b->has_env) return fail("rb_batch_set_env must be called before stepping with actions");
+  if (nsubsteps < 0 || nforward_ticks < 0) return fail("rb_batch_step: negative step counts");
+  DeviceGuard g(b->device);
+  RbBatchDev bt = b->dev;
+  bt.action = action_dev; bt.active = active_dev; bt.hold = hold_dev; bt.nticks = nticks_dev;
+  RbLaunch launch_args{b->env, bt, nsubsteps, nforward_ticks, flags, RbTcpHook{}};
+  if (g_tcp_hook) { launch_args.tcp = *g_tcp_hook; }
+  if (g_multi) { g_multi->push_back(RbCollected{b, launch_args}); return 0; }
+  return rb_issue(b, launch_args, stream);
+}
 // JointControlledTcpArm.set_position_control as ONE launch of the solver simulation (RbTcpHook, rb_types.h)
 int rb_batch_step_tcp(rb_batch* solver, rb_batch* main_batch, const float* action_dev, const int* active_dev, const rb_tcp_args* a, int nsubsteps, int flags, void* stream) {
   if (a && a->self_world) main_batch = solver;      // tcp_solver_mode mocap: one world
@@ -1511,46 +1412,9 @@ int rb_batch_step_tcp(rb_batch* solver, rb_batch* main_batch, const float* actio
 int rb_batch_step(rb_batch* b, const float* action_dev, const int* active_dev, int nsubsteps, int nforward_ticks, int flags, void* stream) {
   return rb_batch_step_ex(b, action_dev, active_dev, nullptr, nullptr, nsubsteps, nforward_ticks, flags, stream);
 }
-int rb_batch_step_ex(rb_batch* b, const float* action_dev, const int* active_dev, const int* hold_dev, const int* nticks_dev, int nsubsteps, int nforward_ticks, int flags, void* stream) {
-  if (!b) return fail("null batch");
-  if (action_dev && !b->has_env) return fail("rb_batch_set_env must be called before stepping with actions");
-  if (nsubsteps < 0 || nforward_ticks < 0) return fail("rb_batch_step: negative step counts");
-  DeviceGuard g(b->device);
-  RbBatchDev bt = b->dev;
-  bt.action = action_dev; bt.active = active_dev; bt.hold = hold_dev; bt.nticks = nticks_dev;
-  RbLaunch launch{b->env, bt, nsubsteps, nforward_ticks, flags, RbTcpHook{}};
-  if (g_tcp_hook) { launch.tcp = *g_tcp_hook; }
-  if (g_multi) { g_multi->push_back(RbCollected{b, launch}); return 0; }
-  return rb_issue(b, launch, stream);
-}
-static int rb_issue(const rb_batch* b, const RbLaunch& launch, void* stream) {
-  const RbBatchDev& bt = launch.bt;
-  DeviceGuard g(b->device);
-#ifdef RG_EMUL
-  EmulRbArgs args{b->model->dev_copy, launch};
-  const size_t arena = 4 * (size_t)b->model->dev.lds_words + 16;
-  if (b->model->config == 1) emul_launch_n(bt.B, RB_T_SMALL, sizeof(rgbs::RbLds) + arena, emul_rbs_entry, &args);
-  else if (b->model->config == 2) emul_launch_n(bt.B, RB_T_MEDIUM, sizeof(rgbm::RbLds) + arena, emul_rbm_entry, &args);
-  else emul_launch_n(bt.B, RB_T_LARGE, sizeof(rgb::RbLds), emul_rb_entry, &args);
-#else
-  const size_t arena = b->model->dev.lds_words ? 4 * (size_t)b->model->dev.lds_words + 16 : 0;   // (+16: the arena starts at the next 16-byte boundary behind RbLds)
-  if (b->model->config == 1) hipLaunchKernelGGL(rgbs::rb_step_kernel, dim3(bt.B), dim3(RB_T_SMALL), sizeof(rgbs::RbLds) + arena, (hipStream_t)stream, b->model->dev_copy, launch);
-  else if (b->model->config == 2) hipLaunchKernelGGL(rgbm::rb_step_kernel, dim3(bt.B), dim3(RB_T_MEDIUM), sizeof(rgbm::RbLds) + arena, (hipStream_t)stream, b->model->dev_copy, launch);
-  else hipLaunchKernelGGL(rgb::rb_step_kernel, dim3(bt.B), dim3(RB_T_LARGE), sizeof(rgb::RbLds), (hipStream_t)stream, b->model->dev_copy, launch);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
-}
-
-#ifdef RG_EMUL
-struct EmulRbPostArgs { const RbModelDev* m; RbBatchDev bt; RbPostArgs a; };
-static void emul_rb_post_entry(void* p_) { EmulRbPostArgs* p = (EmulRbPostArgs*)p_; rgb::rb_post_step_kernel(p->m, p->bt, p->a); }
-struct EmulRbCubeArgs { RbBatchDev bt; int nq, col; const int* tab; const float* ops; int nops; };
-static void emul_rb_cube_entry(void* p_) { EmulRbCubeArgs* p = (EmulRbCubeArgs*)p_; rgb::rb_cube_ops_kernel(p->bt, p->nq, p->col, p->tab, p->ops, p->nops); }
-#endif
 int rb_post_args_size(void) { return (int)sizeof(rb_post_args); }
 int rb_env_post_step(rb_batch* b, const rb_post_args* args, void* stream) {
-  if (g_multi) return fail("rb_env_post_step: not recordable -- called between rb_multi_begin and rb_multi_launch it would run AHEAD of the recorded physics launches; issue it after rb_multi_launch");
+  if (g_multi) return not_recordable("rb_env_post_step");
   if (!b || !args) return fail("null argument");
   const rb_post_args& a = *args;
   const RbModelDev& d = b->model->dev;
@@ -1572,22 +1436,11 @@ int rb_env_post_step(rb_batch* b, const rb_post_args* args, void* stream) {
   if (a.cube_block_col < 0 || a.cube_block_col + 66 > d.nq || a.target_block_col < 0 || a.target_block_col + 66 > d.nq || a.cube_quat_col < 0 || a.cube_quat_col + 4 > d.nq ||
       a.cube_pos_col < 0 || a.cube_pos_col + 3 > d.nq || a.hand_col < 0 || a.hand_col + a.n_hand > d.nq) return fail("rb_env_post_step: qpos column out of range");
   DeviceGuard g(b->device);
-#ifdef RG_EMUL
-  EmulRbPostArgs ea{b->model->dev_copy, b->dev, a};
-  emul_launch(b->dev.B, 1024, emul_rb_post_entry, &ea);
-#else
-  hipLaunchKernelGGL(rgb::rb_post_step_kernel, dim3(b->dev.B), dim3(64), 0, (hipStream_t)stream, b->model->dev_copy, b->dev, a);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return launch(rgb::rb_post_step_kernel, b->dev.B, 64, 0, sizeof(rgb::RbPostLds), stream, b->model->dev_copy, b->dev, a);
 }
-#ifdef RG_EMUL
-struct EmulRaPostArgs { const RbModelDev* m; RbBatchDev bt; RaPostArgs a; };
-static void emul_ra_post_entry(void* p_) { EmulRaPostArgs* p = (EmulRaPostArgs*)p_; rgb::ra_post_step_kernel(p->m, p->bt, p->a); }
-#endif
 int ra_post_args_size(void) { return (int)sizeof(ra_post_args); }
 int ra_env_post_step(rb_batch* b, rb_batch* solver, const ra_post_args* args, void* stream) {
-  if (g_multi) return fail("ra_env_post_step: not recordable -- called between rb_multi_begin and rb_multi_launch it would run AHEAD of the recorded physics launches; issue it after rb_multi_launch");
+  if (g_multi) return not_recordable("ra_env_post_step");
   if (!b || !args) return fail("null argument");
   ra_post_args a = *args;
   const RbModelDev& d = b->model->dev;
@@ -1615,22 +1468,11 @@ int ra_env_post_step(rb_batch* b, rb_batch* solver, const ra_post_args* args, vo
     a.solver_qpos = solver->dev.qpos; a.solver_ctrl = solver->dev.ctrl; a.solver_nq = ds.nq; a.solver_nu = ds.nu;
   } else { a.solver_qpos = nullptr; a.solver_ctrl = nullptr; }
   DeviceGuard g(b->device);
-#ifdef RG_EMUL
-  EmulRaPostArgs ea{b->model->dev_copy, b->dev, a};
-  emul_launch(b->dev.B, 1024, emul_ra_post_entry, &ea);
-#else
-  hipLaunchKernelGGL(rgb::ra_post_step_kernel, dim3(b->dev.B), dim3(64), 0, (hipStream_t)stream, b->model->dev_copy, b->dev, a);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return launch(rgb::ra_post_step_kernel, b->dev.B, 64, 0, 0, stream, b->model->dev_copy, b->dev, a);   // (no LDS)
 }
-#ifdef RG_EMUL
-struct EmulRaRecipeArgs { const RbModelDev* m; RbBatchDev bt; const RbModelDev* ms; RbBatchDev sb; RaRecipeArgs a; };
-static void emul_ra_recipe_entry(void* p_) { EmulRaRecipeArgs* p = (EmulRaRecipeArgs*)p_; rgb::ra_recipe_kernel(p->m, p->bt, p->ms, p->sb, p->a); }
-#endif
 int ra_recipe_args_size(void) { return (int)sizeof(ra_recipe_args); }
 int ra_env_recipe_step(rb_batch* b, rb_batch* solver, const ra_recipe_args* args, void* stream) {
-  if (g_multi) return fail("ra_env_recipe_step: not recordable -- called between rb_multi_begin and rb_multi_launch it would run AHEAD of the recorded physics launches; issue it after rb_multi_launch");
+  if (g_multi) return not_recordable("ra_env_recipe_step");
   if (!b || !args) return fail("null argument");
   const ra_recipe_args& a = *args;
   const RbModelDev& d = b->model->dev;
@@ -1660,30 +1502,16 @@ int ra_env_recipe_step(rb_batch* b, rb_batch* solver, const ra_recipe_args* args
     sb = solver->dev; ms = solver->model->dev_copy;
   }
   DeviceGuard g(b->device);
-#ifdef RG_EMUL
-  EmulRaRecipeArgs ea{b->model->dev_copy, b->dev, ms, sb, a};
-  emul_launch(b->dev.B, 1024, emul_ra_recipe_entry, &ea);
-#else
-  hipLaunchKernelGGL(rgb::ra_recipe_kernel, dim3(b->dev.B), dim3(64), 0, (hipStream_t)stream, b->model->dev_copy, b->dev, ms, sb, a);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return launch(rgb::ra_recipe_kernel, b->dev.B, 64, 0, sizeof(rgb::RaRecipeLds), stream, b->model->dev_copy, b->dev, ms, sb, a);
 }
 int rb_cube_ops(rb_batch* b, int block_col, const int* cube_tab_dev, const float* ops_dev, int nops, const int* active_dev, void* stream) {
-  if (g_multi) return fail("rb_cube_ops: not recordable -- called between rb_multi_begin and rb_multi_launch it would run AHEAD of the recorded physics launches; issue it after rb_multi_launch");
+  if (g_multi) return not_recordable("rb_cube_ops");
   if (!b || !cube_tab_dev || !ops_dev || nops < 0) return fail("rb_cube_ops: bad argument");
   const RbModelDev& d = b->model->dev;
   if (block_col < 0 || block_col + 66 > d.nq) return fail("rb_cube_ops: block column out of range");
   DeviceGuard g(b->device);
   RbBatchDev bt = b->dev; bt.active = active_dev;
-#ifdef RG_EMUL
-  EmulRbCubeArgs ea{bt, d.nq, block_col, cube_tab_dev, ops_dev, nops};
-  emul_launch(bt.B, 1024, emul_rb_cube_entry, &ea);
-#else
-  hipLaunchKernelGGL(rgb::rb_cube_ops_kernel, dim3(bt.B), dim3(64), 0, (hipStream_t)stream, bt, d.nq, block_col, cube_tab_dev, ops_dev, nops);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
+  return launch(rgb::rb_cube_ops_kernel, bt.B, 64, 0, (RBC_BLOCK + 2) * sizeof(float), stream, bt, d.nq, block_col, cube_tab_dev, ops_dev, nops);
 }
 
 int rg_sync(void* stream) {
