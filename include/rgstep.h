@@ -390,9 +390,11 @@ int rb_tcp_args_size(void);   /* sizeof(rb_tcp_args): a binding checks its own l
  * at most 8), or one launch each, in order, when they do not match.  Results are those of the separate launches, bit for bit.
  * While recording: the `stream` argument of the recorded calls is IGNORED (rb_multi_launch's stream is the one); a batch may be recorded once only
  * (rb_multi_launch refuses a duplicate: two workgroups would step the same rows); the entry points that are not recordable -- rb_env_post_step, ra_env_post_step,
- * ra_env_recipe_step, rb_cube_ops -- fail instead of running ahead of the recorded physics. */
+ * ra_env_recipe_step, rb_cube_ops, rb_batch_set_constants -- fail instead of running ahead of the recorded physics. */
 int rb_multi_begin(void);
 int rb_multi_launch(void* stream);
+/* mj_setConst on the large-model stepper: rb_batch_set_constants, the counterpart of rg_batch_set_constants: the three _invweight0 rows of the masked envs'
+ * parameter blocks recomputed on the device from their own rows by rb_setconst_kernel.  Declared and described in rgstep_setconst.h, which the end of this header includes. */
 /* ---- the env-level half of RearrangeEnv.step (one launch after the two physics launches; robogym_amd/csrc/ra_env_kernel.h lists the
  * reference call sites): the 24-key observation of envs/rearrange/common/base.py:376-421 as one packed row per env — obj_pos 3N | obj_rel_pos 3N |
  * obj_vel_pos 3N | obj_rot 3N | obj_vel_rot 3N | robot_joint_pos 6 | gripper_pos 3 | gripper_velp 3 | gripper_controls 1 | gripper_qpos 1 |
@@ -549,4 +551,5 @@ const char* rg_last_error(void);
 #ifdef __cplusplus
 }
 #endif
+#include "rgstep_setconst.h"
 #endif

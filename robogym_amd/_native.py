@@ -129,6 +129,8 @@ EXPORTS = [
     "rg_blob_entry", "rg_model_blob_keys", "rb_model_blob_keys", "rg_compile_mjcf", "rb_compile_mjcf", "rg_compile_mjcf_blob", "rg_blob_free",
     "rb_model_enable_env_params", "rb_prm_layout", "rb_batch_set_action_limits", "ra_env_recipe_step", "ra_recipe_args_size", "rb_tcp_args_size", "rb_multi_begin", "rb_multi_launch",
 ]
+EXPORTS_SETCONST = ["rb_batch_set_constants"]      # include/rgstep_setconst.h (EXPORTS is what include/rgstep.h itself declares)
+
 
 
 class NativeError(RuntimeError):
@@ -205,6 +207,7 @@ def bind(path):
     L.rb_batch_step_ex.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, vp]
     L.rb_batch_step_tcp.argtypes = [vp, vp, vp, vp, ctypes.POINTER(RbTcpArgs), ci, ci, vp]
     L.rb_multi_launch.argtypes = [vp]
+    L.rb_batch_set_constants.argtypes = [vp, vp, vp]
     L.rb_tcp_args_size.restype = ci
     if L.rb_tcp_args_size() != ctypes.sizeof(RbTcpArgs):
         raise NativeError("rb_tcp_args layout mismatch between include/rgstep.h and robogym_amd/_native.py")

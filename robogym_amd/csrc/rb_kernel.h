@@ -2993,4 +2993,150 @@ __global__ void __launch_bounds__(RB_T, RB_WG_PER_CU) rb_step_multi_kernel(RbMul
 #endif
 }
 #endif
+
+// ------------------------------------------------------------------------------------------------- mj_setConst on the device
+// rb_setconst_kernel: the large-model counterpart of rg_setconst_kernel (rg_kernel.h).  The reference calls mujoco_simulation.set_constants() in every dactyl _reset
+// after the randomizers wrote the model (cube_env.py:346-349, simulation_interface.py:199-201); robogym_amd/mujoco/setconst.py:234-263 is the definition.  For every
+// env of the mask, from the env's CURRENT parameter block (body_pos / body_mass / body_inertia / dof_armature / site_pos / geom_pos): the position stages at qpos0
+// (rb_kinematics, rb_com_pos, rb_tendon, rb_crb -- the step kernel's own stage functions), then products with inv(M) through the step kernel's own M solves, and
+//   dof_invweight0[d]  = diag(inv(M)), averaged over the three components of a ball joint and over each half of a free joint,
+//   body_invweight0[b] = (tr(Jp inv(M) Jp') / 3, tr(Jr inv(M) Jr') / 3) at the body's com, floored at 1e-15; 0 for bodies welded to the world (mocap bodies included),
+//   tendon_invweight0[t] = Jt inv(M) Jt', floored at 1e-15,
+// written into the same block.  M is block-diagonal over the kinematic trees and a body's Jacobian lives on its own dof chain: the work is ordered by UNIT -- all
+// trees at once where rb_trees8_solve applies (the rearrange worlds), one star tree (rb_star_solve: the hand, each cube), or one dense group (rb_M_block, factored
+// once per unit on the configurations with several waves, in registers per right-hand side on the one-wave ones) -- and every right-hand side is solved on its unit
+// only: nv + 6 per moving body + 1 per tendon solves per env (full cube: 168 + 6 x 130 + 12 = 960), no inverse is ever formed.  The right-hand side sits in s.grad
+// (zero outside the chain in hand), the solution in s.search; the stage arrays are the env's scratch row, as in the step kernel, so nothing has to survive a
+// factorisation in LDS.  Side effect: the frame / inertia arrays of the env's scratch row hold the qpos0 configuration afterwards (every step launch recomputes
+// them from its qpos before it reads them).  A non-positive pivot sets RG_STATUS_BAD_FACTOR in the env's status word (pivots are clamped: nothing becomes NaN).
+// stat_meaninertia, body_subtreemass, actuator_acc0 and tendon_length0 stay the model's.
+#define RB_SC_TREES8 0
+#define RB_SC_STAR 1
+#define RB_SC_DENSE 2
+__device__ __forceinline__ bool rb_sc_in_unit(RbM m, int kind, int u, int root_body, int dof) {
+  return kind == RB_SC_TREES8 ? true : (kind == RB_SC_STAR ? m.body_rootid[m.dof_bodyid[dof]] == root_body : m.b_dof_group[dof] == u);
+}
+// s.search[dofs of the unit] = inv(M_unit) s.grad[dofs of the unit] (a call of its own: one copy of the solves for the three loops of sc_unit)
+RB_STAGE void sc_solve(RbCtx c, int kind, int u) {
+  RB_STAGE_ENTER();
+  if (kind == RB_SC_TREES8) rb_trees8_solve(m, s, SC(MSP), (const float*)0, 0.f, s.grad, s.search, 1.f);
+  else if (kind == RB_SC_STAR) rb_star_solve(m, s, SC(MSP), u, (const float*)0, 0.f, s.grad, s.search, 1.f);
+  else {
+#if RB_T == 64 && !defined(RB_LDS_CHOL)
+    if (!rb_reg_solve(m, s, u, s.grad, s.search, 1.f) && TID == 0) s.status |= RG_STATUS_BAD_FACTOR;
+#else
+    rb_group_solve(m, s, u, s.grad, s.search, 1.f);
+#endif
+  }
+}
+RB_STAGE void sc_unit(RbCtx c, int kind, int u) {
+  RB_STAGE_ENTER();
+  const int nv = m.nv;
+  const int root_body = kind == RB_SC_STAR ? m.body_rootid[m.dof_bodyid[m.b_tree_desc[4 * u + 1]]] : 0;
+  float *dof_iw = S + m.prm_off[RB_P_DOF_INVWEIGHT0], *body_iw = S + m.prm_off[RB_P_BODY_INVWEIGHT0], *ten_iw = S + m.prm_off[RB_P_TENDON_INVWEIGHT0];
+  const float* cdof = SC(CDOF);
+  if (kind == RB_SC_DENSE) {   // the group's block of M: read by every solve of the unit (factored here once where the substitutions work from LDS)
+    rb_M_block(m, s, SC(MSP), u, (const float*)0, 0.f);
+#if !(RB_T == 64 && !defined(RB_LDS_CHOL))
+    const int n = m.b_group_adr[u + 1] - m.b_group_adr[u];
+    rb_scale_block(s, n);
+    if (!rb_chol(s, n) && TID == 0) s.status |= RG_STATUS_BAD_FACTOR;
+#endif
+  }
+  // ---- dof_invweight0: unit vectors (the averages over ball / free joints follow when every unit is done)
+  for (int i = 0; i < nv; i++) {
+    if (!rb_sc_in_unit(m, kind, u, root_body, i)) continue;
+    if (TID == 0) s.grad[i] = 1.f;
+    BSYNC();
+    sc_solve(c, kind, u);
+    if (TID == 0) { dof_iw[i] = s.search[i]; s.grad[i] = 0.f; }
+  }
+  // ---- body_invweight0: the six rows of the com Jacobian, each on the body's dof chain (thread k holds the chain's k-th dof; a chain has at most nv < RB_T dofs)
+  for (int b = 1; b < m.nbody; b++) {
+    const int last = m.b_body_lastdof[b];
+    if (m.body_weldid[b] == 0 || last < 0) continue;
+    if (!rb_sc_in_unit(m, kind, u, root_body, last)) continue;
+    int mine = -1;
+    { int k = 0; for (int i = last; i >= 0; i = m.dof_parentid[i], k++) if (k == TID) mine = i; }
+    v3 jp = mk3(0, 0, 0), jr = mk3(0, 0, 0);
+    if (mine >= 0) {
+      const v3 off = ld3(SC(XIPOS) + 3 * b) - ld3(SC(ROOTCOM) + 3 * m.body_rootid[b]);
+      jr = ld3(cdof + 6 * mine); jp = rb_jacp(cdof, mine, off);
+    }
+    float tr0 = 0.f, tr1 = 0.f;
+    for (int k = 0; k < 6; k++) {
+      const float v = k == 0 ? jp.x : k == 1 ? jp.y : k == 2 ? jp.z : k == 3 ? jr.x : k == 4 ? jr.y : jr.z;
+      if (mine >= 0) s.grad[mine] = v;
+      BSYNC();
+      sc_solve(c, kind, u);
+      const float w = rb_sum(s, mine >= 0 ? v * s.search[mine] : 0.f);
+      if (k < 3) tr0 += w; else tr1 += w;
+    }
+    if (mine >= 0) s.grad[mine] = 0.f;
+    if (TID == 0) { body_iw[2 * b] = fmaxf(RB_MINVAL, tr0 * (1.f / 3.f)); body_iw[2 * b + 1] = fmaxf(RB_MINVAL, tr1 * (1.f / 3.f)); }
+    BSYNC();   // (the next chain's dofs sit in other threads: their writes must come after this chain's zeros)
+  }
+  // ---- tendon_invweight0: the part of the tendon's Jacobian on this unit (inv(M) is block-diagonal over the units: the parts add up)
+  for (int t = 0; t < m.ntendon; t++) {
+    const int* td = m.b_ten_dofs + RB_TENW * t;
+    bool any = false;
+    for (int q = 0; q < RB_TENW; q++) { const int d = td[q]; if (d >= 0 && rb_sc_in_unit(m, kind, u, root_body, d)) any = true; }
+    if (!any) continue;
+    int mine = -1; float v = 0.f;
+    if (TID < RB_TENW) { const int d = td[TID]; if (d >= 0 && rb_sc_in_unit(m, kind, u, root_body, d)) { mine = d; v = SC(TENJ)[RB_TENW * t + TID]; } }
+    if (mine >= 0) s.grad[mine] = v;
+    BSYNC();
+    sc_solve(c, kind, u);
+    const float w = rb_sum(s, mine >= 0 ? v * s.search[mine] : 0.f);
+    if (mine >= 0) s.grad[mine] = 0.f;
+    if (TID == 0) ten_iw[t] += w;
+    BSYNC();
+  }
+  BSYNC();
+}
+__device__ __forceinline__ void rb_setconst_body(const RbModelDev* mp, RbKlp klp, const int e) {
+  RB_MAKE_CTX();
+  RbLds& s = RB_S();
+  if (e >= L.bt.B || !m.prm_on) return;
+  if (L.bt.active && !L.bt.active[e]) return;       // a masked env's block is not touched
+  float* S = L.bt.scratch + (size_t)e * m.scratch_words;
+  const RbCtx c{(const void*)mp, (const void*)klp, S};
+  BFOR(i, m.nq) s.qpos[i] = m.qpos0[i];
+  BFOR(i, m.nv) { s.grad[i] = 0.f; s.search[i] = 0.f; }
+  if (TID == 0) {
+    s.status = 0; s.env = e; s.time = 0.f; s.has_xfrc = 0; s.stop = 0; s.neqcon = 0;
+    s.mass_default = 0;                              // the subtree masses are summed from the env's own body_mass row
+    s.timestep = S[m.prm_off[RB_P_TIMESTEP]]; s.gscale = S[m.prm_off[RB_P_GEOM_SCALE]];
+  }
+  if (TID < 7 * m.nmocap && TID < 14) s.mocap[TID] = L.bt.mocap[(size_t)e * 7 * m.nmocap + TID];   // (mocap bodies are welded: their pose enters no output)
+  BSYNC();
+  sb_position(c); sb_tendon(c); sb_crb(c);
+  float *dof_iw = S + m.prm_off[RB_P_DOF_INVWEIGHT0], *body_iw = S + m.prm_off[RB_P_BODY_INVWEIGHT0], *ten_iw = S + m.prm_off[RB_P_TENDON_INVWEIGHT0];
+  BFOR(t, m.ntendon) ten_iw[t] = 0.f;
+  BFOR(b, m.nbody) if (b == 0 || m.body_weldid[b] == 0 || m.b_body_lastdof[b] < 0) { body_iw[2 * b] = 0.f; body_iw[2 * b + 1] = 0.f; }
+  BSYNC();
+  if (m.b_tree8[0] > 0) sc_unit(c, RB_SC_TREES8, 0);
+  else for (int g = 0; g < m.ngroup; g++) {
+    if (m.b_star_grp[4 * g + 3]) { for (int t = m.b_tree_adr[g]; t < m.b_tree_adr[g + 1]; t++) sc_unit(c, RB_SC_STAR, t); }
+    else sc_unit(c, RB_SC_DENSE, g);
+  }
+  BFOR(j, m.njnt) {
+    const int da = m.jnt_dofadr[j], t = m.jnt_type[j];
+    if (t != RG_JNT_FREE && t != RG_JNT_BALL) continue;
+    for (int h = 0; h < (t == RG_JNT_FREE ? 2 : 1); h++) {
+      float* d = dof_iw + da + 3 * h;
+      const float a = (d[0] + d[1] + d[2]) * (1.f / 3.f);
+      d[0] = a; d[1] = a; d[2] = a;
+    }
+  }
+  BFOR(t, m.ntendon) ten_iw[t] = fmaxf(RB_MINVAL, ten_iw[t]);
+  if (TID == 0 && s.status) L.bt.status[e] |= s.status;
+}
+__global__ void __launch_bounds__(RB_T, RB_WG_PER_CU) rb_setconst_kernel(const RbModelDev* mp, RbLaunch launch) {
+#ifdef RG_EMUL
+  rb_setconst_body(mp, &launch, (int)blockIdx.x);
+#else
+  rb_setconst_body(mp, (const RG_AS4 char*)__builtin_amdgcn_kernarg_segment_ptr() + 8, (int)blockIdx.x);
+#endif
+}
 }  // namespace rgb

@@ -1412,6 +1412,20 @@ int rb_batch_step_tcp(rb_batch* solver, rb_batch* main_batch, const float* actio
 int rb_batch_step(rb_batch* b, const float* action_dev, const int* active_dev, int nsubsteps, int nforward_ticks, int flags, void* stream) {
   return rb_batch_step_ex(b, action_dev, active_dev, nullptr, nullptr, nsubsteps, nforward_ticks, flags, stream);
 }
+// mj_setConst on the device for the envs of the mask (rb_setconst_kernel, rb_kernel.h): one workgroup per env on the model's configuration, the LDS of a step launch
+int rb_batch_set_constants(rb_batch* b, const int* mask_dev, void* stream) {
+  if (g_multi) return not_recordable("rb_batch_set_constants");
+  if (!b) return fail("null batch");
+  const rb_model* m = b->model;
+  if (!m->dev.prm_on) return fail("rb_batch_set_constants: the batch has no per-env parameter rows (rb_model_enable_env_params); the model's own constants are already consistent");
+  DeviceGuard g(b->device);
+  RbBatchDev bt = b->dev;
+  bt.action = nullptr; bt.active = mask_dev; bt.hold = nullptr; bt.nticks = nullptr;
+  RbLaunch launch_args{b->env, bt, 0, 0, 0, RbTcpHook{}};
+  if (m->config == 1) return launch(rgbs::rb_setconst_kernel, bt.B, RB_T_SMALL, sizeof(rgbs::RbLds) + rb_arena_bytes(m), 0, stream, m->dev_copy, launch_args);
+  if (m->config == 2) return launch(rgbm::rb_setconst_kernel, bt.B, RB_T_MEDIUM, sizeof(rgbm::RbLds) + rb_arena_bytes(m), 0, stream, m->dev_copy, launch_args);
+  return launch(rgb::rb_setconst_kernel, bt.B, RB_T_LARGE, sizeof(rgb::RbLds), 0, stream, m->dev_copy, launch_args);
+}
 int rb_post_args_size(void) { return (int)sizeof(rb_post_args); }
 int rb_env_post_step(rb_batch* b, const rb_post_args* args, void* stream) {
   if (g_multi) return not_recordable("rb_env_post_step");

@@ -4,7 +4,7 @@ robogym_amd/csrc/rb_kernel.h): BASELINE.json configs[2], dactyl/full_perpendicul
 state fields as zero-copy `[B, n]` tensor views, `reset`, `step` / `env_step`, joint groups.  No CPU fallback: the gfx950
 library and a GPU are required (tests may pass `lib=` = the kernel source on the emulation harness, as for the other kernels)."""
 import ctypes
-from typing import Dict
+from typing import Dict, Optional
 
 import numpy as np
 import torch
@@ -173,6 +173,21 @@ class LargeModelSimulation:
         self._keep = [action, args, active]
         assert active is None or (active.dtype == torch.int32 and active.is_contiguous() and active.shape == (self.batch_size,))
         _native.check(self._L, self._L.rb_batch_step_tcp(self._bh, main._bh, None if action is None else ctypes.c_void_p(action.data_ptr()), None if active is None else ctypes.c_void_p(active.data_ptr()), ctypes.byref(args), self.n_substeps, flags, stream), "rb_batch_step_tcp")
+
+    def set_constants(self, mask: Optional[torch.Tensor] = None):
+        """`SimulationInterface.set_constants` (simulation_interface.py:199-201 -> MjSim.set_constants -> mj_setConst), which the
+        reference calls in every dactyl `_reset` after the randomizers have written the model (cube_env.py:346-349): recompute
+        dof / body / tendon `_invweight0` of the masked envs (bool or int32 `[B]`; None: all) from each env's own body_pos / mass /
+        inertia / armature / site_pos row, on the device (`rb_setconst_kernel`), asynchronously on the current stream.  A
+        simulation without parameter rows has nothing to refresh (the model's own constants are consistent)."""
+        if not self._env_params:
+            return
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=torch.int32).contiguous()
+            assert mask.shape == (self.batch_size,)
+        stream = None if self._emul else ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _native.check(self._L, self._L.rb_batch_set_constants(self._bh, None if mask is None else ctypes.c_void_p(mask.data_ptr()), stream), "rb_batch_set_constants")
+        self._keep_mask = mask   # (the launch is asynchronous: the mask must outlive it)
 
     def step(self, active=None):
         """SimulationInterface.step: nsubsteps x mj_step, then mj_forward (its PID tick)."""

@@ -10,7 +10,8 @@ into the rows the kernel reads (include/rgstep.h RG_F_ENVPRM), a randomizer draw
 being reset) and writes them with ordinary tensor ops: no host loop, no synchronisation.  The per-episode formulas are the
 reference's; what is folded in is the ADR parameter plumbing (`_randomizer_param_values` is a constructor argument here).
 Mass / inertia / armature changes need the mj_setConst outputs recomputed (`*_invweight0`: regulariser scales of the
-constraint rows); `refresh_constants` does that on the host with robogym_amd/mujoco/setconst.py for the distinct rows.
+constraint rows); `refresh_constants` does that on the device through the simulation's `set_constants(mask)` (rg_setconst_kernel on
+the hand stepper, rb_setconst_kernel on `LargeModelSimulation` / `FullPerpendicularSimulation`): no host loop, no synchronisation.
 """
 from typing import Optional, Sequence
 
@@ -198,7 +199,8 @@ class _RowSubset:   # (placeholder type for _field(); GenericSimRandomizer.rando
 def refresh_constants(sim, rows: Optional[Sequence[int]] = None):
     """mj_setConst for the envs whose mass / inertia / armature rows were changed (the reference calls
     `mujoco_simulation.set_constants()` in `_reset`, cube_env.py:349): dof / body / tendon `_invweight0` recomputed ON THE
-    DEVICE from each env's own row (`sim.set_constants`, rg_setconst_kernel); no host loop, no synchronisation."""
+    DEVICE from each env's own row (`sim.set_constants`: rg_setconst_kernel, or rb_setconst_kernel on the large-model stepper); no host loop, no
+    synchronisation."""
     if rows is None:
         sim.set_constants()
         return
