@@ -435,6 +435,10 @@ typedef struct ra_post_args {
   int goal_kind;
   int grip_site;                                 /* site robot0:grip (kinds 2-4) */
   float* goal_dist_extra;                        /* [B][2] kind 2: sums of the gripper_pos distances and of `grasped`; NULL otherwise */
+  /* duplicated-object groups (appended; NULL = all objects distinct, the path above).  [B][N] group id of each object; objects with equal ids are interchangeable:
+   * ObjectStateGoal.relative_goal (goals/object_state.py:520-554) matches objects to goals inside each group greedily by position distance, and the relative goal,
+   * both distances and the success count go through that match.  goal_obj_pos / goal_obj_rot / qpos_goal stay indexed by goal.  Kinds 0-2 only. */
+  const int* obj_group;
 } ra_post_args;
 int ra_env_post_step(rb_batch* main, rb_batch* solver, const ra_post_args* args, void* stream);
 int ra_post_args_size(void);
@@ -477,6 +481,19 @@ typedef struct ra_recipe_args {
   float target_height;
   float det_points[2][3];
   int* goal_index;                               /* [B] kind 4 */
+  /* duplicated-object groups (appended; zero-filled = none).  obj_group: ra_post_args' [B][N] row, NULL = all distinct.  group_mode 0: the rows are the caller's
+   * and stay; 1: an env whose episode ends gets a new row from sample_group_counts (common/utils.py:47-73: until the objects are used up lam ~ U(sample_lam), then a
+   * count k in 1..remaining with probability proportional to exp(-k lam)), ids 0, 1, ... over contiguous ranges of objects; draws (seed ^ 0x85EBCA6B, step, env, 3000 + ...): a stream of their own. */
+  int* obj_group;
+  int group_mode;
+  float sample_lam[2];
+  /* goal kind 5, TrainStateGoal (goals/train_state.py; recipe only: ra_post_args scores it as kind 0).  place_targets_with_goal_distance_ratio (common/utils.py:922-994):
+   * per object a uniform proposal inside the area pulled toward the object's position by clip(goal_distance_ratio[env], goal_distance_min / dist if dist >=
+   * goal_distance_min else 0, 1), accepted through _place_objects' collision check (100 restarts x 20 retries per object), then
+   * move_one_object_to_the_air_with_restrictions: one uniform p; p < pickup_proba: one object raised by U(height_range) * ratio; p <= pickup_proba + stacking_proba: a
+   * tower of 2..N objects (a random subset, the first stays, the h-th other gets its x, y and + object_size * (h + 1) * 2 in z). */
+  const float* goal_distance_ratio;              /* [B], NULL = 1 */
+  float goal_distance_min, pickup_proba, stacking_proba;
 } ra_recipe_args;
 int ra_env_recipe_step(rb_batch* main, rb_batch* solver, const ra_recipe_args* args, void* stream);
 int ra_recipe_args_size(void);

@@ -92,7 +92,8 @@ def _ra_post_fields():
                                  "penalty_table_collision", "penalty_objects_off_table", "penalty_safety_stop", "safety_stop_force")]
             + [(n, _i) for n in ("max_timesteps_per_goal", "successes_needed", "use_goal_distance_reward")]
             + [("solver_qpos", _p), ("solver_ctrl", _p), ("solver_nq", _i), ("solver_nu", _i), ("solver_grip_qposadr", _i), ("solver_grip_act", _i), ("frozen", _p), ("reward_clip", _f)]
-            + [("goal_kind", _i), ("grip_site", _i), ("goal_dist_extra", _p)])
+            + [("goal_kind", _i), ("grip_site", _i), ("goal_dist_extra", _p)]
+            + [("obj_group", _p)])
 
 
 class RaPostArgs(ctypes.Structure):
@@ -110,7 +111,9 @@ def _ra_recipe_fields():
             + [("obj_qposadr", _i * RA_MAXOBJ), ("arm_qposadr", _i * 6), ("solver_arm_qposadr", _i * 6), ("arm_start", _f * 6), ("obj_center", (_f * 3) * RA_MAXOBJ),
                ("obj_half", (_f * 3) * RA_MAXOBJ), ("area_offset", _f * 2), ("area_size", _f * 2), ("table_pos", _f * 3), ("table_size", _f * 3), ("stabilize_steps", _i),
                ("n_random_initial_steps", _i), ("settle_steps", _i), ("seed", ctypes.c_uint), ("step", ctypes.c_uint)]
-            + [("goal_kind", _i), ("height_range", _f * 2), ("object_size", _f), ("fixed_order", _i), ("target_height", _f), ("det_points", (_f * 3) * 2), ("goal_index", _p)])
+            + [("goal_kind", _i), ("height_range", _f * 2), ("object_size", _f), ("fixed_order", _i), ("target_height", _f), ("det_points", (_f * 3) * 2), ("goal_index", _p)]
+            + [("obj_group", _p), ("group_mode", _i), ("sample_lam", _f * 2)]
+            + [("goal_distance_ratio", _p), ("goal_distance_min", _f), ("pickup_proba", _f), ("stacking_proba", _f)])
 
 
 class RaRecipeArgs(ctypes.Structure):

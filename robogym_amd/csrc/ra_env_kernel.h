@@ -8,7 +8,7 @@
 //                                                                 robot/ur16e/mujoco/simulation/base.py:142-167 (gripper - table plane)
 //   check_objects_off_table                                       envs/rearrange/simulation/base.py:805-832
 //   reward / done                                                 envs/rearrange/common/base.py:768-795, 824-848
-//   ObjectStateGoal.relative_goal / goal_distance                 envs/rearrange/goals/object_state.py:492-599 (rot_dist_type "full", all objects distinct)
+//   ObjectStateGoal.relative_goal / goal_distance                 envs/rearrange/goals/object_state.py:492-599 (rot_dist_type "full"; duplicated-object groups: ra_group_match)
 //   _get_goal_info, MultiGoalTracker.process                      robot_env.py:577-625, utils/multi_goal_tracker.py:157-241
 //   JointControlledTcpArm.on_observations_updated                 robot/ur16e/mujoco/joint_controlled_tcp_arm.py:114-129 (gripper state -> solver world)
 // Rotation helpers follow robogym/utils/rotation.py (mat2euler, quat2mat, normalize_angles) as rb_env_kernel.h's rbc_* do.
@@ -16,6 +16,52 @@
 #include "rb_env_kernel.h"
 
 namespace rgb {
+
+// ObjectStateGoal.relative_goal's matching of interchangeable objects to goals (goals/object_state.py:520-554), one wave per env: returns, on lane i < N, the goal j
+// that object i is measured against.  The reference goes group by group: the n x n matrix of |obj_pos[i] - goal_pos[j]| over the group's objects, n times
+// np.argmin (row-major: the lowest flat index among equal minima) -> pair (i, j), then row i and column j set to +inf.  Here ONE N x N matrix over all objects, the
+// pairs that cross a group at +inf from the start, and N rounds of a wave-wide minimum.  The two are the same matching: a wipe clears a row and a column, whose finite
+// entries all lie inside the picked pair's own group, so the pairs a group still has alive are exactly those its own loop would have; the global minimum of a round is
+// the minimum of SOME group, and it is the pair that group's loop would pick next (inside a group the flat index i * N + j orders pairs as the group's own i' * n + j'
+// does, its objects being listed in increasing id); rounds of different groups commute.  Every group of size n receives exactly n of the N picks.
+// Squared distances are compared (the square root is monotone).  Pair p = i * N + j lives on lane p % 64, slot p / 64 (N <= 16: at most 4 per lane); the wiped
+// rows / columns are two 16-bit masks, the same on every lane.  A distance that is not finite is never picked: such an object keeps its own goal.
+__device__ inline int ra_group_match(const int* grp, const float* xpos, const int* obj_body, const float* goal, int N, int lane) {
+  float d[4];
+  for (int s = 0; s < 4; s++) {
+    const int p = lane + 64 * s;
+    d[s] = INFINITY;
+    if (p < N * N) {
+      const int i = p / N, j = p - i * N;
+      if (grp[i] == grp[j]) {
+        const float* x = xpos + 3 * obj_body[i]; const float* g = goal + 7 * j;
+        const float dx = x[0] - g[0], dy = x[1] - g[1], dz = x[2] - g[2];
+        d[s] = dx * dx + dy * dy + dz * dz;
+      }
+    }
+  }
+  unsigned rows = 0u, cols = 0u;
+  int mine = lane;
+  for (int round = 0; round < N; round++) {
+    float best = INFINITY; int at = 0x7fffffff;
+    for (int s = 0; s < 4; s++) {      // (ascending flat index: the strict < keeps the lowest among equals)
+      const int p = lane + 64 * s;
+      if (p < N * N) {
+        const int i = p / N, j = p - i * N;
+        if (!((rows >> i) & 1u) && !((cols >> j) & 1u) && d[s] < best) { best = d[s]; at = p; }
+      }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ob = __shfl_xor(best, o); const int oa = __shfl_xor(at, o);
+      if (ob < best || (ob == best && oa < at)) { best = ob; at = oa; }
+    }
+    if (at == 0x7fffffff) break;        // (wave-uniform: every lane holds the same pair)
+    const int i = at / N, j = at - i * N;
+    rows |= 1u << i; cols |= 1u << j;
+    if (lane == i) mine = j;
+  }
+  return mine;
+}
 
 __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, RbBatchDev bt, RaPostArgs a) {
   const RbModelDev& m = *mp;
@@ -46,6 +92,8 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
   float dpos = 0.f, drot = 0.f, dgrip = 0.f, grasp = 0.f;
   const int reach = a.goal_kind >= 3;
   const float* grip = S + m.off[RB_O_SPOS] + 3 * a.grip_site;      // (kinds 2-4 only)
+  int mgoal = lane;                              // the goal this lane's object is measured against: its own, or its match inside its group of duplicates
+  if (a.obj_group) mgoal = ra_group_match(a.obj_group + (size_t)e * N, xpos, a.obj_body, a.goal + (size_t)e * N * 7, N, lane);
   if (lane < N) {
     const int b = a.obj_body[lane];
     float M[9], eul[3], vp[3], vr[3];
@@ -53,14 +101,15 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
     rbc_mat2euler(M, eul);
     for (int k = 0; k < 3; k++) eul[k] = rbc_wrap(eul[k]);
     body_vel(b, vp, vr);
-    const float* gp = a.goal + ((size_t)e * N + lane) * 7;
+    const float* gp = a.goal + ((size_t)e * N + lane) * 7;        // goal_obj_pos / goal_obj_rot stay indexed by goal
+    const float* gm = a.goal + ((size_t)e * N + mgoal) * 7;
     float qc[4] = {xquat[4 * b], -xquat[4 * b + 1], -xquat[4 * b + 2], -xquat[4 * b + 3]}, qd[4], Md[9], rel[3];
     if (reach) { qc[0] = 1.f; qc[1] = qc[2] = qc[3] = 0.f; }      // ObjectReachGoal.current_state: the achieved rotation is zero
-    rbc_qmul(gp + 3, qc, qd);                 // subtract_euler(goal, current) = quat2euler(q_goal conj(q_obj))
+    rbc_qmul(gm + 3, qc, qd);                 // subtract_euler(goal, current) = quat2euler(q_goal conj(q_obj))
     rbc_quat2mat(qd, Md); rbc_mat2euler(Md, rel);
     for (int k = 0; k < 3; k++) rel[k] = rbc_wrap(rel[k]);
     const float* ach = reach ? grip : xpos + 3 * b;                // ... and the achieved position the grip site's
-    const float rx = gp[0] - ach[0], ry = gp[1] - ach[1], rz = gp[2] - ach[2];
+    const float rx = gm[0] - ach[0], ry = gm[1] - ach[1], rz = gm[2] - ach[2];
     dpos = fmaxf(sqrtf(rx * rx + ry * ry + rz * rz) + a.goal_pos_offset, 0.f);
     rbc_qsign(qd);
     { const float n = sqrtf(qd[0] * qd[0] + qd[1] * qd[1] + qd[2] * qd[2] + qd[3] * qd[3]); for (int k = 0; k < 4; k++) qd[k] /= n; }
@@ -291,6 +340,51 @@ __device__ inline bool ra_place(const RaRecipeArgs& a, int N, bool no_grid, cons
   return ok;
 }
 
+// place_targets_with_goal_distance_ratio (common/utils.py:922-994) through _place_objects (:623-716): per object, in object order, a uniform proposal for the centre of
+// its bounding box inside the placement area, pulled toward the object's own position (`qrow`: the env's qpos row) by clip(ratio, dmin / dist if dist >= dmin else 0, 1),
+// rejected while its box overlaps a goal already placed; an object that runs out of its 1 + 20 proposals restarts the set, up to 100 sets.  Returns false when those ran
+// out (out = the last proposals).
+__device__ inline bool ra_place_near(const RaRecipeArgs& a, int N, const float* yaw, int ystride, const float* qrow, float ratio_in, unsigned seed, unsigned step, unsigned e, unsigned& k,
+                                     float (*out)[3]) {
+  auto U = [&]() -> float { return (float)(rbp_hash(seed, step, e, k++) >> 8) * (1.0f / 16777216.0f); };
+  float hx[RA_MAXOBJ], hy[RA_MAXOBJ], cx[RA_MAXOBJ], cy[RA_MAXOBJ], px[RA_MAXOBJ], py[RA_MAXOBJ];
+  const float width = a.area_size[0], height = a.area_size[1];
+  for (int i = 0; i < N; i++) {
+    const float c = cosf(yaw[i * ystride]), s_ = sinf(yaw[i * ystride]);
+    hx[i] = fabsf(c) * a.obj_half[i][0] + fabsf(s_) * a.obj_half[i][1]; hy[i] = fabsf(s_) * a.obj_half[i][0] + fabsf(c) * a.obj_half[i][1];
+    cx[i] = c * a.obj_center[i][0] - s_ * a.obj_center[i][1]; cy[i] = s_ * a.obj_center[i][0] + c * a.obj_center[i][1];
+    px[i] = py[i] = 0.f;
+  }
+  bool ok = false;
+  for (int round = 0; round < 100 && !ok; round++) {
+    ok = true;
+    for (int i = 0; i < N && ok; i++) {
+      // the object's box centre relative to the placement area
+      const float x = qrow[a.obj_qposadr[i]] - a.area_offset[0] + a.table_size[0] - a.table_pos[0] + cx[i];
+      const float y = qrow[a.obj_qposadr[i] + 1] - a.area_offset[1] + a.table_size[1] - a.table_pos[1] + cy[i];
+      bool placed = false;
+      for (int trial = 0; trial <= 20 && !placed; trial++) {
+        float gx = hx[i] + U() * (width - 2.f * hx[i]), gy = hy[i] + U() * (height - 2.f * hy[i]);
+        const float dist = sqrtf((gx - x) * (gx - x) + (gy - y) * (gy - y));
+        const float min_ratio = dist >= a.goal_distance_min ? a.goal_distance_min / dist : 0.f;
+        const float ratio = fminf(fmaxf(ratio_in, min_ratio), 1.f);
+        gx = x + (gx - x) * ratio; gy = y + (gy - y) * ratio;
+        bool free_ = true;
+        for (int d = 0; d < i; d++) free_ = free_ && (fabsf(gx - px[d]) >= hx[i] + hx[d] || fabsf(gy - py[d]) >= hy[i] + hy[d]);
+        px[i] = gx; py[i] = gy;
+        placed = free_;
+      }
+      ok = placed;
+    }
+  }
+  for (int i = 0; i < N; i++) {
+    out[i][0] = px[i] - cx[i] + a.area_offset[0] - a.table_size[0] + a.table_pos[0];
+    out[i][1] = py[i] - cy[i] + a.area_offset[1] - a.table_size[1] + a.table_pos[1];
+    out[i][2] = a.obj_half[i][2] + 2.f * a.table_size[2] - a.table_size[2] + a.table_pos[2] - a.obj_center[i][2];
+  }
+  return ok;
+}
+
 __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbBatchDev bt, const RbModelDev* sp, RbBatchDev sb, RaRecipeArgs a) {
 #ifdef RG_EMUL
   RaRecipeLds& F = *(RaRecipeLds*)emul_lds();
@@ -358,6 +452,26 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
         if (!a.fixed_order)
           for (int i = N - 1; i > 0; i--) { int j = (int)(UG() * (float)(i + 1)); j = j > i ? i : j; const int tmp = order[i]; order[i] = order[j]; order[j] = tmp; }
         for (int i = 0; i < N; i++) { F.gpos[order[i]][0] = bot[0][0]; F.gpos[order[i]][1] = bot[0][1]; F.gpos[order[i]][2] = bot[0][2] + (float)i * 2.f * a.object_size; }
+      } else if (kind == 5) {                                          // TrainStateGoal (goals/train_state.py:81-113): goals near the objects, then one in the air or a tower
+        const float ratio = a.goal_distance_ratio ? a.goal_distance_ratio[e] : 1.f;
+        if (!ra_place_near(a, N, gy, gstride, bt.qpos + (size_t)e * nq, ratio, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
+        if (a.pickup_proba + a.stacking_proba > 0.f) {                 // move_one_object_to_the_air_with_restrictions (:13-78)
+          const float p = UG();
+          if (p > a.pickup_proba + a.stacking_proba) {
+          } else if (p < a.pickup_proba) {
+            const float h = a.height_range[0] + UG() * (a.height_range[1] - a.height_range[0]);
+            int i = (int)(UG() * (float)N); i = i > N - 1 ? N - 1 : i;
+            F.gpos[i][2] += h * ratio;
+          } else if (N >= 2) {                                         // a tower of 2..N objects: a random subset in random order, from this env's stream
+            int tower = 2 + (int)(UG() * (float)(N - 1)); tower = tower > N ? N : tower;
+            int order[RA_MAXOBJ];
+            for (int i = 0; i < N; i++) order[i] = i;
+            for (int t = 0; t < tower; t++) { int j = t + (int)(UG() * (float)(N - t)); j = j > N - 1 ? N - 1 : j; const int tmp = order[t]; order[t] = order[j]; order[j] = tmp; }
+            for (int h = 1; h < tower; h++) {
+              F.gpos[order[h]][0] = F.gpos[order[0]][0]; F.gpos[order[h]][1] = F.gpos[order[0]][1]; F.gpos[order[h]][2] += a.object_size * (float)h * 2.f;
+            }
+          }
+        }
       } else {                                                         // reach: the object goes to the placement, the goal target_height above it
         if (kind == 3) {
           if (!ra_place(a, 1, true, gy, gstride, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
@@ -375,6 +489,27 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
     // ---- an episode that ended on this step: its recipe begins (the returned observation / reward / done are the terminal ones)
     if (!started && st == 0 && a.done[e]) {
       ended = 1;
+      if (a.obj_group && a.group_mode == 1) {                          // _randomize_object_groups, the first act of RearrangeEnv._reset: sample_group_counts
+        // (common/utils.py:47-73) -- until the objects are used up: lam ~ U(sample_lam), a count c in 1..remaining with probability proportional to exp(-c lam)
+        // (the inverse of its cumulative sum at a second uniform); group g = the next c objects.  A stream of its own (seed ^ constant, as the goal's): disjoint from
+        // the placement's draws however often that restarts
+        k = 3000u;
+        const unsigned grseed = a.seed ^ 0x85EBCA6Bu;
+        auto UR = [&]() -> float { return (float)(rbp_hash(grseed, a.step, (unsigned)e, k++) >> 8) * (1.0f / 16777216.0f); };
+        int* grow = a.obj_group + (size_t)e * N;
+        for (int first = 0, g = 0; first < N; g++) {
+          const int rem = N - first;
+          const float lam = a.sample_lam[0] + UR() * (a.sample_lam[1] - a.sample_lam[0]);
+          const float q = expf(-lam);
+          float total = 0.f, w = 1.f;                                  // weights exp(-(c - 1) lam): the common factor exp(-lam) cancels
+          for (int c = 1; c <= rem; c++) { total += w; w *= q; }
+          const float target = UR() * total;
+          int c = 1; float cum = 1.f; w = q;
+          while (c < rem && !(target < cum)) { cum += w; w *= q; c++; }
+          for (int i = 0; i < c; i++) grow[first + i] = g;
+          first += c;
+        }
+      }
       k = 1000u;
       float* yw = a.yaw + (size_t)e * N;
       for (int i = 0; i < N; i++) yw[i] = 2.f * RBC_PI * U();
@@ -386,7 +521,7 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
     // controller ticks of the NEXT step's main-world launch: two for live envs, one inside the recipe, two on the recipe's last step
     // (reach: one on the recipe's last step -- the goal moves the object, the forward of _observe_sync follows it: the host's launch over the reobserve codes)
     const int last_stage = a.n_random_initial_steps >= 1 ? 3 : 1;
-    a.nticks[e] = st > 0 ? ((st == last_stage && lf <= 1 && a.goal_kind < 3) ? 2 : 1) : 2;
+    a.nticks[e] = st > 0 ? ((st == last_stage && lf <= 1 && !(a.goal_kind == 3 || a.goal_kind == 4)) ? 2 : 1) : 2;
     a.stage[e] = st; a.left[e] = lf;
     a.reobserve[e] = started ? 1 : (regoal ? 3 : 2);
     a.ended[e] = (unsigned char)ended; a.stabilised[e] = (unsigned char)stabilised;

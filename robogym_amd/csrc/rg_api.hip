@@ -1475,6 +1475,7 @@ int ra_env_post_step(rb_batch* b, rb_batch* solver, const ra_post_args* args, vo
   if (a.goal_kind >= 2 && (a.grip_site < 0 || a.grip_site >= d.nsite)) return fail("ra_env_post_step: grip site id out of range");
   if (a.goal_kind == 2 && !a.goal_dist_extra) return fail("ra_env_post_step: the stack goal needs goal_dist_extra");
   if (a.goal_kind >= 3 && a.num_objects != 1) return fail("ra_env_post_step: the reach goals take exactly one object");
+  if (a.obj_group && a.goal_kind >= 3) return fail("ra_env_post_step: obj_group with a reach goal (one object: nothing to match)");
   if (solver) {
     if (solver->dev.B != b->dev.B || solver->device != b->device) return fail("ra_env_post_step: the two batches must have the same size and device");
     const RbModelDev& ds = solver->model->dev;
@@ -1504,10 +1505,16 @@ int ra_env_recipe_step(rb_batch* b, rb_batch* solver, const ra_recipe_args* args
   for (int k = 0; k < 6; k++) if (a.arm_qposadr[k] < 0 || a.arm_qposadr[k] >= d.nq) return fail("ra_env_recipe_step: arm joint address out of range");
   if (!(a.area_size[0] > 0.f) || !(a.area_size[1] > 0.f)) return fail("ra_env_recipe_step: empty placement area");
   if (a.stabilize_steps < 0 || a.n_random_initial_steps < 0 || a.settle_steps < 0) return fail("ra_env_recipe_step: negative step count");
-  if (a.goal_kind < 0 || a.goal_kind > 4) return fail("ra_env_recipe_step: goal_kind out of range (0 object state, 1 pick-and-place, 2 stack, 3 reach, 4 deterministic reach)");
-  if (a.goal_kind == 1 && !(a.height_range[0] <= a.height_range[1])) return fail("ra_env_recipe_step: empty height_range");
-  if (a.goal_kind >= 3 && a.num_objects != 1) return fail("ra_env_recipe_step: the reach goals take exactly one object");
+  if (a.goal_kind < 0 || a.goal_kind > 5) return fail("ra_env_recipe_step: goal_kind out of range (0 object state, 1 pick-and-place, 2 stack, 3 reach, 4 deterministic reach, 5 train)");
+  if ((a.goal_kind == 1 || a.goal_kind == 5) && !(a.height_range[0] <= a.height_range[1])) return fail("ra_env_recipe_step: empty height_range");
+  if ((a.goal_kind == 3 || a.goal_kind == 4) && a.num_objects != 1) return fail("ra_env_recipe_step: the reach goals take exactly one object");
+  if (a.goal_kind == 5 && !(a.goal_distance_min >= 0.f && a.pickup_proba >= 0.f && a.stacking_proba >= 0.f && a.pickup_proba + a.stacking_proba <= 1.f))
+    return fail("ra_env_recipe_step: the train goal needs goal_distance_min >= 0 and 0 <= pickup_proba + stacking_proba <= 1");
   if (a.goal_kind == 4 && !a.goal_index) return fail("ra_env_recipe_step: the deterministic reach goal needs goal_index");
+  if (a.group_mode < 0 || a.group_mode > 1) return fail("ra_env_recipe_step: group_mode out of range (0 the rows stay, 1 sampled at every episode start)");
+  if (a.group_mode == 1 && !a.obj_group) return fail("ra_env_recipe_step: group_mode 1 needs obj_group");
+  if (a.obj_group && (a.goal_kind == 3 || a.goal_kind == 4)) return fail("ra_env_recipe_step: obj_group with a reach goal (one object: nothing to group)");
+  if (a.group_mode == 1 && !(a.sample_lam[0] >= 0.f && a.sample_lam[0] <= a.sample_lam[1])) return fail("ra_env_recipe_step: sample_lam is not a range of non-negative rates");
   RbBatchDev sb; memset(&sb, 0, sizeof sb);
   const RbModelDev* ms = nullptr;
   if (solver) {

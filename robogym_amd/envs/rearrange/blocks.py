@@ -27,7 +27,10 @@ and aligns the commanded orientation with the vertical (rb_tcp_args.wrist_only).
 `tcp_solver_mode = "mocap"` (MujocoIdealURGripperCompositeRobot, composite/ur_gripper_arm.py:126-128): the main world's arm on the mocap weld, no joint actuators, no solver
 world; the hook runs on the env's own world (rb_tcp_args.self_world) -- ONE physics launch per step.  Blocks, synchronous reset.
 
-Not built for this env: vision, `teleport_to_goal`, masks of the placement area, duplicated-object groups.
+Duplicated-object groups (`object_groups`; the reference's `_randomize_object_groups` + the greedy matching of `ObjectStateGoal.relative_goal`) are opt-in here: the
+default "distinct" keeps every object its own group, where the reference samples groups at every reset.
+
+Not built for this env: vision, `teleport_to_goal`, masks of the placement area, per-group materials / colours / scales.
 """
 import ctypes
 from typing import Optional
@@ -45,9 +48,11 @@ JOINT_DRIFT_THRESHOLD = float(np.deg2rad(1))
 FLAG_FULL_FORWARD = 32
 #: the goal generators of the rearrange block tasks (ra_post_args.goal_kind): ObjectStateGoal (goals/object_state.py), PickAndPlaceGoal (goals/pickandplace.py),
 #: ObjectStackGoal (goals/object_stack_goal.py), ObjectReachGoal / DeterministicReachGoal (goals/object_reach_goal.py)
-GOAL_KINDS = {"object_state": 0, "pickandplace": 1, "stack": 2, "reach": 3, "det-reach": 4}
+GOAL_KINDS = {"object_state": 0, "pickandplace": 1, "stack": 2, "reach": 3, "det-reach": 4, "train": 5}      # (train: TrainStateGoal, goals/train_state.py)
 #: DeterministicReachGoal's two object positions (goals/object_reach_goal.py:65-66)
 DET_REACH_POINTS = np.array([[1.50253879, 0.36960144, 0.5170952], [1.32253879, 0.53960144, 0.5170952]])
+#: lambda range of `sample_group_counts` (common/utils.py:47-49, the function's own defaults)
+SAMPLE_LAM = (1.0, 8.0)
 
 OBS_KEYS = [("obj_pos", "N3"), ("obj_rel_pos", "N3"), ("obj_vel_pos", "N3"), ("obj_rot", "N3"), ("obj_vel_rot", "N3"), ("robot_joint_pos", 6), ("gripper_pos", 3),
             ("gripper_velp", 3), ("gripper_controls", 1), ("gripper_qpos", 1), ("gripper_vel", 1), ("qpos", "nq"), ("qpos_goal", "nq"), ("goal_obj_pos", "N3"),
@@ -63,6 +68,133 @@ def euler2quat(e):
     return np.stack([cx * cy * cz - sx * sy * sz, sx * cy * cz + cx * sy * sz, cx * sy * cz - sx * cy * sz, cx * cy * sz + sx * sy * cz], axis=-1)
 
 
+def sample_group_counts(random_state, total: int, lam_low: float = SAMPLE_LAM[0], lam_high: float = SAMPLE_LAM[1]):
+    """`sample_group_counts` (common/utils.py:47-73), draw for draw: counts that sum to `total`; each round lam ~ U(lam_low, lam_high), then a count k in
+    1..remaining with probability proportional to exp(-k lam)."""
+    remaining, counts = int(total), []
+    while remaining > 0:
+        ks = np.arange(1, remaining + 1)
+        lam = random_state.uniform(lam_low, lam_high)
+        probs = np.exp(-ks * lam)
+        probs /= probs.sum()
+        k = int(random_state.choice(ks, p=probs))
+        counts.append(k)
+        remaining -= k
+    return counts
+
+
+def group_ids(counts):
+    """counts -> the group id of each object: groups are contiguous ranges of object ids (common/base.py:536-547)"""
+    return np.repeat(np.arange(len(counts)), counts).astype(np.int32)
+
+
+def greedy_group_match(obj_pos, goal_pos, groups):
+    """The goal each object is measured against (`ObjectStateGoal.relative_goal`, goals/object_state.py:520-554; host numpy, ra_group_match does the same on the
+    device; the env itself never evaluates goal distances on the host -- this is the reference restatement for tests and for bindings that want one): inside each
+    group of equal ids, n times the closest (object, goal) pair still free, ties to the lowest row-major index.  [N, 3], [N, 3], [N] -> [N]."""
+    obj_pos, goal_pos, groups = np.asarray(obj_pos), np.asarray(goal_pos), np.asarray(groups)
+    match = np.arange(len(groups))
+    for g in np.unique(groups):
+        ids = np.nonzero(groups == g)[0]
+        dist = np.linalg.norm(obj_pos[ids][:, None, :] - goal_pos[ids][None, :, :], axis=-1)
+        for _ in range(len(ids)):
+            i, j = np.unravel_index(np.argmin(dist), dist.shape)
+            match[ids[i]] = ids[j]
+            dist[i, :] = np.inf
+            dist[:, j] = np.inf
+    return match
+
+
+def place_targets_with_goal_distance_ratio(random_state, centre, half, table_pos, table_size, area_offset, area_size, object_pos, goal_distance_ratio, goal_distance_min,
+                                           max_trials=100, max_trials_per_object=20):
+    """`place_targets_with_goal_distance_ratio` over `_place_objects` (common/utils.py:922-994, 623-716), draw for draw, for axis-aligned boxes (`centre`, `half` [N, 3]:
+    each object's bounding box in its body frame, as yawed): per object a uniform proposal inside the area pulled toward the object's position, accepted when its box
+    overlaps no goal placed before it.  Returns ([N, 3] body origins in world coordinates, valid); on failure the last proposals (the reference returns zeros)."""
+    N = len(centre)
+    table_pos, table_size = np.asarray(table_pos, dtype=np.float64), np.asarray(table_size, dtype=np.float64)
+    shift = np.array([area_offset[0], area_offset[1], 0.0]) - table_size + table_pos
+    width, height = area_size[0], area_size[1]
+    last = np.zeros((N, 3))
+    for _ in range(max_trials):
+        placed, valid = [], True
+        for i in range(N):
+            z = half[i, 2] + 2 * table_size[2] - centre[i, 2]
+            trials = 0
+            while True:
+                gx, gy = random_state.uniform(low=(half[i, 0], half[i, 1]), high=(width - half[i, 0], height - half[i, 1]))
+                place = object_pos[i] - shift
+                x, y = place[0] + centre[i, 0], place[1] + centre[i, 1]
+                dist = np.linalg.norm([gx - x, gy - y])
+                ratio = np.clip(goal_distance_ratio, goal_distance_min / dist if dist >= goal_distance_min else 0.0, 1.0)
+                gx, gy = x + (gx - x) * ratio, y + (gy - y) * ratio
+                cand = np.array([gx - centre[i, 0], gy - centre[i, 1], z]) + shift
+                last[i] = cand
+                free = all(abs(cand[0] + centre[i, 0] - q[0] - centre[d, 0]) >= half[i, 0] + half[d, 0] or abs(cand[1] + centre[i, 1] - q[1] - centre[d, 1]) >= half[i, 1] + half[d, 1]
+                           for d, q in enumerate(placed))
+                if free:
+                    break
+                trials += 1
+                if trials > max_trials_per_object:
+                    valid = False
+                    break
+            if not valid:
+                break
+            placed.append(cand)
+        if valid:
+            return np.array(placed), True
+    return last, False
+
+
+def move_one_object_to_the_air_with_restrictions(random_state, placement, height_range, object_size, pickup_proba=0.0, stacking_proba=0.0, goal_distance_ratio=1.0):
+    """goals/train_state.py:13-78, draw for draw up to the tower's members: nothing without probabilities; else one uniform p -- above their sum nothing, below
+    `pickup_proba` one random object raised by U(height_range) * ratio, otherwise a tower of randint(2, N + 1) objects: the first of a random subset stays, the h-th other
+    one gets its x, y and + object_size * (h + 1) * 2.  (The reference takes the subset from the global `np.random`; here it is `random_state`'s.)"""
+    if pickup_proba + stacking_proba == 0:
+        return placement
+    p = random_state.random_sample()
+    n = placement.shape[0]
+    if p > pickup_proba + stacking_proba:
+        return placement
+    if p < pickup_proba:
+        h = random_state.uniform(low=height_range[0], high=height_range[1])
+        placement[random_state.randint(n), -1] += h * goal_distance_ratio
+        return placement
+    if n >= 2:
+        tower = random_state.randint(2, n + 1)
+        ids = random_state.permutation(n)[:tower]
+        for h, i in enumerate(ids[1:]):
+            placement[i, 0], placement[i, 1] = placement[ids[0], 0], placement[ids[0], 1]
+            placement[i, 2] += object_size * (h + 1) * 2
+    return placement
+
+
+def _parse_object_groups(object_groups, num_objects):
+    """`object_groups` -> (mode, counts): "distinct" (None), "single", "sample" (counts drawn per env and episode), or explicit counts -- a list of ints or of the
+    reference's `ObjectGroupConfig` fields as dicts, of which `count` alone is built."""
+    if object_groups is None or (isinstance(object_groups, str) and object_groups == "distinct"):
+        return "distinct", None
+    if isinstance(object_groups, str):
+        if object_groups == "single":
+            return "fixed", [int(num_objects)]
+        if object_groups == "sample":
+            return "sample", None
+        raise ValueError("object_groups %r is not \"distinct\", \"single\", \"sample\" or a list of counts" % (object_groups,))
+    counts = []
+    if len(object_groups) == 0:
+        raise NotImplementedError("parameters.simulation_params.object_groups: an empty list is not implemented by the batched rearrange env (\"distinct\", \"single\", \"sample\" or counts)")
+    for g in object_groups:
+        if isinstance(g, dict):
+            unset = lambda v: v is None or (isinstance(v, (dict, str, int, float)) and v in ({}, "default", 1, 1.0))      # (arrays, lists: a given value)
+            other = sorted(k for k, v in g.items() if k not in ("count", "object_ids") and not unset(v))
+            if other:
+                raise NotImplementedError("object_groups: per-group %s not implemented by the batched rearrange env (count only)" % ", ".join(other))
+            g = g.get("count", 1)
+        counts.append(int(g))
+    if min(counts, default=0) < 1 or sum(counts) != int(num_objects):
+        raise ValueError("object_groups counts %r do not sum to num_objects=%d" % (counts, num_objects))
+    return "fixed", counts
+
+
 class BatchedBlockRearrangeEnv:
     def __init__(self, batch_size: int, device="cuda:0", num_objects: int = 5, starting_seed: int = 0, max_position_change: float = 0.1,
                  arm_reset_controller_error: bool = True, n_random_initial_steps: int = 10, stabilize_steps: int = 100, settle_steps: int = 100,
@@ -71,7 +203,9 @@ class BatchedBlockRearrangeEnv:
                  main_model=None, wrappers: bool = False, n_action_bins: int = 11, smooth_alpha: float = 0.3, reward_clip: float = 100.0,
                  pipelined_reset: bool = False, action_spacing: str = "linear", per_env_parameters: bool = True, randomizer_params: Optional[dict] = None,
                  stabilize_object_damping: float = 1.0e-3, control_mode: str = "tcp+roll+yaw", device_reset: bool = False, tcp_solver_mode: str = "mocap_ik",
-                 goal_kind: str = "object_state", height_range=(0.05, 0.25), object_size: float = 0.0254, fixed_order: bool = False, target_height: float = 0.1):
+                 goal_kind: str = "object_state", height_range=(0.05, 0.25), object_size: float = 0.0254, fixed_order: bool = False, target_height: float = 0.1,
+                 object_groups="distinct", sample_lam=SAMPLE_LAM, goal_distance_ratio=1.0, goal_distance_min: float = 0.06, pickup_proba: float = 0.0,
+                 stacking_proba: float = 0.0):
         """`per_env_parameters`: every env carries its own copy of the randomisable model fields (`self.sim.params`, LargeModelSimulation(env_params=True)) -- what
         the reference's simulation randomizers and `stabilize_objects` write into `sim.model`.  On by default (measured cost: 0.7 % of the step,
         profiles/r05_ab_rb_env_params.txt); off: the model's own arrays, no randomizers, no damping change while the objects stabilise.
@@ -79,17 +213,31 @@ class BatchedBlockRearrangeEnv:
         env kernel (ra_env_recipe_step, include/rgstep.h) instead of host numpy behind a readback of the done / goal flags: a step call never waits for the GPU.
         `randomizer_params`: name -> parameter of `build_simulation_randomizers` (the reference's ADR-controlled values; all zero by default = identity).
         `goal_kind` (GOAL_KINDS): the task's goal generator -- "object_state" (this env's own), "pickandplace" (`height_range`), "stack" (`object_size`, `fixed_order`),
-        "reach" / "det-reach" (one object, `target_height`); envs/rearrange/blocks_pickandplace.py, blocks_stack.py, blocks_reach.py and ycb_pickandplace.py set it."""
+        "reach" / "det-reach" (one object, `target_height`); envs/rearrange/blocks_pickandplace.py, blocks_stack.py, blocks_reach.py and ycb_pickandplace.py set it.
+        `object_groups`: groups of interchangeable duplicates, matched to goals greedily by distance inside the env kernel (`self.obj_group` [B, N], ra_post_args.obj_group):
+        "distinct" (default: no row, every object its own goal), "single" (one group; envs/rearrange/blocks_duplicate.py), "sample" (`sample_group_counts` with
+        `sample_lam` per env at every episode start, host recipe and device recipe alike) or explicit counts that sum to `num_objects`.
+        goal_kind "train" (envs/rearrange/blocks_train.py): `goal_distance_ratio` (a scalar or [B]: `self.goal_distance_ratio`, a device row a curriculum may write per
+        env), `goal_distance_min`, `pickup_proba`, `stacking_proba`, with `height_range` and `object_size`."""
         self.B, self.N = int(batch_size), int(num_objects)
         if goal_kind not in GOAL_KINDS:
             raise ValueError("goal_kind %r is not one of %s" % (goal_kind, ", ".join(GOAL_KINDS)))
         self.goal_kind_name, self.goal_kind = goal_kind, GOAL_KINDS[goal_kind]
-        self.reach = self.goal_kind >= 3
+        self.reach = self.goal_kind in (3, 4)
+        self.goal_distance_min, self.pickup_proba, self.stacking_proba = float(goal_distance_min), float(pickup_proba), float(stacking_proba)
+        if not (self.goal_distance_min >= 0 and self.pickup_proba >= 0 and self.stacking_proba >= 0 and self.pickup_proba + self.stacking_proba <= 1.0):
+            raise ValueError("goal_distance_min >= 0 and 0 <= pickup_proba + stacking_proba <= 1 (got %r, %r, %r)" % (goal_distance_min, pickup_proba, stacking_proba))
         if self.reach and self.N != 1:
             raise ValueError("the reach goals take exactly one object (ObjectReachGoal: \"reach only supports one objects\"), got num_objects=%d" % self.N)
         self.height_range, self.object_size, self.fixed_order, self.target_height = (float(height_range[0]), float(height_range[1])), float(object_size), bool(fixed_order), float(target_height)
         if not self.height_range[0] <= self.height_range[1]:
             raise ValueError("height_range %r is empty" % (height_range,))
+        self.group_mode, self.group_counts = _parse_object_groups(object_groups, self.N)
+        self.sample_lam = (float(sample_lam[0]), float(sample_lam[1]))
+        if self.group_mode != "distinct" and self.reach:
+            raise ValueError("object_groups with a reach goal: one object, nothing to match")
+        if not 0.0 <= self.sample_lam[0] <= self.sample_lam[1]:
+            raise ValueError("sample_lam %r is not a range of non-negative rates" % (sample_lam,))
         self._L = lib if lib is not None else _native.lib()
         self.control_mode = _control_mode_name(control_mode)
         self.joint_control = self.control_mode == "joint"      # ControlMode.JOINT: no TCP solver world (RobotControlParameters.requires_solver_sim, robot_interface.py:83-91)
@@ -121,6 +269,7 @@ class BatchedBlockRearrangeEnv:
         self.n_random_initial_steps, self.stabilize_steps, self.settle_steps = n_random_initial_steps, stabilize_steps, settle_steps
         self.used_table_portion = used_table_portion
         self._rng = np.random.RandomState(starting_seed)
+        self.host_placement_failed = 0      # host recipe: goal placements that ran out of restarts (the device recipe counts per env in `placement_failed`)
         A, As = main.arrays, (None if solver is None else solver.arrays)
         jn, sj = main.names["joint"], (None if solver is None else solver.names["joint"])
         self.arm_q = [int(A["jnt_qposadr"][jn.index("robot0:J%d" % k)]) for k in range(1, 7)]
@@ -177,6 +326,7 @@ class BatchedBlockRearrangeEnv:
         self.goal, self.goal_rot, self.qpos_goal, self.static_obs = z(B, N, 7), z(B, N, 3), z(B, self.nq), z(B, N, 7)
         self.reward, self.goal_dist, self.goal_dist_extra = z(B, 3), z(B, 2), z(B, 2)
         self.goal_index = z(B, dt=torch.int32)                  # DeterministicReachGoal.idx, per env
+        self.goal_distance_ratio = torch.as_tensor(np.broadcast_to(np.asarray(goal_distance_ratio, dtype=np.float32), (B,)).copy(), device=dev)      # per env (train)
         self.done, self.goal_reset, self.trial_success, self.sub_goal_ok, self.env_crash, self.objects_off_table = (z(B, dt=torch.bool) for _ in range(6))
         self.info_ssl = z(B, dt=torch.int32)
         self.goal[:, :, 3] = 1.0
@@ -218,8 +368,13 @@ class BatchedBlockRearrangeEnv:
         a.safety_stop_force = 150.0                                      # robot/ur16e/arm_interface.py:46
         a.max_timesteps_per_goal, a.successes_needed, a.use_goal_distance_reward = max_timesteps_per_goal_per_obj * N, successes_needed, int(use_goal_distance_reward)
         a.solver_grip_qposadr, a.solver_grip_act = self.solver_grip_q, self.solver_grip_act
-        a.goal_kind, a.grip_site, a.goal_dist_extra = self.goal_kind, main.names["site"].index("robot0:grip"), P(self.goal_dist_extra)
+        a.goal_kind, a.grip_site, a.goal_dist_extra = (0 if self.goal_kind == 5 else self.goal_kind), main.names["site"].index("robot0:grip"), P(self.goal_dist_extra)
         self._grip_site = int(a.grip_site)
+        self.obj_group = None
+        if self.group_mode != "distinct":      # ("sample": all distinct until the first reset draws the rows)
+            ids = group_ids(self.group_counts if self.group_mode == "fixed" else [1] * N)
+            self.obj_group = torch.tensor(np.tile(ids, (B, 1)), dtype=torch.int32, device=dev).contiguous()
+            a.obj_group = P(self.obj_group)
         self.action_shape = (self.B, self.action_dim)
         self._zero_action = z(B, AD)
         # ---- per-env model parameters: the reference's simulation randomizers (applied after _reset, robot_env.py:779-783) and stabilize_objects' damping change
@@ -293,6 +448,10 @@ class BatchedBlockRearrangeEnv:
             for j in range(2):
                 for k in range(3):
                     r.det_points[j][k] = float(DET_REACH_POINTS[j, k])
+            r.goal_distance_ratio, r.goal_distance_min, r.pickup_proba, r.stacking_proba = P(self.goal_distance_ratio), self.goal_distance_min, self.pickup_proba, self.stacking_proba
+            if self.obj_group is not None:
+                r.obj_group, r.group_mode = P(self.obj_group), int(self.group_mode == "sample")
+                r.sample_lam[0], r.sample_lam[1] = self.sample_lam
 
     # ------------------------------------------------------------------ launches
     def _stream(self):
@@ -495,6 +654,22 @@ class BatchedBlockRearrangeEnv:
         """`_sample_next_goal_positions` of the env's goal generator for the envs `rows` (host numpy; ra_recipe_kernel does the same on the device): [len(rows), N, 3].
         Reach also moves the object itself (`set_object_pos`: position only) -- the caller's forward makes the observation see it."""
         R, N, kind = len(rows), self.N, self.goal_kind
+        if kind == 5:          # TrainStateGoal: goals near the objects' current positions, then one in the air or a tower (goals/train_state.py:81-113)
+            idx = torch.as_tensor(rows, device=self.device, dtype=torch.long)
+            qpos = self.sim.qpos[idx].cpu().numpy().astype(np.float64)
+            ratios = self.goal_distance_ratio[idx].cpu().numpy().astype(np.float64)
+            half = self._aabb_half(yaw)
+            c, s_ = np.cos(yaw), np.sin(yaw)
+            centre = np.stack([c * self.obj_center[:, 0] - s_ * self.obj_center[:, 1], s_ * self.obj_center[:, 0] + c * self.obj_center[:, 1], np.broadcast_to(self.obj_center[:, 2], yaw.shape)], -1)
+            offset, size = self.placement_area()
+            pos = np.zeros((R, N, 3))
+            for r in range(R):
+                op = np.array([qpos[r, qa:qa + 3] for qa in self.obj_q])
+                pos[r], ok = place_targets_with_goal_distance_ratio(self._rng, centre[r], half[r], self.table_pos, self.table_size, offset, size, op, ratios[r], self.goal_distance_min)
+                if not ok:
+                    self.host_placement_failed += 1
+                move_one_object_to_the_air_with_restrictions(self._rng, pos[r], self.height_range, self.object_size, self.pickup_proba, self.stacking_proba, ratios[r])
+            return pos
         if kind <= 1:
             pos = self._grid_placement(yaw, rows)
             if kind == 1:      # move_one_object_to_the_air (goals/pickandplace.py:30-52): a height, then the object it raises
@@ -560,6 +735,9 @@ class BatchedBlockRearrangeEnv:
         rotations about z and their placement, bounding boxes / colours of the static observation.  Returns the drawn yaw angles [len(rows), N]."""
         dev, N = self.device, self.N
         A = self.model.arrays
+        if self.group_mode == "sample":      # _randomize_object_groups: the first act of RearrangeEnv._reset (common/base.py:903)
+            rows_ids = np.stack([group_ids(sample_group_counts(self._rng, N, *self.sample_lam)) for _ in rows])
+            self.obj_group[idx] = torch.tensor(rows_ids, dtype=torch.int32, device=dev)
         worlds = [(self.sim, A)] + ([] if self.solver_sim is None else [(self.solver_sim, self.solver_model.arrays)])
         if self.per_env_parameters:      # _recreate_sim (common/base.py:850-856): a fresh model -- the previous episode's randomised values are gone
             for k, v in self._param_defaults.items():
@@ -860,10 +1038,10 @@ def action_bin_array(lower_bound, upper_bound, n_bins, spacing="linear"):
 
 
 SUPPORTED_PARAMETERS = {"simulation_params", "robot_control_params", "n_random_initial_steps"}
-SUPPORTED_SIMULATION_PARAMS = {"num_objects", "penalty", "used_table_portion"}
+SUPPORTED_SIMULATION_PARAMS = {"num_objects", "penalty", "used_table_portion", "object_groups", "goal_distance_ratio", "goal_distance_min"}
 SUPPORTED_ROBOT_CONTROL_PARAMS = {"max_position_change", "arm_reset_controller_error", "control_mode", "tcp_solver_mode"}
 SUPPORTED_CONSTANTS = {"success_threshold", "successes_needed", "success_reward", "max_timesteps_per_goal_per_obj", "n_action_bins", "action_spacing", "use_goal_distance_reward",
-                       "goal_reward_per_object", "normalize_mesh", "randomize"}
+                       "goal_reward_per_object", "normalize_mesh", "randomize", "sample_lam_low", "sample_lam_high"}
 
 
 def _control_mode_name(mode) -> str:
@@ -898,6 +1076,16 @@ def _check_supported(parameters, sp, rc, constants):
     _solver_mode_name(rc.get("tcp_solver_mode", "mocap_ik"))
 
 
+def group_args(sp, constants):
+    """The constructor's group keywords from `simulation_params.object_groups` ("distinct" / "single" / "sample" / counts) and `constants.sample_lam_low / _high`."""
+    out = {}
+    if "object_groups" in sp:
+        out["object_groups"] = sp["object_groups"]
+    if "sample_lam_low" in constants or "sample_lam_high" in constants:
+        out["sample_lam"] = (constants.get("sample_lam_low", SAMPLE_LAM[0]), constants.get("sample_lam_high", SAMPLE_LAM[1]))
+    return out
+
+
 def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants=None, starting_seed: int = 0, apply_wrappers: bool = True, **kw):
     """`BlockRearrangeEnv.build` surface (robot_env.py:1081-1089) for the batched env; `apply_wrappers` (default True, as in the reference) = the rearrange
     wrapper stack of common/base.py:986-996 (MultiDiscrete actions of `constants.n_action_bins` = 11 bins, action smoothing, reward clipping).  `parameters` / `constants` accept the subset this env
@@ -914,6 +1102,10 @@ def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants
         if k in constants:
             args[k] = constants[k]
     for k in ("penalty", "used_table_portion"):      # (a given penalty dict replaces the default one as a whole, as the reference's attrs field does)
+        if k in sp:
+            args[k] = sp[k]
+    args.update(group_args(sp, constants))
+    for k in ("goal_distance_ratio", "goal_distance_min"):
         if k in sp:
             args[k] = sp[k]
     if constants.get("randomize", True) is False:    # RobotEnvConstants.randomize (robot_env.py:155): no simulation randomizers at all

@@ -274,7 +274,7 @@ class GroupedYcbRearrangeEnv:
 
 def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants=None, starting_seed: int = 0, apply_wrappers: bool = True, **kw):
     """`YcbRearrangeEnv.build` surface (ycb.py:96) for the batched env; accepts what envs/rearrange/blocks.py `make_env` accepts."""
-    from robogym_amd.envs.rearrange.blocks import _check_supported
+    from robogym_amd.envs.rearrange.blocks import _check_supported, group_args
 
     parameters, constants = dict(parameters or {}), dict(constants or {})
     sp, rc = dict(parameters.get("simulation_params", {})), dict(parameters.get("robot_control_params", {}))
@@ -292,6 +292,7 @@ def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants
     for k in ("penalty", "used_table_portion"):
         if k in sp:
             args[k] = sp[k]
+    args.update(group_args(sp, constants))
     args.update(kw)
     object_sets = args.pop("object_sets", None)      # e.g. (0, 1, 2, 3): different object sets across the batch (GroupedYcbRearrangeEnv)
     if object_sets is not None and len(object_sets) > 1:
