@@ -31,12 +31,10 @@ using namespace rgl;   // small math, wave collectives and the MPR / support rou
 typedef const RbModelDev& RbM;
 typedef const RbLaunch& RbLRef;
 #define RB_S() (*(RbLds*)emul_lds())
-#define RB_ARENA() ((float*)((char*)emul_lds() + RB_ARENA_BASE))
 #else
 typedef const RG_AS4 RbModelDev& RbM;
 typedef const RG_AS4 RbLaunch& RbLRef;
 #define RB_S() (*(RbLds*)rg_lds_raw)
-#define RB_ARENA() ((float*)(rg_lds_raw + RB_ARENA_BASE))   /* as a generic pointer: the stage functions reach their arrays through flat loads either way */
 #endif
 #define TID ((int)threadIdx.x)
 #define WID (TID >> 6)
@@ -49,7 +47,7 @@ typedef const RG_AS4 RbLaunch& RbLRef;
 #ifndef RB_WG_PER_CU
 #define RB_WG_PER_CU 4   /* resident workgroups per CU the kernel is compiled for (register budget 512 / RB_WG_PER_CU per lane) */
 #endif
-#define RB_CST (7 * RB_CONW + RB_NW + 2)   /* words of a staged contact; <= RB_T */
+#define RB_CST (7 * RB_CONW + RB_NW + 2)   /* half the words of RbLds::cst */
 #ifndef RB_COST_EPS
 #define RB_COST_EPS 1e-7f   /* relative rounding noise of the fp32 cost sum: improvements below it are not resolvable */
 #endif
@@ -59,7 +57,7 @@ struct RbLds {
   float Dinv[RB_MAXGROUP * 8];   // inverses of the 8 x 8 diagonal blocks of the factor
   float prow[8];
   float yb[2 * 8];   // rb_chol_solve: the current block's solution, double-buffered
-  float cst[2 * RB_CST];   // rb_hessian_add: the contact being added and the next one (basis Jacobians, block rows, weights, nnz, dim)
+  float cst[2 * RB_CST];   // work area of the constraint stages: rb_hessian_add keeps the column offsets and dim | mode of a chunk of contacts here
   float sc[RB_MAXGROUP];
   float qpos[RB_MAXNQ], qvel[RB_MAXNV], warm[RB_MAXNV], ctrl[RB_MAXNU], pid[3 * RB_MAXNU], actlen[RB_MAXNU], actfrc[RB_MAXNU];
   // the force terms of the smooth dynamics are dead once qfrc_smooth is formed (sb_smooth; their stage dump sits right behind it), the solver's work vectors
@@ -121,18 +119,10 @@ __device__ __forceinline__ int rb_slot(RbLds& s, bool pred, int* cnt, int cap, u
   BSYNC();
   return (pred && slot < cap) ? slot : -1;
 }
-// a stage array of this env.  Default build: in the HBM scratch row.  With -DRB_LDS_ARENA (an experiment of round 5, kept as a build option: tools/gpu_call_r05b.sh,
-// DESIGN.md section 3.4c): in the workgroup's LDS arena if the model's placement (RB_LDS_PLACE) puts it there -- one scalar select per use of the pointer; the stage
-// functions reach their arrays through generic pointers (flat loads) either way, so nothing else changes.  Measured: per-workgroup latency falls by 1.7x, occupancy
-// by 2.3x (LDS), throughput by 17-27 %: what binds these kernels at 4 waves per SIMD is not the scratch row's latency alone.
 // a randomisable model field of this env: from the env's parameter block when the model carries per-env rows (rb_types.h RB_P_*), else the model's own array
 #define PRM(field, K) (m.prm_on ? (const float*)(S + m.prm_off[K]) : m.field)
-#define RB_ARENA_BASE ((sizeof(RbLds) + 15) & ~(size_t)15)
-#ifdef RB_LDS_ARENA
-#define SC(name) (m.lds_off[RB_O_##name] >= 0 ? RB_ARENA() + m.lds_off[RB_O_##name] : S + m.off[RB_O_##name])
-#else
+// a stage array of this env, in its HBM scratch row.  (Keeping stage arrays in LDS instead was measured twice and lost: DESIGN.md section 3.4c.)
 #define SC(name) (S + m.off[RB_O_##name])
-#endif
 
 // ------------------------------------------------------------------------------------------------- position stage
 // engine_core_smooth.c mj_kinematics: body frames top-down (level sweep), joint anchors / axes, geoms, sites
@@ -452,9 +442,6 @@ __device__ __forceinline__ bool rb_chol(RbLds& s, int n) {
   bool ok = true;
   for (int kb = 0; kb < n; kb += RB_NB) {
     const int nb = n - kb < RB_NB ? n - kb : RB_NB;
-#ifdef RB_CHOL_PROBE
-    const long long tprobe = rg_clock();
-#endif
     // (a1) the diagonal block, by wave 0 alone: lane r < 8 holds row r in registers, pivots and multipliers travel by v_readlane
     // (no LDS round trip, no barrier inside); lane c then builds column c of inv(L) the same way
     if (WID == 0) {
@@ -508,9 +495,6 @@ __device__ __forceinline__ bool rb_chol(RbLds& s, int n) {
       }
     }
     BSYNC();
-#ifdef RB_CHOL_PROBE
-    if (TID == 0) s.prof[15] += (float)(rg_clock() - tprobe);
-#endif
     // (b) trailing update: A[i][j] -= sum_c L[i][kb + c] L[j][kb + c], i, j >= kb + RB_NB
     const int t0 = kb + RB_NB;
     if (t0 < n) {
@@ -1656,7 +1640,6 @@ __device__ __forceinline__ void rb_make_constraint(RbM m, RbLds& s, float* S, co
         const q4 q1 = ldq(SC(XQUAT) + 4 * o1), q2 = ldq(SC(XQUAT) + 4 * o2);
         q4 qc; qc.w = q2.w; qc.x = -q2.x; qc.y = -q2.y; qc.z = -q2.z;
         const q4 qr = qmul(q1, ldq(L_eq_data + 7 * e + 3));
-#ifndef RB_ROWS_LEGACY
         if (RB_NWAVE == 1) {
           // (as for the contacts below: the dof list in LDS first, then every column formed in registers -- side 0 = body 1, then body 2 -- and stored once)
           int* li = (int*)s.A + RB_CONW * TID;
@@ -1690,7 +1673,6 @@ __device__ __forceinline__ void rb_make_constraint(RbM m, RbLds& s, float* S, co
             for (int r = 0; r < 6; r++) J[r * RB_CONW + q] = col[r];
           }
         } else
-#endif
         for (int side = 0; side < 2; side++) {
           const int bb = side ? o2 : o1; const float sg = side ? -1.f : 1.f;   // body1 - body2 ("opposite of contact")
           if (bb <= 0 || m.body_weldid[bb] == 0) continue;
@@ -1729,7 +1711,6 @@ __device__ __forceinline__ void rb_make_constraint(RbM m, RbLds& s, float* S, co
     int nnz = 0;
     float bd[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     bool bd_done = false;
-#ifndef RB_ROWS_LEGACY
     if (RB_NWAVE == 1) {
       // One wave per env (round 5): the dof list is built in LDS first (the block's storage is free until the smooth stage: RB_CONW words per lane, dof | sides << 16),
       // then every column of the six basis rows is formed in registers and stored ONCE -- instead of searching the list in the scratch row and six
@@ -1760,7 +1741,6 @@ __device__ __forceinline__ void rb_make_constraint(RbM m, RbLds& s, float* S, co
       }
       bd_done = true;
     } else
-#endif
     for (int side = 0; side < 2; side++) {
       const int bb = side ? b1 : b2; const float sg = side ? -1.f : 1.f;   // difference body2 - body1
       const v3 off = pos - ld3(rootcom + 3 * m.body_rootid[bb]);
@@ -2090,9 +2070,6 @@ __device__ __forceinline__ void rb_row_diag(RbM m, RbLds& s, float* S, int g, fl
 }
 
 // s.A (holding the group's block of M) += J' diag(D, quadratic rows) J restricted to group g
-#ifndef RB_HESS_MULTIWAVE_OFF
-#define RB_HESS_MULTIWAVE_OFF 0      /* 1: configurations with several waves keep the staged one-contact-per-barrier assembly (A/B switch) */
-#endif
 // (-DRB_HESS_PROBE=k: cycles of section k of the assembly -- 1 static rows, 2 contact weights, 3 the contacts' entries -- accumulate in prof[15]; a profiling build)
 #ifdef RB_HESS_PROBE
 #define RB_HPROBE_BEGIN(k) long long tprobe##k = 0; if (RB_HESS_PROBE == k) { BSYNC(); tprobe##k = rg_clock(); }
@@ -2133,7 +2110,7 @@ __device__ __forceinline__ void rb_hessian_add(RbM m, RbLds& s, float* S, int g)
     BSYNC();
   }
   // contacts: A += Jc' W Jc with the 6 x 6 weight W of the contact's quadratic pyramid edges (w_row = e0 +- mu_k e_(k+1)):
-  // the weights of all contacts first (one contact per thread), then the contacts one at a time, one (a, b) entry per thread
+  // the weights of all contacts first (one contact per thread), then the contacts' entries, a lane per (contact, column)
   RB_HPROBE_END(1)
   RB_HPROBE_BEGIN(2)
   float* Wc = SC(CONF);   // RB_NW words per contact.  Pyramidal: W00, W0k[5], Wkk[5] (mode 1).  Elliptic / equality: the lower triangle of the 6 x 6 weight
@@ -2192,160 +2169,86 @@ __device__ __forceinline__ void rb_hessian_add(RbM m, RbLds& s, float* S, int g)
   if (TID == 0) s.wcnt[0] = 0;
   RB_HPROBE_END(2)
   if (!any) return;
-  // One contact at a time (two contacts may share entries; the order of the sums is fixed), but its data -- six basis Jacobian rows,
-  // the dofs' rows in the block, the weights -- is staged through LDS by one load per thread while the previous contact is being
-  // added: a thread adding an entry then reads LDS only.  (Reading them from the scratch row cost ~30 global loads per thread and
-  // contact: 40 % of the kernel's vector memory instructions.)
-  // (one word per thread at 256 threads, three at 64; the load is issued before the current contact is added, the LDS store after it, so that the
-  //  load's latency is covered by the adding instead of being waited for in front of it)
   const float* cloc = SC(CONLOC);
-#ifndef RB_HESS_SERIAL
-  if (RB_NWAVE == 1 || !(RB_HESS_MULTIWAVE_OFF)) {
-    RB_HPROBE_BEGIN(3)
-    // One wave per env (round 5): a lane per (contact, Jacobian column).  The columns of up to 64 contacts are numbered through a prefix sum of nnz; a round takes as
-    // many whole contacts as fit 64 lanes.  A lane fetches ITS column of the six basis rows, its block row and the contact's weight once (one round of independent
-    // loads), then walks the contact's columns k = 0 .. nnz - 1: the partner column comes by lane exchange from the lane that holds it, and the pair (e, k <= e) is
-    // added into the block with an LDS atomic.  A single wave issues its LDS atomics in program order and resolves same-address lanes in lane order, so the sums
-    // are run-to-run identical (rg_kernel.h relies on the same property).  Against the staged loop below: no barrier and no staging round trip per contact, no idle
-    // lanes; against one entry per lane: a sixth of the loads.
-    // Several waves (the large configuration): EVERY wave walks all columns, and a lane adds its entry only if the entry's block row belongs to its wave
-    // (row mod RB_NWAVE): waves never touch the same address, each wave's own atomics are ordered as above -- still run-to-run identical, four waves' worth of
-    // lanes on the pairs, at the price of every wave loading every column.
-    int* offs = (int*)s.cst;           // 65 words: column offsets of this chunk's contacts
-    int* cmeta = (int*)s.cst + 65;     // 64 words: dim | mode << 8 of this chunk's contacts
-    for (int c0 = 0; c0 < s.ncon; c0 += 64) {
-      const int c = c0 + WL;
-      int cnt = 0, meta = 0;
-      if (c < s.ncon) { const int mode = (int)Wc[RB_NW * c + RB_NW - 1]; if (mode != 0) { cnt = (int)con[RB_CONREC * c + RB_CR_NNZ]; meta = (int)con[RB_CONREC * c + RB_CR_DIM] | (mode << 8); } }
-      int incl = cnt;
-      for (int o = 1; o < 64; o <<= 1) { const int t = __shfl(incl, WL >= o ? WL - o : WL); if (WL >= o) incl += t; }
-      BSYNC();
-      if (WID == 0) { offs[WL + 1] = incl; cmeta[WL] = meta; }      // (every wave computed the same numbers: one writes)
-      if (TID == 0) offs[0] = 0;
-      BSYNC();
-      int cs = 0;                       // first contact (chunk-local) of the round
-      while (cs < 64 && offs[cs] < offs[64]) {
-        // the round's contacts: cs .. ce - 1, the longest run whose columns fit the wave (a single contact has at most RB_CONW <= 64 columns)
-        const unsigned long long fit = __ballot(WL >= cs && offs[WL + 1] - offs[cs] <= 64);
-        const int ce = cs + __popcll(fit);
-        const int t = offs[cs] + WL;
-        const bool on = t < offs[ce];
-        int lo = cs, hi = ce;
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (offs[mid] <= t) lo = mid; else hi = mid; }
-        const int cl = on ? lo : cs, cc = c0 + cl, e = on ? t - offs[cl] : 0;
-        const int base = offs[cl] - offs[cs], nnz = offs[cl + 1] - offs[cl], dim = cmeta[cl] & 255, mode = cmeta[cl] >> 8;
-        const float* K = cj + 6 * RB_CONW * cc; const float* W = Wc + RB_NW * cc;
-        float ja[6], w[21];
+  RB_HPROBE_BEGIN(3)
+  // One wave per env (round 5): a lane per (contact, Jacobian column).  The columns of up to 64 contacts are numbered through a prefix sum of nnz; a round takes as
+  // many whole contacts as fit 64 lanes.  A lane fetches ITS column of the six basis rows, its block row and the contact's weight once (one round of independent
+  // loads), then walks the contact's columns k = 0 .. nnz - 1: the partner column comes by lane exchange from the lane that holds it, and the pair (e, k <= e) is
+  // added into the block with an LDS atomic.  A single wave issues its LDS atomics in program order and resolves same-address lanes in lane order, so the sums
+  // are run-to-run identical (rg_kernel.h relies on the same property).  Against staging one contact per barrier through LDS: no barrier and no staging round trip per contact, no idle
+  // lanes; against one entry per lane: a sixth of the loads.
+  // Several waves (the large configuration): EVERY wave walks all columns, and a lane adds its entry only if the entry's block row belongs to its wave
+  // (row mod RB_NWAVE): waves never touch the same address, each wave's own atomics are ordered as above -- still run-to-run identical, four waves' worth of
+  // lanes on the pairs, at the price of every wave loading every column.
+  int* offs = (int*)s.cst;           // 65 words: column offsets of this chunk's contacts
+  int* cmeta = (int*)s.cst + 65;     // 64 words: dim | mode << 8 of this chunk's contacts
+  for (int c0 = 0; c0 < s.ncon; c0 += 64) {
+    const int c = c0 + WL;
+    int cnt = 0, meta = 0;
+    if (c < s.ncon) { const int mode = (int)Wc[RB_NW * c + RB_NW - 1]; if (mode != 0) { cnt = (int)con[RB_CONREC * c + RB_CR_NNZ]; meta = (int)con[RB_CONREC * c + RB_CR_DIM] | (mode << 8); } }
+    int incl = cnt;
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl(incl, WL >= o ? WL - o : WL); if (WL >= o) incl += t; }
+    BSYNC();
+    if (WID == 0) { offs[WL + 1] = incl; cmeta[WL] = meta; }      // (every wave computed the same numbers: one writes)
+    if (TID == 0) offs[0] = 0;
+    BSYNC();
+    int cs = 0;                       // first contact (chunk-local) of the round
+    while (cs < 64 && offs[cs] < offs[64]) {
+      // the round's contacts: cs .. ce - 1, the longest run whose columns fit the wave (a single contact has at most RB_CONW <= 64 columns)
+      const unsigned long long fit = __ballot(WL >= cs && offs[WL + 1] - offs[cs] <= 64);
+      const int ce = cs + __popcll(fit);
+      const int t = offs[cs] + WL;
+      const bool on = t < offs[ce];
+      int lo = cs, hi = ce;
+      while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (offs[mid] <= t) lo = mid; else hi = mid; }
+      const int cl = on ? lo : cs, cc = c0 + cl, e = on ? t - offs[cl] : 0;
+      const int base = offs[cl] - offs[cs], nnz = offs[cl + 1] - offs[cl], dim = cmeta[cl] & 255, mode = cmeta[cl] >> 8;
+      const float* K = cj + 6 * RB_CONW * cc; const float* W = Wc + RB_NW * cc;
+      float ja[6], w[21];
 #pragma unroll
-        for (int q = 0; q < 6; q++) ja[q] = (on && q < dim) ? K[q * RB_CONW + e] : 0.f;
-        const int la = on ? (int)cloc[RB_CONW * cc + e] : 0;
-        // the weight: pyramid (mode 1) W00, W0k[5], Wkk[5]; diagonal (mode 3) the six diagonal entries; general (mode 2) the lower triangle of the 6 x 6
+      for (int q = 0; q < 6; q++) ja[q] = (on && q < dim) ? K[q * RB_CONW + e] : 0.f;
+      const int la = on ? (int)cloc[RB_CONW * cc + e] : 0;
+      // the weight: pyramid (mode 1) W00, W0k[5], Wkk[5]; diagonal (mode 3) the six diagonal entries; general (mode 2) the lower triangle of the 6 x 6
 #pragma unroll
-        for (int q = 0; q < 21; q++) w[q] = 0.f;
-        if (on && mode == 1) { for (int q = 0; q < 11; q++) w[q] = W[q]; }
-        else if (on && mode == 3) { for (int q = 0; q < 6; q++) if (q < dim) w[q] = W[q * (q + 1) / 2 + q]; }
-        else if (on) { for (int q = 0; q < 21; q++) w[q] = W[q]; }
-        int kmax = on ? nnz : 0;
-        for (int o = 32; o > 0; o >>= 1) { const int other = __shfl_xor(kmax, o); kmax = other > kmax ? other : kmax; }
-        for (int k = 0; k < kmax; k++) {
-          const int src = (base + (k < nnz ? k : 0)) & 63;
-          float jb[6];
+      for (int q = 0; q < 21; q++) w[q] = 0.f;
+      if (on && mode == 1) { for (int q = 0; q < 11; q++) w[q] = W[q]; }
+      else if (on && mode == 3) { for (int q = 0; q < 6; q++) if (q < dim) w[q] = W[q * (q + 1) / 2 + q]; }
+      else if (on) { for (int q = 0; q < 21; q++) w[q] = W[q]; }
+      int kmax = on ? nnz : 0;
+      for (int o = 32; o > 0; o >>= 1) { const int other = __shfl_xor(kmax, o); kmax = other > kmax ? other : kmax; }
+      for (int k = 0; k < kmax; k++) {
+        const int src = (base + (k < nnz ? k : 0)) & 63;
+        float jb[6];
 #pragma unroll
-          for (int q = 0; q < 6; q++) jb[q] = __shfl(ja[q], src);
-          const int lb = __shfl(la, src);
-          if (!(on && k <= e)) continue;
-          float v;
-          if (mode == 1) {
-            v = w[0] * ja[0] * jb[0];
-#pragma unroll
-            for (int q = 0; q < 5; q++) if (q < dim - 1) v += w[1 + q] * (ja[0] * jb[q + 1] + ja[q + 1] * jb[0]) + w[6 + q] * ja[q + 1] * jb[q + 1];
-          } else if (mode == 3) {
-            v = 0.f;
-#pragma unroll
-            for (int q = 0; q < 6; q++) if (q < dim) v += w[q] * ja[q] * jb[q];
-          } else {
-            v = 0.f;
-#pragma unroll
-            for (int q = 0; q < 6; q++) if (q < dim) {
-              v += w[q * (q + 1) / 2 + q] * ja[q] * jb[q];
-#pragma unroll
-              for (int r = 0; r < 5; r++) if (r < q) { const float wk = w[q * (q + 1) / 2 + r]; if (wk != 0.f) v += wk * (ja[q] * jb[r] + ja[r] * jb[q]); }
-            }
-          }
-          const int rmax = la >= lb ? la : lb, rmin = la >= lb ? lb : la;
-          if (RB_NWAVE == 1 || (rmax & (RB_NWAVE - 1)) == WID) atomicAdd(&s.A[RB_TRI(rmax, rmin)], v);
-        }
-        cs = ce;
-      }
-      BSYNC();
-    }
-    RB_HPROBE_END(3)
-    return;
-  }
-#endif
-  constexpr int NST = (RB_CST + RB_T - 1) / RB_T;   // words per thread (1 at 256 threads)
-  struct Staged { float v[NST]; };
-  auto stage_load = [&](int c) -> Staged {
-    Staged r;
-#pragma unroll
-    for (int k = 0; k < NST; k++) {
-      const int t = TID + k * RB_T;
-      float v = 0.f;
-      if (t < 6 * RB_CONW) v = cj[6 * RB_CONW * c + t];
-      else if (t < 7 * RB_CONW) v = cloc[RB_CONW * c + t - 6 * RB_CONW];
-      else if (t < 7 * RB_CONW + RB_NW) v = Wc[RB_NW * c + t - 7 * RB_CONW];
-      else if (t < RB_CST) v = con[RB_CONREC * c + (t == 7 * RB_CONW + RB_NW ? RB_CR_NNZ : RB_CR_DIM)];
-      r.v[k] = v;
-    }
-    return r;
-  };
-  auto stage_store = [&](int b, const Staged& r) {
-#pragma unroll
-    for (int k = 0; k < NST; k++) { const int t = TID + k * RB_T; if (t < RB_CST) s.cst[RB_CST * b + t] = r.v[k]; }
-  };
-  const Staged zero = {};
-  int buf = 0;
-  stage_store(0, stage_load(0));
-  Staged next = s.ncon > 1 ? stage_load(1) : zero;   // three contacts in flight: the words stored at the end of a pass were requested two passes earlier
-  Staged next2 = s.ncon > 2 ? stage_load(2) : zero;
-  BSYNC();
-  for (int c = 0; c < s.ncon; c++, buf ^= 1) {
-    const Staged after = c + 3 < s.ncon ? stage_load(c + 3) : zero;
-    const float* K = s.cst + RB_CST * buf;
-    const float* W = K + 7 * RB_CONW;
-    const float mode = W[RB_NW - 1];
-    if (mode != 0.f) {
-      const int nnz = (int)K[7 * RB_CONW + RB_NW], dim = (int)K[7 * RB_CONW + RB_NW + 1];
-      for (int w = TID; w < nnz * (nnz + 1) / 2; w += RB_T) {
-        int ea = (int)((sqrtf(8.f * (float)w + 1.f) - 1.f) * 0.5f);
-        if (ea * (ea + 1) / 2 > w) ea--; else if ((ea + 1) * (ea + 2) / 2 <= w) ea++;
-        const int eb = w - ea * (ea + 1) / 2;                    // every unordered pair of the contact's dofs once (eb <= ea)
+        for (int q = 0; q < 6; q++) jb[q] = __shfl(ja[q], src);
+        const int lb = __shfl(la, src);
+        if (!(on && k <= e)) continue;
         float v;
-        if (mode == 1.f) {
-          v = W[0] * K[ea] * K[eb];
-          for (int k = 0; k < dim - 1; k++) {
-            const float ja = K[(k + 1) * RB_CONW + ea], jb = K[(k + 1) * RB_CONW + eb];
-            v += W[1 + k] * (K[ea] * jb + ja * K[eb]) + W[6 + k] * ja * jb;
-          }
-        } else if (mode == 3.f) {   // diagonal weight (the same sums as the general form with its zero terms left out)
+        if (mode == 1) {
+          v = w[0] * ja[0] * jb[0];
+#pragma unroll
+          for (int q = 0; q < 5; q++) if (q < dim - 1) v += w[1 + q] * (ja[0] * jb[q + 1] + ja[q + 1] * jb[0]) + w[6 + q] * ja[q + 1] * jb[q + 1];
+        } else if (mode == 3) {
           v = 0.f;
-          for (int j = 0; j < dim; j++) v += W[j * (j + 1) / 2 + j] * K[j * RB_CONW + ea] * K[j * RB_CONW + eb];
-        } else {   // general symmetric weight of the basis rows
+#pragma unroll
+          for (int q = 0; q < 6; q++) if (q < dim) v += w[q] * ja[q] * jb[q];
+        } else {
           v = 0.f;
-          for (int j = 0; j < dim; j++) {
-            const float ja = K[j * RB_CONW + ea], jb = K[j * RB_CONW + eb];
-            v += W[j * (j + 1) / 2 + j] * ja * jb;
-            for (int k = 0; k < j; k++) { const float wk = W[j * (j + 1) / 2 + k]; if (wk != 0.f) v += wk * (ja * K[k * RB_CONW + eb] + K[k * RB_CONW + ea] * jb); }
+#pragma unroll
+          for (int q = 0; q < 6; q++) if (q < dim) {
+            v += w[q * (q + 1) / 2 + q] * ja[q] * jb[q];
+#pragma unroll
+            for (int r = 0; r < 5; r++) if (r < q) { const float wk = w[q * (q + 1) / 2 + r]; if (wk != 0.f) v += wk * (ja[q] * jb[r] + ja[r] * jb[q]); }
           }
         }
-        const int la = (int)K[6 * RB_CONW + ea], lb = (int)K[6 * RB_CONW + eb];
-        s.A[la >= lb ? RB_TRI(la, lb) : RB_TRI(lb, la)] += v;
+        const int rmax = la >= lb ? la : lb, rmin = la >= lb ? lb : la;
+        if (RB_NWAVE == 1 || (rmax & (RB_NWAVE - 1)) == WID) atomicAdd(&s.A[RB_TRI(rmax, rmin)], v);
       }
+      cs = ce;
     }
-    stage_store(buf ^ 1, next);
-    next = next2; next2 = after;
     BSYNC();
   }
+  RB_HPROBE_END(3)
 }
 
 // ------------------------------------------------------------------------------------------------- stage calls
@@ -2948,18 +2851,6 @@ __device__ __forceinline__ void rb_step_body(const RbModelDev* mp, RbKlp klp, co
       *gc = clampf(*gc + clampf(tcp_grip_action, -1.f, 1.f) * 0.5f * (L.tcp.grip_hi - L.tcp.grip_lo), L.tcp.grip_lo, L.tcp.grip_hi);
     }
   }
-#ifdef RB_LDS_ARENA
-  if (m.lds_words > 0) {   // LDS-resident stage arrays -> the env's scratch row (what the env kernel and the host's stage readers see)
-    BSYNC();
-#pragma unroll 1
-    for (int k = 0; k < RB_NOFF; k++) {
-      const int lo = m.lds_off[k];
-      if (lo < 0) continue;
-      const float* src = RB_ARENA() + lo; float* dst = S + m.off[k];
-      BFOR(w, m.lds_len[k]) dst[w] = src[w];
-    }
-  }
-#endif
   if (TID < 7 * m.nmocap && TID < 14) L.bt.mocap[(size_t)e * 7 * m.nmocap + TID] = s.mocap[TID];
   BFOR(i, nq) L.bt.qpos[(size_t)e * nq + i] = s.qpos[i];
   BFOR(i, nv) { L.bt.qvel[(size_t)e * nv + i] = s.qvel[i]; L.bt.qacc_warmstart[(size_t)e * nv + i] = s.warm[i]; }

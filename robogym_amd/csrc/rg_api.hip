@@ -881,19 +881,19 @@ void rb_model_free(rb_model* m) {
   delete m;
 }
 // the per-env scratch row: stage arrays at the model's capacities, then (models switched to per-env parameters) the env's parameter block
-// One row per stage array, in the order of the RB_O_* enumeration (rb_types.h; RB_O_PRM, the parameter block, follows the table): its name (RB_LDS_PLACE), its
-// words at the model's capacities (cw: dofs per contact row the model's configuration is compiled for) and whether it may live in the LDS arena.
-struct RbStageArray { const char* name; int (*words)(const RbModelDev& d, int cw); bool placeable; };
+// One row per stage array, in the order of the RB_O_* enumeration (rb_types.h; RB_O_PRM, the parameter block, follows the table): its words at the
+// model's capacities (cw: dofs per contact row the model's configuration is compiled for).
+typedef int (*RbStageWords)(const RbModelDev& d, int cw);
 #define RB_WORDS(expr) [](const RbModelDev& d, int cw) -> int { (void)cw; return (expr); }
-static const RbStageArray rb_stage_arrays[] = {
-  {"xpos", RB_WORDS(3 * d.nbody), true}, {"xquat", RB_WORDS(4 * d.nbody), true}, {"xipos", RB_WORDS(3 * d.nbody), true}, {"xiquat", RB_WORDS(4 * d.nbody), true},
-  {"xanchor", RB_WORDS(3 * d.njnt), true}, {"xaxis", RB_WORDS(3 * d.njnt), true}, {"gpos", RB_WORDS(3 * d.ngeom), true}, {"gquat", RB_WORDS(4 * d.ngeom), true},
-  {"spos", RB_WORDS(3 * d.nsite), true}, {"rootcom", RB_WORDS(3 * d.nbody), true}, {"cinert", RB_WORDS(10 * d.nbody), true}, {"crb", RB_WORDS(10 * d.nbody), true},
-  {"cdof", RB_WORDS(6 * d.nv), true}, {"cdofdot", RB_WORDS(6 * d.nv), true}, {"cvel", RB_WORDS(6 * d.nbody), true}, {"cacc", RB_WORDS(6 * d.nbody), true},
-  {"cfrc", RB_WORDS(6 * d.nbody), true}, {"tenlen", RB_WORDS(d.ntendon), true}, {"tenj", RB_WORDS(RB_TENW * d.ntendon), true}, {"tenvel", RB_WORDS(d.ntendon), true},
-  {"msp", RB_WORDS(d.nM), true}, {"cand", RB_WORDS(d.maxcand), true}, {"con", RB_WORDS(RB_CONREC * d.maxcon), true}, {"conj", RB_WORDS(6 * cw * d.maxcon), true},
-  {"conidx", RB_WORDS(cw * d.maxcon), true}, {"row", RB_WORDS(RB_ROWREC * d.maxrow), true}, {"dofcon_adr", RB_WORDS(d.nv + 1), true}, {"dofcon", RB_WORDS(cw * d.maxcon), true},
-  {"conf", RB_WORDS(RB_NW * d.maxcon), true}, {"dbg", RB_WORDS(8 + 5 * d.nv + 16), false}, {"cfrcext", RB_WORDS(6 * d.nbody), true}, {"conloc", RB_WORDS(cw * d.maxcon), true},
+static const RbStageWords rb_stage_arrays[] = {
+  /* xpos */ RB_WORDS(3 * d.nbody), /* xquat */ RB_WORDS(4 * d.nbody), /* xipos */ RB_WORDS(3 * d.nbody), /* xiquat */ RB_WORDS(4 * d.nbody),
+  /* xanchor */ RB_WORDS(3 * d.njnt), /* xaxis */ RB_WORDS(3 * d.njnt), /* gpos */ RB_WORDS(3 * d.ngeom), /* gquat */ RB_WORDS(4 * d.ngeom),
+  /* spos */ RB_WORDS(3 * d.nsite), /* rootcom */ RB_WORDS(3 * d.nbody), /* cinert */ RB_WORDS(10 * d.nbody), /* crb */ RB_WORDS(10 * d.nbody),
+  /* cdof */ RB_WORDS(6 * d.nv), /* cdofdot */ RB_WORDS(6 * d.nv), /* cvel */ RB_WORDS(6 * d.nbody), /* cacc */ RB_WORDS(6 * d.nbody),
+  /* cfrc */ RB_WORDS(6 * d.nbody), /* tenlen */ RB_WORDS(d.ntendon), /* tenj */ RB_WORDS(RB_TENW * d.ntendon), /* tenvel */ RB_WORDS(d.ntendon),
+  /* msp */ RB_WORDS(d.nM), /* cand */ RB_WORDS(d.maxcand), /* con */ RB_WORDS(RB_CONREC * d.maxcon), /* conj */ RB_WORDS(6 * cw * d.maxcon),
+  /* conidx */ RB_WORDS(cw * d.maxcon), /* row */ RB_WORDS(RB_ROWREC * d.maxrow), /* dofcon_adr */ RB_WORDS(d.nv + 1), /* dofcon */ RB_WORDS(cw * d.maxcon),
+  /* conf */ RB_WORDS(RB_NW * d.maxcon), /* dbg */ RB_WORDS(8 + 5 * d.nv + 16), /* cfrcext */ RB_WORDS(6 * d.nbody), /* conloc */ RB_WORDS(cw * d.maxcon),
 };
 #undef RB_WORDS
 static_assert(sizeof rb_stage_arrays / sizeof rb_stage_arrays[0] == RB_NOFF - 1 && RB_O_PRM == RB_NOFF - 1, "one row per RB_O_* stage array, and the parameter block last");
@@ -901,7 +901,7 @@ static int rb_conw(const rb_model* m) { return m->config ? RB_CONW_ONEWAVE : RB_
 static void rb_layout(rb_model* m) {
   RbModelDev& d = m->dev;
   int o = 0;
-  for (int k = 0; k < RB_O_PRM; k++) { d.off[k] = o; o += (rb_stage_arrays[k].words(d, rb_conw(m)) + 3) & ~3; }
+  for (int k = 0; k < RB_O_PRM; k++) { d.off[k] = o; o += (rb_stage_arrays[k](d, rb_conw(m)) + 3) & ~3; }
   d.prm_words = 0;
   for (int k = 0; k < RB_NPRMF; k++) d.prm_off[k] = 0;
   d.off[RB_O_PRM] = o;
@@ -1022,39 +1022,6 @@ rb_model* rb_model_create(const void* blob, size_t nbytes, char* err, int errlen
     for (int k = 0; k < RB_NPRMF; k++) { m->prm_default.insert(m->prm_default.end(), vals[k].begin(), vals[k].end()); m->prm_default.resize((m->prm_default.size() + 3) & ~(size_t)3, 0.f); }
   }
   rb_layout(m);
-  // ---- LDS residency of stage arrays (rb_types.h lds_off): RB_LDS_PLACE = a preset or a comma-separated list of array names.  Only arrays whose length does not
-  // depend on the number of contacts / rows of the mj_step can be placed (their capacity is the model's own size).
-  {
-    for (int k = 0; k < RB_NOFF; k++) { d.lds_off[k] = -1; d.lds_len[k] = 0; }
-    d.lds_words = 0;
-    const char* place = getenv("RB_LDS_PLACE");
-    std::string want = place ? place : "";
-    if (want == "frames") want = "xpos,xquat,xipos,xiquat,xanchor,xaxis,gpos,gquat,spos,rootcom";
-    else if (want == "kin") want = "xpos,xquat,xipos,xiquat,xanchor,xaxis,gpos,gquat,spos,rootcom,cinert,crb,cdof,cdofdot,cvel,cacc,cfrc,tenlen,tenj,tenvel,msp,dofcon_adr,cfrcext";
-    else if (want == "dyn") want = "cinert,crb,cdof,cdofdot,cvel,cacc,cfrc,msp";
-#ifndef RB_LDS_ARENA
-    if (!want.empty()) return bail("RB_LDS_PLACE: this library was built without -DRB_LDS_ARENA (rb_kernel.h)", m);
-#endif
-    if (!want.empty() && m->config != 0) {   // (the one-wave configurations; the large configuration's LDS is spoken for by its 96-dof block)
-      int lo = 0;
-      size_t at = 0;
-      while (at <= want.size()) {
-        const size_t e2 = want.find(',', at);
-        const std::string nm = want.substr(at, e2 == std::string::npos ? std::string::npos : e2 - at);
-        at = e2 == std::string::npos ? want.size() + 1 : e2 + 1;
-        if (nm.empty()) continue;
-        int k = -1;
-        for (int q = 0; q < RB_O_PRM; q++) if (nm == rb_stage_arrays[q].name) k = q;
-        const int len = k >= 0 && rb_stage_arrays[k].placeable ? rb_stage_arrays[k].words(d, rb_conw(m)) : 0;   // (tendon arrays are accepted by name also in a model without tendons)
-        if (k < 0 || (len == 0 && k != RB_O_TENLEN && k != RB_O_TENJ && k != RB_O_TENVEL)) return bail("RB_LDS_PLACE: unknown or unplaceable stage array name", m);
-        if (d.lds_off[k] >= 0 || len == 0) continue;
-        d.lds_off[k] = lo; d.lds_len[k] = len; lo += (len + 3) & ~3;
-      }
-      d.lds_words = lo;
-      const size_t base = m->config == 1 ? ((sizeof(rgbs::RbLds) + 15) & ~(size_t)15) : ((sizeof(rgbm::RbLds) + 15) & ~(size_t)15);
-      if (base + 4 * (size_t)lo > 64 * 1024) return bail("RB_LDS_PLACE: the arena exceeds 64 kB of LDS per workgroup", m);
-    }
-  }
   void* p = nullptr;
   if (hipMalloc(&p, sizeof(RbModelDev)) != hipSuccess) return bail("hipMalloc failed", m);
   m->allocs.push_back(p);
@@ -1192,7 +1159,7 @@ int rb_model_info(const rb_model* m, int* out, int n) {
   if (!m) return fail("null model");
   const RbModelDev& d = m->dev;
   const int v[] = {d.nq, d.nv, d.nu, d.nbody, d.njnt, d.ngeom, d.nsite, d.ntendon, d.nM, d.npair, d.ngroup, d.gmax, d.maxcon, d.maxrow, d.scratch_words, RB_CONREC, RB_ROWREC, rb_conw(m), RB_TENW,
-                   (m->config == 1 ? (int)sizeof(rgbs::RbLds) : m->config == 2 ? (int)sizeof(rgbm::RbLds) : (int)sizeof(rgb::RbLds)) + (d.lds_words ? 4 * d.lds_words + 16 : 0), m->config == 1 ? RB_T_SMALL : m->config == 2 ? RB_T_MEDIUM : RB_T_LARGE};
+                   (m->config == 1 ? (int)sizeof(rgbs::RbLds) : m->config == 2 ? (int)sizeof(rgbm::RbLds) : (int)sizeof(rgb::RbLds)), m->config == 1 ? RB_T_SMALL : m->config == 2 ? RB_T_MEDIUM : RB_T_LARGE};
   const int k = (int)(sizeof v / sizeof v[0]);
   for (int i = 0; i < k && i < n; i++) out[i] = v[i];
   return k;
@@ -1329,13 +1296,11 @@ static thread_local const RbTcpHook* g_tcp_hook = nullptr;   // set by rb_batch_
 // their launch instead of issuing it
 struct RbCollected { const rb_batch* b; RbLaunch launch; };
 static thread_local std::vector<RbCollected>* g_multi = nullptr;
-// dynamic LDS of a launch behind RbLds: the model's arena, if it placed stage arrays there (+16: the arena starts at the next 16-byte boundary behind RbLds)
-static size_t rb_arena_bytes(const rb_model* m) { return m->dev.lds_words ? 4 * (size_t)m->dev.lds_words + 16 : 0; }
 static int rb_issue(const rb_batch* b, const RbLaunch& launch_args, void* stream) {
   const rb_model* m = b->model;
   DeviceGuard g(b->device);
-  if (m->config == 1) return launch(rgbs::rb_step_kernel, launch_args.bt.B, RB_T_SMALL, sizeof(rgbs::RbLds) + rb_arena_bytes(m), 0, stream, m->dev_copy, launch_args);
-  if (m->config == 2) return launch(rgbm::rb_step_kernel, launch_args.bt.B, RB_T_MEDIUM, sizeof(rgbm::RbLds) + rb_arena_bytes(m), 0, stream, m->dev_copy, launch_args);
+  if (m->config == 1) return launch(rgbs::rb_step_kernel, launch_args.bt.B, RB_T_SMALL, sizeof(rgbs::RbLds), 0, stream, m->dev_copy, launch_args);
+  if (m->config == 2) return launch(rgbm::rb_step_kernel, launch_args.bt.B, RB_T_MEDIUM, sizeof(rgbm::RbLds), 0, stream, m->dev_copy, launch_args);
   return launch(rgb::rb_step_kernel, launch_args.bt.B, RB_T_LARGE, sizeof(rgb::RbLds), 0, stream, m->dev_copy, launch_args);
 }
 int rb_multi_begin(void) {
@@ -1352,8 +1317,7 @@ int rb_multi_launch(void* stream) {
   for (size_t a = 0; a < v.size(); a++) for (size_t c = a + 1; c < v.size(); c++) if (v[a].b == v[c].b) return fail("rb_multi_launch: the same batch was recorded twice between rb_multi_begin and rb_multi_launch");
   bool same = v.size() <= RB_MAXMULTI;
   for (const RbCollected& c : v)
-    same = same && c.b->dev.B == v[0].b->dev.B && c.b->device == v[0].b->device && c.b->model->config == v[0].b->model->config && (c.b->model->config == 1 || c.b->model->config == 2) &&
-           c.b->model->dev.lds_words == v[0].b->model->dev.lds_words;
+    same = same && c.b->dev.B == v[0].b->dev.B && c.b->device == v[0].b->device && c.b->model->config == v[0].b->model->config && (c.b->model->config == 1 || c.b->model->config == 2);
   if (!same || v.size() == 1) {      // different sizes / configurations (or a single batch): one launch each, in order
     for (const RbCollected& c : v) { const int rc = rb_issue(c.b, c.launch, stream); if (rc) return rc; }
     return 0;
@@ -1363,9 +1327,8 @@ int rb_multi_launch(void* stream) {
   ml.n = (int)v.size(); ml.group_size = v[0].b->dev.B;
   for (size_t k = 0; k < v.size(); k++) { ml.m[k] = v[k].b->model->dev_copy; ml.L[k] = v[k].launch; }
   const int total = ml.n * ml.group_size, cfg = v[0].b->model->config;
-  const size_t arena = rb_arena_bytes(v[0].b->model);
-  if (cfg == 1) return launch(rgbs::rb_step_multi_kernel, total, RB_T_SMALL, sizeof(rgbs::RbLds) + arena, 0, stream, ml);
-  return launch(rgbm::rb_step_multi_kernel, total, RB_T_MEDIUM, sizeof(rgbm::RbLds) + arena, 0, stream, ml);
+  if (cfg == 1) return launch(rgbs::rb_step_multi_kernel, total, RB_T_SMALL, sizeof(rgbs::RbLds), 0, stream, ml);
+  return launch(rgbm::rb_step_multi_kernel, total, RB_T_MEDIUM, sizeof(rgbm::RbLds), 0, stream, ml);
 }
 int rb_batch_step_ex(rb_batch* b, const float* action_dev, const int* active_dev, const int* hold_dev, const int* nticks_dev, int nsubsteps, int nforward_ticks, int flags, void* stream) {
   if (!b) return fail("null batch");
@@ -1422,8 +1385,8 @@ int rb_batch_set_constants(rb_batch* b, const int* mask_dev, void* stream) {
   RbBatchDev bt = b->dev;
   bt.action = nullptr; bt.active = mask_dev; bt.hold = nullptr; bt.nticks = nullptr;
   RbLaunch launch_args{b->env, bt, 0, 0, 0, RbTcpHook{}};
-  if (m->config == 1) return launch(rgbs::rb_setconst_kernel, bt.B, RB_T_SMALL, sizeof(rgbs::RbLds) + rb_arena_bytes(m), 0, stream, m->dev_copy, launch_args);
-  if (m->config == 2) return launch(rgbm::rb_setconst_kernel, bt.B, RB_T_MEDIUM, sizeof(rgbm::RbLds) + rb_arena_bytes(m), 0, stream, m->dev_copy, launch_args);
+  if (m->config == 1) return launch(rgbs::rb_setconst_kernel, bt.B, RB_T_SMALL, sizeof(rgbs::RbLds), 0, stream, m->dev_copy, launch_args);
+  if (m->config == 2) return launch(rgbm::rb_setconst_kernel, bt.B, RB_T_MEDIUM, sizeof(rgbm::RbLds), 0, stream, m->dev_copy, launch_args);
   return launch(rgb::rb_setconst_kernel, bt.B, RB_T_LARGE, sizeof(rgb::RbLds), 0, stream, m->dev_copy, launch_args);
 }
 int rb_post_args_size(void) { return (int)sizeof(rb_post_args); }

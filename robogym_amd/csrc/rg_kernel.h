@@ -72,21 +72,13 @@ __device__ __forceinline__ unsigned long long rg_uniform(const void* p) {
 #define RG_M(c) (*(const RG_AS4 RgModelDev*)rg_uniform((c).km))
 #define RG_L(c) (*(const RG_AS4 RgLaunch*)rg_uniform((c).kl))
 #define RG_S() (*(RgLds*)rg_lds_raw)
-#ifdef RG_INLINE_STAGES
-#define RG_STAGE __device__ __forceinline__
-#else
 #define RG_STAGE __device__ __attribute__((noinline))
-#endif
 typedef const RG_AS4 RgLaunch& RgLRef;
 #endif
 #ifdef RG_EMUL
 #define RG_STAGE_BIG static inline
 #else
-#ifdef RG_BIG_STAGES_AS_CALLS
-#define RG_STAGE_BIG __device__ __attribute__((noinline))
-#else
 #define RG_STAGE_BIG __device__ __forceinline__   /* the register-hungriest stages stay in the kernel body: a call would save/restore ~30 callee-saved VGPRs through scratch */
-#endif
 #endif
 // env handled by this workgroup: the launch may carry a permutation (longest-expected-first dispatch order)
 #ifdef RG_EMUL
@@ -262,7 +254,7 @@ __device__ __forceinline__ void wave_argmax(float& v, int& i) {
 #ifdef RG_EMUL
 static inline long long rg_clock() { return 0; }
 #else
-#ifdef RG_CLOCK_REALTIME   /* analysis builds (tools/tail_analysis.py): the constant-rate counter instead of the shader clock */
+#ifdef RG_CLOCK_REALTIME   /* analysis builds (tools/residency_curve.py): the constant-rate counter instead of the shader clock */
 __device__ __forceinline__ long long rg_clock() { return (long long)__builtin_amdgcn_s_memrealtime(); }
 #else
 __device__ __forceinline__ long long rg_clock() { return (long long)__builtin_readcyclecounter(); }
@@ -278,8 +270,6 @@ static inline int rg_ld_sc1(const int* p) { return *p; }
 static inline float rg_ld_sc1(const float* p) { return *p; }
 static inline unsigned rg_ld_sc1(const unsigned* p) { return *p; }
 static inline void rg_st_sc1(int* p, int v) { *p = v; }
-static inline void rg_st_sc1(unsigned* p, unsigned v) { *p = v; }
-static inline void rg_st_sc1(float* p, float v) { *p = v; }
 static inline int rg_ticket(int* p) { int o = *p; *p = o + 1; return o; }
 static inline void rg_drain_stores() {}
 static inline void rg_pause() {}
@@ -290,8 +280,6 @@ __device__ __forceinline__ int rg_ld_sc1(const int* p) { return __hip_atomic_loa
 __device__ __forceinline__ unsigned rg_ld_sc1(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float rg_ld_sc1(const float* p) { return __builtin_bit_cast(float, __hip_atomic_load((const int*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); }
 __device__ __forceinline__ void rg_st_sc1(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void rg_st_sc1(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void rg_st_sc1(float* p, float v) { __hip_atomic_store((int*)p, __builtin_bit_cast(int, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ int rg_ticket(int* p) { return __hip_atomic_fetch_add(p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void rg_drain_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void rg_pause() { __builtin_amdgcn_s_sleep(16); }
@@ -345,16 +333,11 @@ static float rg_wchk_max = 0.f; static int rg_wchk_n = 0, rg_wchk_rows = 0;   //
 #else
 #define RG_ROW_LD(p) (*(p))
 #endif
-// stores of the rows a later work item of the env reads.  Default: plain stores (made visible in the XCD's L2 by rg_item_publish's vmcnt drain: the vector L1 is
-// write-through).  -DRG_ROW_ST_SC1: agent-scope relaxed atomic stores, the formal counterpart of RG_ROW_LD (A/B: profiles/r05_ab_items_sc1_stores.txt).
+// stores of the rows a later work item of the env reads: plain stores (made visible in the XCD's L2 by rg_item_publish's vmcnt drain: the vector L1 is
+// write-through).  Agent-scope relaxed atomic stores, the formal counterpart of RG_ROW_LD, cost 2.5 % (A/B: profiles/r05_ab_items_sc1_stores.txt).
 #undef RG_SEPDIR_ST
-#if RG_ITEMS && defined(RG_ROW_ST_SC1)
-#define RG_ROW_ST(p, v) rg_st_sc1((p), (v))
-#define RG_SEPDIR_ST(p, cd) do { float* sp__ = (float*)(p); rg_st_sc1(sp__, (cd).x); rg_st_sc1(sp__ + 1, (cd).y); rg_st_sc1(sp__ + 2, (cd).z); } while (0)
-#else
 #define RG_ROW_ST(p, v) (*(p) = (v))
 #define RG_SEPDIR_ST(p, cd) (*(p) = (cd))
-#endif
 #ifndef RG_SETCONST
 #define RG_SETCONST 0  /* 1: this configuration also carries rg_setconst_kernel (one instantiation is enough) */
 #endif
@@ -2525,11 +2508,7 @@ template <bool SENSORS> __device__ __forceinline__ int rg_solve(RgM m, RgLds& s,
   SYNC();
   // When every contact couples the dofs of ONE chain only (a body against a static geom, or against one of its own
   // ancestors), J'DJ has the pattern of M and the Hessian is factorised tree-sparsely like M instead of densely.
-#ifdef RG_NO_TREE_NEWTON
-  bool tree = false;
-#else
   bool tree = m.tree_newton_ok != 0;
-#endif
   if (tree) {
     bool cross = false;
     PFOR(c, ncon) {
@@ -2750,13 +2729,8 @@ template <bool SENSORS> __device__ __forceinline__ int rg_solve(RgM m, RgLds& s,
   PROFF(35);
   // Every exit of the loop leaves s.jtf = J' f(a) for the final a (the gradient evaluation at the top of the pass that
   // broke out, or the pass whose step length came out zero), so the forces at the solution are already there; only the
-  // expansion to the full dof space remains.  (RG_SOLVE_RECOMPUTE: evaluate them once more from J a - aref computed from
-  // scratch instead of the incrementally advanced residuals: identical to ~1e-7 relative, and 3.5 % of the step.)
-#ifdef RG_SOLVE_RECOMPUTE
-  rg_J_mul(m, s, RR, s.a, false);
-  { bool chg; int nsd; rg_constraint_update(m, s, RR, chg, nsd); }
-  rg_JT_force(m, s, RR, s.jtf);
-#endif
+  // expansion to the full dof space remains.  (Evaluating them once more from J a - aref computed from scratch instead of
+  // the incrementally advanced residuals came out identical to ~1e-7 relative, and cost 3.5 % of the step.)
   if (SENSORS) {   // sensor pass (its own instantiation: the hot path's solver carries none of this): normal force of every contact = sum of its pyramid edge forces (mju_decodePyramid), f = -D jar where jar < 0
     PFOR(c, ncon) s.c_bdot[c] = 0.f;
     SYNC();
@@ -2909,8 +2883,8 @@ RG_STAGE void st_factor_smooth(RgCtx c) { RgLds& s = RG_S(); rg_ltdl_factor_solv
 // The Newton stage runs at raised wave priority (s_setprio): it is the kernel's longest dependent instruction chain (the register elimination alone takes 5.3 k cycles
 // for a wave by itself and 15 k between two others), while the waves it shares its SIMD with are mostly in stages with independent work in flight -- the arbiter
 // then serves the chain first.  Measured +0.4 ... +0.6 % on the bench line (profiles/r06_ab_newton.txt); level 3, or raising the collision stage / the tree sweeps as
-// well, measured no better.  -DRG_NO_PRIO builds without it.
-#if !defined(RG_EMUL) && !defined(RG_NO_PRIO)
+// well, measured no better.
+#ifndef RG_EMUL
 #define RG_SOLVE_PRIO(level) __builtin_amdgcn_s_setprio(level)
 #else
 #define RG_SOLVE_PRIO(level) do { } while (0)
