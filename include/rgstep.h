@@ -258,6 +258,88 @@ typedef struct rg_post_args {
 } rg_post_args;
 int rg_env_post_step(rg_batch* b, const rg_post_args* args, void* stream);
 int rg_post_args_size(void);   /* sizeof(rg_post_args) as compiled: a binding checks its own struct against it */
+/* ---- The default wrapper stack of the dactyl cube envs, per-step half, as two launches around the physics launch
+ * (rg_wrap_kernel.h; the tensor form is robogym_amd/wrappers/dactyl_cube.py, BatchedDactylCubeWrappers.step):
+ *   rg_wrap_pre_step    MultiDiscrete bin index -> action, previous_action, action noise, exponential smoothing, action latency,
+ *                       backlash, fixed wrist, clip: writes the [B][nu] action row that rg_batch_step_ex reads
+ *   rg_wrap_post_step   randomized timestep and wind into the env's parameter row, stop-on-fall with the drop reward,
+ *                       min_episode_length, reward concat + clip, and every observation key into ONE packed [B][W] row
+ * Neither takes an rg_batch: all arrays are plain device pointers (float32 / int32 unless noted), rows of the env's own buffers
+ * with their strides in 4-byte words, so a scripted env or a C host can feed them.  The per-env wrapper state lives in two
+ * caller-owned rows (float [B][lay.fwidth], int [B][lay.iwidth]); rg_wrap_layout fills `lay` from `dims`: the state offsets, the
+ * column offset of every key in the packed row (-1: the configuration has no such key) and the column of every draw.  The reset
+ * half of the stack (episode parameters, biases, buffers) is the caller's: it writes the state rows.
+ * Randomness stays outside: u [B][32] uniforms in [0,1), n [B][128] standard normals, e [B][32] unit exponentials or NULL
+ * (then -log1p(-u) of the same column: u and e share one cursor).  Draw columns, randomize: normals = nu action noise, 3 wind,
+ * then cube_pos 3, cube_quat 1, fingertip_pos ntip, hand_angle nh; uniforms = timestep flip, timestep exponential, wind hit,
+ * 3 quaternion axis, 5 + 5 finger freeze (happens, length), 1 + 1 cube freeze.  Without randomize only the observation noise
+ * and the quaternion axis are drawn, from column 0. */
+#define RG_WRAP_U_POOL 32
+#define RG_WRAP_N_POOL 128
+enum {   /* keys of the packed row, in the reference's key order; RG_WK_DELTA is the block of the RandomizedBodyWrapper family's entries (dims.ndelta floats, the caller knows its parts) */
+  RG_WK_CUBE_POS, RG_WK_CUBE_QUAT, RG_WK_QPOS, RG_WK_QVEL, RG_WK_HAND_ANGLE, RG_WK_FINGERTIP_POS, RG_WK_GOAL_POS, RG_WK_GOAL_QUAT, RG_WK_QPOS_GOAL,
+  RG_WK_IS_GOAL_ACHIEVED, RG_WK_FELL_DOWN, RG_WK_ACTION_HISTORY, RG_WK_ACTION_DELAY, RG_WK_DELTA, RG_WK_NOISY_CUBE_POS, RG_WK_NOISY_CUBE_QUAT,
+  RG_WK_NOISY_FINGERTIP_POS, RG_WK_NOISY_HAND_ANGLE, RG_WK_ACTION_EMA, RG_WK_ACH_POS, RG_WK_REL_POS, RG_WK_NACH_POS, RG_WK_NREL_POS, RG_WK_ACH_QUAT,
+  RG_WK_REL_QUAT, RG_WK_NACH_QUAT, RG_WK_NREL_QUAT, RG_WK_RELATIVE_GOAL, RG_WK_NOISY_RELATIVE_GOAL, RG_WK_ACHIEVED_GOAL, RG_WK_NOISY_ACHIEVED_GOAL,
+  RG_WK_GOAL, RG_WK_PREVIOUS_ACTION, RG_WK_REWARD, RG_WK_COUNT
+};
+typedef struct rg_wrap_dims {
+  int nq, nv, nu, nh, ntip;     /* widths of the env's observation row: cube_pos 3 | cube_quat 4 | qpos nq | qvel nv | hand_angle nh | fingertip_pos ntip; nu actuators */
+  int ndelta;                   /* floats of the RandomizedBodyWrapper family's observation entries (0 without randomize) */
+  int randomize, relative_goal; /* the stack's constructor options that change the key set */
+} rg_wrap_dims;
+typedef struct rg_wrap_lay {
+  int fwidth, iwidth, W;        /* floats / ints of state per env, floats of the packed row */
+  /* float state: previous_action nu, EMA value nu, EMA alpha 1, action_ema nu, action history nu, slack nu, backlash coefficients down / up nu each,
+   * action-noise mult / add nu each, additive and multiplicative observation biases (cube_pos 3, cube_quat 1, fingertip_pos ntip, hand_angle nh each),
+   * timestep noise (pos_lambda, neg_lambda, side, p_flip_pos, p_flip_neg), wind hit probability, occlusion buffer ntip, finger freeze buffer ntip and
+   * its 5 counters, cube freeze counter and buffers (relative pos 3, relative quat 4, achieved pos 3, achieved quat 4, cube pos 3), the ndelta entries */
+  int s_prev, s_ema, s_alpha, s_aema, s_hist, s_slack, s_cdown, s_cup, s_anmult, s_anadd, s_addb, s_mulb, s_ts, s_wind, s_occl, s_ffbuf, s_ffleft, s_cfleft, s_cfbuf, s_delta;
+  int i_emat, i_steps, i_drops, i_first, i_delay;   /* int state: EMA step count, steps, drops_so_far, first_drop, action delay nu */
+  int n_action, n_wind, n_noise[4];                 /* columns of n: action noise, wind, observation noise per sorted key */
+  int u_ts, u_wind, u_axis, u_ff, u_cf;             /* columns of u / e */
+  int key[RG_WK_COUNT];
+} rg_wrap_lay;
+typedef struct rg_wrap_args {
+  int B, device;
+  rg_wrap_dims dims;
+  rg_wrap_lay lay;              /* as rg_wrap_layout(&dims, &lay) filled it */
+  float* fstate; int* istate;
+  const float *u, *n, *e;       /* the step's draw blocks (e may be NULL) */
+  /* ---- pre */
+  const long long* action_index;   /* int64 [B][nu] bin indices */
+  const float* bins; int nbins;    /* [nbins] bin centres */
+  float* action_out;               /* [B][nu] */
+  const float* qpos; int qpos_stride;      /* the envs' qpos rows (backlash, fixed wrist; may be NULL when neither is on) */
+  const int* hand_q;                       /* [nh] qpos columns of the hand joints */
+  const float* pos_to_ctrl;                /* [nu][nh] */
+  float* prm; int prm_stride;              /* the envs' parameter rows (randomize; rg_prm_layout offsets below) or NULL */
+  int p_ctrlrange, p_timestep, p_xfrc_cube, p_mass_cube;   /* offsets of actuator_ctrlrange, timestep, the cube body's xfrc_applied and body_mass */
+  int relative_action, nsubsteps, fixed_wrist, wrist_act, wrist_qadr;
+  float wrist_lo, wrist_hi;                /* the wrist actuator's ctrlrange when there is no parameter row */
+  /* ---- post: what the env's step produced */
+  const float* obs; int obs_stride;
+  const float *goal_pos, *goal_quat, *qpos_goal;   /* [B][3] or NULL (zeros), [B][4], [B][nq] */
+  const int* is_goal_achieved;
+  const float* contact; int contact_stride, ncon_slots;   /* the stepper's raw contact record [slots][3] = geom1, geom2, dist (rg_xdata_layout) */
+  const float* ncon; int ncon_stride;
+  const float* env_reward;                 /* [B][3] */
+  const unsigned char* env_done;           /* [B] */
+  const int* successes_so_far;
+  /* ---- post: outputs */
+  float *out, *reward_out;                 /* [B][lay.W], [B][4] = env, goal, success, drop */
+  unsigned char *done_out, *fell_out;      /* [B] */
+  int* info_out;                           /* [B][2] = drops_so_far, first_drop */
+  /* ---- constants (thresholds in fp32: what the tensor form compares in) */
+  float occ_geom[5]; int n_occ;            /* occlusion geom ids as the floats of the contact record; 0: no occlusion check */
+  float timestep0, cube_body_z, fall_z, occ_cutoff, ff_p, cf_p, freeze_scale, drop_reward, clip;
+  int min_episode_length;
+  float unc[4];                            /* uncorrelated noise level per sorted key */
+} rg_wrap_args;
+int rg_wrap_layout(const rg_wrap_dims* dims, rg_wrap_lay* lay);
+int rg_wrap_pre_step(const rg_wrap_args* args, void* stream);
+int rg_wrap_post_step(const rg_wrap_args* args, void* stream);
+int rg_wrap_args_size(void);
 /* mj_setConst for the envs of `mask_dev` (int [B] device pointer, NULL: all) -- replaces `MjSim.set_constants()` =
  * `mujoco_simulation.set_constants()`, which the reference calls in every `_reset` after the randomizers have written
  * the model (/root/reference/robogym/envs/dactyl/common/cube_env.py:346-349,

@@ -122,6 +122,48 @@ class RaRecipeArgs(ctypes.Structure):
     _fields_ = _ra_recipe_fields()
 
 
+# the wrapper stack's two launches (include/rgstep.h rg_wrap_*): the packed row's keys in RG_WK_* order ("_delta": the block of the RandomizedBodyWrapper family's entries)
+RG_WRAP_U_POOL, RG_WRAP_N_POOL = 32, 128
+RG_WRAP_KEYS = ["cube_pos", "cube_quat", "qpos", "qvel", "hand_angle", "fingertip_pos", "goal_pos", "goal_quat", "qpos_goal", "is_goal_achieved", "fell_down", "action_history",
+                "action_delay", "_delta", "noisy_cube_pos", "noisy_cube_quat", "noisy_fingertip_pos", "noisy_hand_angle", "action_ema", "achieved_goal_pos", "relative_goal_pos",
+                "noisy_achieved_goal_pos", "noisy_relative_goal_pos", "achieved_goal_quat", "relative_goal_quat", "noisy_achieved_goal_quat", "noisy_relative_goal_quat",
+                "relative_goal", "noisy_relative_goal", "achieved_goal", "noisy_achieved_goal", "goal", "previous_action", "reward"]
+
+
+class WrapDims(ctypes.Structure):
+    """`rg_wrap_dims` of include/rgstep.h."""
+
+    _fields_ = [(n, ctypes.c_int) for n in ("nq", "nv", "nu", "nh", "ntip", "ndelta", "randomize", "relative_goal")]
+
+
+class WrapLay(ctypes.Structure):
+    """`rg_wrap_lay` of include/rgstep.h."""
+
+    _fields_ = ([(n, ctypes.c_int) for n in ("fwidth", "iwidth", "W", "s_prev", "s_ema", "s_alpha", "s_aema", "s_hist", "s_slack", "s_cdown", "s_cup", "s_anmult", "s_anadd", "s_addb",
+                                             "s_mulb", "s_ts", "s_wind", "s_occl", "s_ffbuf", "s_ffleft", "s_cfleft", "s_cfbuf", "s_delta", "i_emat", "i_steps", "i_drops", "i_first",
+                                             "i_delay", "n_action", "n_wind")]
+                + [("n_noise", ctypes.c_int * 4)] + [(n, ctypes.c_int) for n in ("u_ts", "u_wind", "u_axis", "u_ff", "u_cf")] + [("key", ctypes.c_int * len(RG_WRAP_KEYS))])
+
+
+def _wrap_fields():
+    p_, i_, f_ = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    return ([("B", i_), ("device", i_), ("dims", WrapDims), ("lay", WrapLay), ("fstate", p_), ("istate", p_), ("u", p_), ("n", p_), ("e", p_),
+             ("action_index", p_), ("bins", p_), ("nbins", i_), ("action_out", p_), ("qpos", p_), ("qpos_stride", i_), ("hand_q", p_), ("pos_to_ctrl", p_),
+             ("prm", p_), ("prm_stride", i_)]
+            + [(n, i_) for n in ("p_ctrlrange", "p_timestep", "p_xfrc_cube", "p_mass_cube", "relative_action", "nsubsteps", "fixed_wrist", "wrist_act", "wrist_qadr")]
+            + [("wrist_lo", f_), ("wrist_hi", f_), ("obs", p_), ("obs_stride", i_), ("goal_pos", p_), ("goal_quat", p_), ("qpos_goal", p_), ("is_goal_achieved", p_),
+               ("contact", p_), ("contact_stride", i_), ("ncon_slots", i_), ("ncon", p_), ("ncon_stride", i_), ("env_reward", p_), ("env_done", p_), ("successes_so_far", p_),
+               ("out", p_), ("reward_out", p_), ("done_out", p_), ("fell_out", p_), ("info_out", p_), ("occ_geom", f_ * 5), ("n_occ", i_)]
+            + [(n, f_) for n in ("timestep0", "cube_body_z", "fall_z", "occ_cutoff", "ff_p", "cf_p", "freeze_scale", "drop_reward", "clip")]
+            + [("min_episode_length", i_), ("unc", f_ * 4)])
+
+
+class WrapArgs(ctypes.Structure):
+    """`rg_wrap_args` of include/rgstep.h (field order and types must match; bind() checks the size)."""
+
+    _fields_ = _wrap_fields()
+
+
 EXPORTS = [
     "rg_model_create", "rg_model_free", "rg_model_dims", "rg_batch_create", "rg_batch_free", "rg_batch_set_env",
     "rg_batch_copy", "rg_batch_reset", "rg_batch_step", "rg_obs_dim", "rg_debug_size", "rg_lds_bytes", "rg_sync",
@@ -131,6 +173,7 @@ EXPORTS = [
     "rb_batch_field_ptr", "rb_batch_step", "rb_batch_step_ex", "rb_env_post_step", "rb_post_args_size", "rb_cube_ops", "rb_batch_step_tcp", "ra_env_post_step", "ra_post_args_size",
     "rg_blob_entry", "rg_model_blob_keys", "rb_model_blob_keys", "rg_compile_mjcf", "rb_compile_mjcf", "rg_compile_mjcf_blob", "rg_blob_free",
     "rb_model_enable_env_params", "rb_prm_layout", "rb_batch_set_action_limits", "ra_env_recipe_step", "ra_recipe_args_size", "rb_tcp_args_size", "rb_multi_begin", "rb_multi_launch",
+    "rg_wrap_layout", "rg_wrap_pre_step", "rg_wrap_post_step", "rg_wrap_args_size",
 ]
 EXPORTS_SETCONST = ["rb_batch_set_constants"]      # include/rgstep_setconst.h (EXPORTS is what include/rgstep.h itself declares)
 
@@ -180,6 +223,12 @@ def bind(path):
     L.rg_post_args_size.restype = ci
     if L.rg_post_args_size() != ctypes.sizeof(PostArgs):
         raise NativeError("rg_post_args layout mismatch between include/rgstep.h and robogym_amd/_native.py")
+    L.rg_wrap_layout.argtypes = [ctypes.POINTER(WrapDims), ctypes.POINTER(WrapLay)]
+    L.rg_wrap_pre_step.argtypes = [ctypes.POINTER(WrapArgs), vp]
+    L.rg_wrap_post_step.argtypes = [ctypes.POINTER(WrapArgs), vp]
+    L.rg_wrap_args_size.restype = ci
+    if L.rg_wrap_args_size() != ctypes.sizeof(WrapArgs):
+        raise NativeError("rg_wrap_args layout mismatch between include/rgstep.h and robogym_amd/_native.py")
     L.rg_batch_set_constants.argtypes = [vp, vp, vp]
     L.rg_batch_items_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
     L.rb_model_create.restype = vp

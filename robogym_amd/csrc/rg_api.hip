@@ -91,6 +91,7 @@ struct DeviceGuard {
 #endif
 
 #include "rg_env_kernel.h"
+#include "rg_wrap_kernel.h"
 #define RB_NS rgb            /* large configuration: 4 waves per env (dactyl/full_perpendicular) */
 #define RB_T RB_T_LARGE
 #define RB_MAXGROUP RB_MAXGROUP_LARGE
@@ -838,6 +839,83 @@ int rg_env_post_step(rg_batch* b, const rg_post_args* args, void* stream) {
   if (d.nu > 20) return fail("rg_env_post_step: nu exceeds RG_POST_NDRAW's action slots");
   DeviceGuard g(b->device);
   return launch(rg_post_step_kernel, b->dev.B, RG_WAVE, 0, sizeof(RgPostFlags), stream, b->dev, a, d.nq, d.nv, d.nu, d.npair);
+}
+
+// ---- the wrapper stack's two launches (rg_wrap_kernel.h)
+int rg_wrap_args_size(void) { return (int)sizeof(rg_wrap_args); }
+int rg_wrap_layout(const rg_wrap_dims* dims, rg_wrap_lay* lay) {
+  if (!dims || !lay) return fail("rg_wrap_layout: null argument");
+  const rg_wrap_dims& d = *dims;
+  if (d.nq < 0 || d.nv < 0 || d.nu < 1 || d.nh < 0 || d.ntip < 0 || d.ndelta < 0) return fail("rg_wrap_layout: negative width");
+  const int rnd = d.randomize != 0, rel = d.relative_goal != 0, nb = 4 + d.ntip + d.nh;
+  rg_wrap_lay& L = *lay;
+  // the one table of each layout: (field, width) in order
+  int at = 0;
+  const struct { int* off; int n; } fstate[] = {
+    {&L.s_prev, d.nu}, {&L.s_ema, d.nu}, {&L.s_alpha, 1}, {&L.s_aema, d.nu}, {&L.s_hist, d.nu}, {&L.s_slack, d.nu}, {&L.s_cdown, d.nu}, {&L.s_cup, d.nu},
+    {&L.s_anmult, d.nu}, {&L.s_anadd, d.nu}, {&L.s_addb, nb}, {&L.s_mulb, nb}, {&L.s_ts, 5}, {&L.s_wind, 1}, {&L.s_occl, d.ntip}, {&L.s_ffbuf, d.ntip},
+    {&L.s_ffleft, 5}, {&L.s_cfleft, 1}, {&L.s_cfbuf, 17}, {&L.s_delta, d.ndelta}};
+  for (const auto& f : fstate) { *f.off = at; at += f.n; }
+  L.fwidth = at;
+  at = 0;
+  const struct { int* off; int n; } istate[] = {{&L.i_emat, 1}, {&L.i_steps, 1}, {&L.i_drops, 1}, {&L.i_first, 1}, {&L.i_delay, d.nu}};
+  for (const auto& f : istate) { *f.off = at; at += f.n; }
+  L.iwidth = at;
+  // draw columns, in the tensor stack's consumption order
+  at = 0;
+  if (rnd) { L.n_action = at; at += d.nu; L.n_wind = at; at += 3; } else { L.n_action = L.n_wind = -1; }
+  const int nw[4] = {3, 1, d.ntip, d.nh};
+  for (int k = 0; k < 4; k++) { L.n_noise[k] = at; at += nw[k]; }
+  if (at > RG_WRAP_N_POOL) return fail("rg_wrap_layout: the step's normal draws exceed RG_WRAP_N_POOL");
+  at = 0;
+  if (rnd) { L.u_ts = at; at += 2; L.u_wind = at; at += 1; } else { L.u_ts = L.u_wind = -1; }
+  L.u_axis = at; at += 3;
+  if (rnd) { L.u_ff = at; at += 10; L.u_cf = at; at += 2; } else { L.u_ff = L.u_cf = -1; }
+  // packed row: (key, width, present)
+  const struct { int key, n, on; } keys[] = {
+    {RG_WK_CUBE_POS, 3, 1}, {RG_WK_CUBE_QUAT, 4, 1}, {RG_WK_QPOS, d.nq, 1}, {RG_WK_QVEL, d.nv, 1}, {RG_WK_HAND_ANGLE, 2 * d.nh, 1}, {RG_WK_FINGERTIP_POS, d.ntip, 1},
+    {RG_WK_GOAL_POS, 3, 1}, {RG_WK_GOAL_QUAT, 4, 1}, {RG_WK_QPOS_GOAL, d.nq, 1}, {RG_WK_IS_GOAL_ACHIEVED, 1, 1}, {RG_WK_FELL_DOWN, 1, 1},
+    {RG_WK_ACTION_HISTORY, d.nu, rnd}, {RG_WK_ACTION_DELAY, d.nu, rnd}, {RG_WK_DELTA, d.ndelta, rnd},
+    {RG_WK_NOISY_CUBE_POS, 3, 1}, {RG_WK_NOISY_CUBE_QUAT, 4, 1}, {RG_WK_NOISY_FINGERTIP_POS, d.ntip, 1}, {RG_WK_NOISY_HAND_ANGLE, 2 * d.nh, 1}, {RG_WK_ACTION_EMA, d.nu, 1},
+    {RG_WK_ACH_POS, 3, rel}, {RG_WK_REL_POS, 3, rel}, {RG_WK_NACH_POS, 3, rel}, {RG_WK_NREL_POS, 3, rel}, {RG_WK_ACH_QUAT, 4, rel}, {RG_WK_REL_QUAT, 4, rel},
+    {RG_WK_NACH_QUAT, 4, rel}, {RG_WK_NREL_QUAT, 4, rel}, {RG_WK_RELATIVE_GOAL, 7, rel}, {RG_WK_NOISY_RELATIVE_GOAL, 7, rel}, {RG_WK_ACHIEVED_GOAL, 7, rel},
+    {RG_WK_NOISY_ACHIEVED_GOAL, 7, rel}, {RG_WK_GOAL, 7, 1}, {RG_WK_PREVIOUS_ACTION, d.nu, 1}, {RG_WK_REWARD, 2, 1}};
+  static_assert(sizeof keys / sizeof keys[0] == RG_WK_COUNT, "one table entry per key");
+  at = 0;
+  for (const auto& k : keys) { L.key[k.key] = k.on ? at : -1; at += k.on ? k.n : 0; }
+  L.W = at;
+  return 0;
+}
+// the checks both launches share: every pointer the configuration reads, and that `lay` is what rg_wrap_layout gives for `dims`
+static int rg_wrap_check(const rg_wrap_args* args, bool post) {
+  if (!args) return fail("rg_wrap: null argument");
+  const rg_wrap_args& a = *args;
+  rg_wrap_lay want;
+  if (rg_wrap_layout(&a.dims, &want) != 0) return -1;
+  if (memcmp(&want, &a.lay, sizeof want) != 0) return fail("rg_wrap: args.lay is not rg_wrap_layout(args.dims)");
+  if (a.B < 1 || !a.fstate || !a.istate || !a.n || !a.u) return fail("rg_wrap: B, the state rows and the draw blocks u, n are required");
+  const int rnd = a.dims.randomize != 0;
+  if (rnd && (!a.prm || !a.qpos || !a.hand_q || !a.pos_to_ctrl)) return fail("rg_wrap: randomize needs prm, qpos, hand_q and pos_to_ctrl");
+  if (!post) {
+    if (!a.action_index || !a.bins || a.nbins < 1 || !a.action_out) return fail("rg_wrap_pre_step: action_index, bins and action_out are required");
+    if (a.fixed_wrist && (!a.qpos || a.wrist_act < 0 || a.wrist_act >= a.dims.nu)) return fail("rg_wrap_pre_step: fixed_wrist needs qpos and a wrist actuator below nu");
+    return 0;
+  }
+  if (!a.obs || !a.goal_quat || !a.qpos_goal || !a.is_goal_achieved || !a.env_reward || !a.env_done || !a.successes_so_far || !a.out || !a.reward_out || !a.done_out ||
+      !a.fell_out || !a.info_out) return fail("rg_wrap_post_step: a required array is NULL");
+  if (a.obs_stride < 7 + a.dims.nq + a.dims.nv + a.dims.nh + a.dims.ntip) return fail("rg_wrap_post_step: obs_stride is shorter than the observation row of dims");
+  if (rnd && a.n_occ > 0 && (a.n_occ > 5 || !a.contact || !a.ncon || a.ncon_slots < 0 || a.contact_stride < 3 * a.ncon_slots)) return fail("rg_wrap_post_step: the occlusion check needs contact, ncon and at most 5 geoms");
+  return 0;
+}
+int rg_wrap_pre_step(const rg_wrap_args* args, void* stream) {
+  if (rg_wrap_check(args, false) != 0) return -1;
+  DeviceGuard g(args->device);
+  return launch(rg_wrap_pre_kernel, args->B, RG_WAVE, 0, 0, stream, *args);
+}
+int rg_wrap_post_step(const rg_wrap_args* args, void* stream) {
+  if (rg_wrap_check(args, true) != 0) return -1;
+  DeviceGuard g(args->device);
+  return launch(rg_wrap_post_kernel, args->B, RG_WAVE, 0, 0, stream, *args);
 }
 
 int rg_batch_set_constants(rg_batch* b, const int* mask_dev, void* stream) {

@@ -23,6 +23,8 @@ snapshot CubeFriction takes BEFORE RobotFriction draws in the same reset; Random
 timestep in place across a reset; Wind's hit probability is computed from whatever timestep is current at reset;
 RandomizedActionLatency's history shift aliases itself, so the delayed action always equals the current one.
 """
+import ctypes
+import types
 from collections import OrderedDict
 from typing import Dict, Optional
 
@@ -72,6 +74,12 @@ class TorchDraws:
         # ("e": -log(1 - u) of the same block, for `exponential` -- a draw takes ITS columns of one of the two, so no number is used twice)
         self._pool = {"u": [u, 0], "e": [torch.log1p(-u).neg_(), 0],
                       "n": [torch.randn((self.B, self.N_POOL), generator=self.gen, device=self.device), 0]}
+
+    def step_blocks(self):
+        """The two blocks of `begin_step`, drawn in the same generator order, for a consumer that reads them by column itself (the fused stack's two kernels):
+        (u [B, 32], n [B, 128], e or None -- None: the consumer forms -log1p(-u) of the columns it needs)."""
+        u = torch.rand((self.B, self.U_POOL), generator=self.gen, device=self.device)
+        return u, torch.randn((self.B, self.N_POOL), generator=self.gen, device=self.device), None
 
     def end_step(self):
         self._pool = {}
@@ -128,9 +136,19 @@ def _bmask(mask, t):
 class BatchedDactylCubeWrappers:
     def __init__(self, env, randomize: bool = False, n_action_bins: Optional[int] = None, relative_goal_wrapper: bool = True, drop_reward: float = -20.0,
                  min_episode_length: int = -1, noise_levels: Optional[dict] = None, smooth_alpha: float = 0.0, clip: float = 100.0, fixed_wrist: bool = False,
-                 draws=None, auto_reset: bool = False):
+                 draws=None, auto_reset: bool = False, fused: bool = False):
         self.fixed_wrist = bool(fixed_wrist)
         self.env = env
+        # fused: `step` is two HIP launches around env.step (rg_wrap_pre_step / rg_wrap_post_step, csrc/rg_wrap_kernel.h) instead of ~190 tensor kernels; the per-env
+        # wrapper state then lives in two rows those kernels own, and `reset` (still the tensor code below) writes its results into them
+        self.fused = bool(fused)
+        if self.fused and (auto_reset or getattr(env, "pipelined_reset", False)):
+            raise ValueError("fused=True cannot be combined with auto_reset / pipelined_reset: the fused kernels cover the step of the synchronous-reset stack only")
+        if self.fused and hasattr(env, "relative_goal"):
+            raise NotImplementedError("fused=True around the full cube: rg_wrap_post_kernel has LockedParallelGoal's relative goal and no face angles")
+        if self.fused and noise_levels is not None and sorted(noise_levels) != sorted(NO_NOISE_LEVELS):
+            raise ValueError("fused=True needs noise_levels for exactly %s" % sorted(NO_NOISE_LEVELS))
+        self._fz = None
         self.unwrapped = env
         self.randomize = bool(randomize)
         # auto_reset: around an env with `pipelined_reset=True` — a finished episode restarts by itself inside the following steps, and
@@ -560,6 +578,8 @@ class BatchedDactylCubeWrappers:
         self._episode_start(mask)
         out = self._observation(obs, torch.zeros((B, self.nu), device=dev), torch.zeros((B, 2), device=dev), at_reset=mask)
         self._action_noise_reset(mask)
+        if self.fused:
+            self._fused_push(obs)
         return out
 
     def _episode_start(self, mask, deltas=None):
@@ -584,6 +604,8 @@ class BatchedDactylCubeWrappers:
     def step(self, action: torch.Tensor):
         """action: int64 [B, nu] bin indices in [0, n_action_bins).  Returns (obs dict, reward [B, 4] = env, goal, success, drop,
         done [B], info)."""
+        if self.fused:
+            return self._step_fused(action)
         if hasattr(self.draws, "begin_step"):
             self.draws.begin_step()
         a = self._bins[torch.as_tensor(action, device=self.device).long()]              # DiscretizeActionWrapper.action
@@ -664,3 +686,179 @@ class BatchedDactylCubeWrappers:
         if hasattr(self.draws, "end_step"):
             self.draws.end_step()
         return out, reward, done, info
+
+    # ================================================================== fused=True: the step as two HIP launches (csrc/rg_wrap_kernel.h)
+    _CF_SLOTS = {"noisy_relative_goal_pos": 0, "noisy_relative_goal_quat": 3, "noisy_achieved_goal_pos": 7, "noisy_achieved_goal_quat": 10, "noisy_cube_pos": 14}
+    _ENV_ROW_KEYS = ("cube_pos", "cube_quat", "qpos", "qvel", "hand_angle", "fingertip_pos")
+
+    def _fused_setup(self, obs):
+        """Once, after the first reset (every width is known by then): the state rows, the kernels' argument struct with everything that does not change
+        from step to step, and the column views' table."""
+        F = types.SimpleNamespace()
+        env, B, dev = self.env, self.B, self.device
+        sim = env.mujoco_simulation
+        F.L = getattr(sim, "_L", None) or _native.lib()
+        F.native = hasattr(env, "_obs_buf")        # BatchedLockedEnv: its own fp32 buffers are read in place; any other env: fp32 staging copies per step
+        a = F.a = _native.WrapArgs()
+        d = a.dims
+        d.nq, d.nv, d.nh, d.ntip = (int(obs[k].shape[1]) for k in ("qpos", "qvel", "hand_angle", "fingertip_pos"))
+        d.nu = self.nu
+        d.randomize, d.relative_goal = int(self.randomize), int(bool(self.relative_goal_wrapper))
+        F.delta = [(k, int(v.shape[1])) for k, v in self._obs_delta.items()] if self.randomize else []
+        d.ndelta = sum(n for _, n in F.delta)
+        _native.check(F.L, F.L.rg_wrap_layout(ctypes.byref(d), ctypes.byref(a.lay)), "rg_wrap_layout")
+        L = a.lay
+        F.frow = torch.zeros((B, L.fwidth), dtype=torch.float32, device=dev)
+        F.irow = torch.zeros((B, L.iwidth), dtype=torch.int32, device=dev)
+        F.act_out = torch.zeros((B, self.nu), dtype=torch.float32, device=dev)
+        a.B, a.device = B, (dev.index or 0)
+        a.fstate, a.istate, a.action_out = F.frow.data_ptr(), F.irow.data_ptr(), F.act_out.data_ptr()
+        F.bins = self._bins.to(torch.float32).contiguous()
+        a.bins, a.nbins = F.bins.data_ptr(), self.n_action_bins
+        a.nsubsteps, a.cube_body_z, a.fall_z = self._nsub, float(self._cube_center_z0), 0.04
+        a.drop_reward, a.clip, a.min_episode_length = self.drop_reward, self.clip, self.min_episode_length
+        for i, key in enumerate(sorted(NO_NOISE_LEVELS)):
+            a.unc[i] = float(self.levels[key].get("uncorrelated", 0.0))
+        if self.fixed_wrist:
+            m = sim.model
+            a.fixed_wrist, a.wrist_act = 1, m.names["actuator"].index("robot0:A_WRJ0")
+            a.wrist_qadr = int(m.arrays["jnt_qposadr"][m.names["joint"].index("robot0:WRJ0")])
+            a.wrist_lo, a.wrist_hi = (float(v) for v in m.arrays["actuator_ctrlrange"][a.wrist_act])
+        if self.randomize:
+            F.hand_q = self._hand_q.to(torch.int32).contiguous()
+            F.p2c = self._pos_to_ctrl.to(torch.float32).contiguous()
+            a.hand_q, a.pos_to_ctrl, a.relative_action = F.hand_q.data_ptr(), F.p2c.data_ptr(), int(bool(env.constants.relative_action))
+            a.timestep0, a.occ_cutoff, a.ff_p, a.cf_p, a.freeze_scale = self._timestep0, OCCLUSION_DIST_CUTOFF, self._ff_p, self._cf_p, self._freeze_scale
+            occ = self._idx["occlusion"]
+            a.n_occ = 0 if occ is None else len(occ)
+            for i, g in enumerate([] if occ is None else occ.tolist()):
+                a.occ_geom[i] = float(g)
+        if F.native:
+            a.obs, a.obs_stride = env._obs_buf.data_ptr(), env._obs_buf.shape[1]
+            a.goal_pos, a.goal_quat, a.qpos_goal, a.is_goal_achieved = env._goal_pos.data_ptr(), env._goal_quat.data_ptr(), env._qpos_goal.data_ptr(), env._is_successful.data_ptr()
+            q = sim.view(_native.RG_F_QPOS)
+            a.qpos, a.qpos_stride = q.data_ptr(), q.shape[1]
+            if self.randomize:
+                lay = _native.prm_layout(F.L)
+                rows = self._P.rows
+                a.prm, a.prm_stride = rows.data_ptr(), rows.shape[1]
+                a.p_ctrlrange, a.p_timestep = lay["actuator_ctrlrange"], lay["timestep"]
+                a.p_xfrc_cube, a.p_mass_cube = lay["xfrc_applied"] + 6 * self._cube_body, lay["body_mass"] + self._cube_body
+                if a.n_occ:
+                    data = sim.data            # (switches the contact readout on, as the tensor stack's first step does)
+                    a.contact, a.ncon = data._contact.data_ptr(), data._ncon.data_ptr()
+                    a.contact_stride = a.ncon_stride = sim._xdata.shape[1]
+                    a.ncon_slots = data._contact.shape[1]
+        elif self.randomize:
+            F.prm = torch.zeros((B, 2 * self.nu + 5), dtype=torch.float32, device=dev)      # staging row: actuator_ctrlrange | timestep | cube xfrc_applied[:3] | cube body_mass
+            a.prm, a.prm_stride = F.prm.data_ptr(), F.prm.shape[1]
+            a.p_ctrlrange, a.p_timestep, a.p_xfrc_cube, a.p_mass_cube = 0, 2 * self.nu, 2 * self.nu + 1, 2 * self.nu + 4
+        # the packed row's column views: (key, first column, one past the last)
+        offs = sorted((L.key[i], name) for i, name in enumerate(_native.RG_WRAP_KEYS) if L.key[i] >= 0)
+        F.columns = []
+        for (lo, name), (hi, _) in zip(offs, offs[1:] + [(L.W, None)]):
+            if name != "_delta":
+                F.columns.append((name, lo, hi))
+            else:
+                for key, n in F.delta:
+                    F.columns.append((key, lo, lo + n))
+                    lo += n
+        F.keep = []
+        self._fz = F
+
+    def _fused_push(self, obs):
+        """After the tensor `reset`: its results go into the state rows, and the attributes it works on become views of those rows -- so the next `reset(mask)` reads
+        the state the kernels left, merges the masked envs' new values in, and the other envs' rows are rewritten with their own values."""
+        if self._fz is None:
+            self._fused_setup(obs)
+        F, B, nu = self._fz, self.B, self.nu
+        L, fr, ir = F.a.lay, F.frow, F.irow
+
+        def put(row, off, t):
+            t = t.reshape(B, -1)
+            dst = row[:, off:off + t.shape[1]]
+            if dst.data_ptr() != t.data_ptr():
+                dst.copy_(t)
+            return dst
+
+        self._previous_action, self._ema_value = put(fr, L.s_prev, self._previous_action), put(fr, L.s_ema, self._ema_value)
+        self._ema_alpha = put(fr, L.s_alpha, self._ema_alpha)[:, 0]
+        fr[:, L.s_aema:L.s_aema + nu] = 0.0            # (every env's: a reset returns zeros for action_ema, the next step overwrites it before it is read)
+        self._ema_t, self._steps = put(ir, L.i_emat, self._ema_t)[:, 0], put(ir, L.i_steps, self._steps)[:, 0]
+        self._drops_so_far, self._first_drop = put(ir, L.i_drops, self._drops_so_far)[:, 0], put(ir, L.i_first, self._first_drop)[:, 0]
+        at = 0
+        for key in sorted(self.levels):
+            n = self._key_len[key]
+            self._additive_bias[key] = put(fr, L.s_addb + at, self._additive_bias[key])
+            self._multiplicative_bias[key] = put(fr, L.s_mulb + at, self._multiplicative_bias[key])
+            at += n
+        if not self.randomize:
+            return
+        self._action_history = put(fr, L.s_hist, self._action_history[:, 0])[:, None, :].expand(B, 2, nu)
+        self._slack, self._coef_down, self._coef_up = put(fr, L.s_slack, self._slack), put(fr, L.s_cdown, self._coef_down), put(fr, L.s_cup, self._coef_up)
+        self._an_mult, self._an_add = put(fr, L.s_anmult, self._an_mult), put(fr, L.s_anadd, self._an_add)
+        self._action_delay = put(ir, L.i_delay, self._action_delay)
+        for i, k in enumerate(("pos_lambda", "neg_lambda", "side", "p_flip_pos", "p_flip_neg")):
+            self._ts[k] = put(fr, L.s_ts + i, self._ts[k])[:, 0]
+        self._wind_hit_prob = put(fr, L.s_wind, self._wind_hit_prob)[:, 0]
+        self._occl_buf, self._ff_buf = put(fr, L.s_occl, self._occl_buf), put(fr, L.s_ffbuf, self._ff_buf)
+        self._ff_left, self._cf_left = put(fr, L.s_ffleft, self._ff_left), put(fr, L.s_cfleft, self._cf_left)[:, 0]
+        for k in self._cf_buf:
+            self._cf_buf[k] = put(fr, L.s_cfbuf + self._CF_SLOTS[k], self._cf_buf[k])
+        at = L.s_delta
+        for key, n in F.delta:
+            self._obs_delta[key] = put(fr, at, self._obs_delta[key])
+            at += n
+
+    def _step_fused(self, action):
+        F = self._fz
+        if F is None:
+            raise RuntimeError("call reset() before step()")
+        a, env, B, dev = F.a, self.env, self.B, self.device
+        sim = env.mujoco_simulation
+        f32 = lambda t: t.to(torch.float32).contiguous()
+        u, n, e = self.draws.step_blocks()
+        u, n, e = f32(u), f32(n), None if e is None else f32(e)
+        action = torch.as_tensor(action, device=dev).to(torch.int64).contiguous()
+        a.u, a.n, a.e, a.action_index = u.data_ptr(), n.data_ptr(), None if e is None else e.data_ptr(), action.data_ptr()
+        stream = None if dev.type == "cpu" else ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stage = []
+        if not F.native:
+            if self.randomize or self.fixed_wrist:
+                stage.append(f32(sim.qpos))
+                a.qpos, a.qpos_stride = stage[-1].data_ptr(), stage[-1].shape[1]
+            if self.randomize:
+                P, nu = self._P, self.nu
+                F.prm[:, :2 * nu] = P["actuator_ctrlrange"].reshape(B, -1)
+                F.prm[:, 2 * nu] = P["timestep"][:, 0]
+                F.prm[:, 2 * nu + 1:2 * nu + 4] = P["xfrc_applied"][:, self._cube_body, :3]
+                F.prm[:, 2 * nu + 4] = P["body_mass"][:, self._cube_body]
+        _native.check(F.L, F.L.rg_wrap_pre_step(ctypes.byref(a), stream), "rg_wrap_pre_step")
+        obs, rew, done, info = env.step(F.act_out)
+        if not F.native:
+            stage += [f32(torch.cat([obs[k].reshape(B, -1) for k in self._ENV_ROW_KEYS], dim=1)), f32(obs["goal_pos"]), f32(obs["goal_quat"]), f32(obs["qpos_goal"]),
+                      obs["is_goal_achieved"].reshape(B).to(torch.int32).contiguous()]
+            a.obs, a.obs_stride = stage[-5].data_ptr(), stage[-5].shape[1]
+            a.goal_pos, a.goal_quat, a.qpos_goal, a.is_goal_achieved = (t.data_ptr() for t in stage[-4:])
+            if self.randomize and a.n_occ:
+                g1, g2, dist = sim.data.contact
+                stage += [f32(torch.stack([g1.to(torch.float32), g2.to(torch.float32), dist.to(torch.float32)], dim=-1)), f32(sim.data.ncon)]
+                a.contact, a.contact_stride, a.ncon_slots, a.ncon, a.ncon_stride = stage[-2].data_ptr(), 3 * g1.shape[1], g1.shape[1], stage[-1].data_ptr(), 1
+        rew, done, succ = f32(rew), done.to(torch.bool).contiguous(), info["successes_so_far"].to(torch.int32).contiguous()
+        a.env_reward, a.env_done, a.successes_so_far = rew.data_ptr(), done.data_ptr(), succ.data_ptr()
+        out = torch.empty((B, a.lay.W), dtype=torch.float32, device=dev)
+        reward = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        flags = torch.empty((2, B), dtype=torch.bool, device=dev)
+        ints = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        a.out, a.reward_out, a.done_out, a.fell_out, a.info_out = out.data_ptr(), reward.data_ptr(), flags[0].data_ptr(), flags[1].data_ptr(), ints.data_ptr()
+        _native.check(F.L, F.L.rg_wrap_post_step(ctypes.byref(a), stream), "rg_wrap_post_step")
+        if not F.native and self.randomize:      # the staging row's two written fields go back to the env's own parameter tensors
+            P, nu = self._P, self.nu
+            P["timestep"][:, 0] = F.prm[:, 2 * nu]
+            P["xfrc_applied"][:, self._cube_body, :3] = F.prm[:, 2 * nu + 1:2 * nu + 4]
+        F.keep.append((u, n, e, action, stage, rew, done, succ))      # the launches are asynchronous: their operands outlive a few calls
+        del F.keep[:-4]
+        o = OrderedDict((name, out[:, lo:hi]) for name, lo, hi in F.columns)
+        info = dict(info)
+        info.update({"fell_down": flags[1], "drops_so_far": ints[:, 0], "first_drop": ints[:, 1]})
+        return o, reward, flags[0], info
