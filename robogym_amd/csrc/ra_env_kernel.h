@@ -230,26 +230,17 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
     const float gdr = (a.prev_valid[e] && !crash) ? (reach ? a.prev_nsucc[e] - gscore : gscore - a.prev_nsucc[e]) : 0.f;
     a.prev_nsucc[e] = gscore; a.prev_valid[e] = 1;
     const int succ = !crash && nsucc == N;
-    // ---- MultiGoalTracker.process (multi_goal_tracker.py:157-241)
-    a.steps[e] += 1;
-    int ssl = a.steps_since_last_goal[e] + 1;
-    const int cons = succ ? a.consecutive[e] + 1 : 0;
-    const int got = cons >= 1;
-    if (got) a.successes_so_far[e] += 1;
-    const int timeout = !got && ssl >= a.max_timesteps_per_goal;
-    const int trial = got && a.successes_so_far[e] >= a.successes_needed;
-    if (trial) ssl = 0;
-    const int newgoal = got && !trial;
-    if (newgoal) { ssl = 0; a.prev_valid[e] = 0; }          // reset_goal: reset_goal_steps, _previous_goal_distance = None (robot_env.py:893-909)
-    a.steps_since_last_goal[e] = ssl; a.consecutive[e] = cons;
+    EnvTracked tk = env_tracker_process(e, a.steps, a.steps_since_last_goal, a.successes_so_far, a.consecutive, a.max_timesteps_per_goal, a.successes_needed, succ);
+    // reset_goal's reset_goal_steps and _previous_goal_distance = None (robot_env.py:893-909) inline: the goal itself comes from ra_recipe_kernel or the host
+    if (tk.newgoal) { tk.ssl = 0; a.steps_since_last_goal[e] = 0; a.prev_valid[e] = 0; }
     float* rw = a.reward + 3 * (size_t)e;
-    rw[0] = env_reward; rw[1] = a.use_goal_distance_reward ? gdr : 0.f; rw[2] = got ? a.success_reward : 0.f;
+    rw[0] = env_reward; rw[1] = a.use_goal_distance_reward ? gdr : 0.f; rw[2] = tk.got ? a.success_reward : 0.f;
     if (a.reward_clip > 0.f) for (int k = 0; k < 3; k++) rw[k] = fminf(fmaxf(rw[k], -a.reward_clip), a.reward_clip);   // ClipRewardWrapper
     a.goal_dist[2 * e] = sp; a.goal_dist[2 * e + 1] = sr;
     if (a.goal_kind == 2) { a.goal_dist_extra[2 * e] = dgrip; a.goal_dist_extra[2 * e + 1] = grasp; }
-    done = done || timeout || trial || crash;
-    a.done[e] = done; a.goal_reset[e] = newgoal; a.trial_success[e] = trial; a.sub_goal_ok[e] = got; a.env_crash[e] = crash;
-    a.objects_off_table[e] = any_off; a.info_ssl[e] = ssl;
+    done = done || tk.timeout || tk.trial || crash;
+    a.done[e] = done; a.goal_reset[e] = tk.newgoal; a.trial_success[e] = tk.trial; a.sub_goal_ok[e] = tk.got; a.env_crash[e] = crash;
+    a.objects_off_table[e] = any_off; a.info_ssl[e] = tk.ssl;
     const int g0 = 15 * N + 15 + 2 * nq;
     row[g0 + 6 * N] = (float)succ;                          // is_goal_achieved
     float* o = row + g0 + 21 * N + 1;
@@ -278,7 +269,7 @@ struct RaRecipeLds { int started, ended, regoal, moved; float pos[RA_MAXOBJ][3],
 // sampling ran out of restarts (out = its last proposal).  `k`: this env's running draw index.  `no_grid`: place_objects_with_no_constraint even where the grid
 // has cells enough (the stack and reach goals' own placement).
 __device__ inline bool ra_place(const RaRecipeArgs& a, int N, bool no_grid, const float* yaw, int ystride, unsigned seed, unsigned step, unsigned e, unsigned& k, float (*out)[3]) {
-  auto U = [&]() -> float { return (float)(rbp_hash(seed, step, e, k++) >> 8) * (1.0f / 16777216.0f); };
+  auto U = [&]() -> float { return env_u01(seed, step, e, k++); };
   float hx[RA_MAXOBJ], hy[RA_MAXOBJ], xy[RA_MAXOBJ][2];
   float mx = 0.f, my = 0.f;
   for (int i = 0; i < N; i++) {      // rotate_bounding_box
@@ -346,7 +337,7 @@ __device__ inline bool ra_place(const RaRecipeArgs& a, int N, bool no_grid, cons
 // out (out = the last proposals).
 __device__ inline bool ra_place_near(const RaRecipeArgs& a, int N, const float* yaw, int ystride, const float* qrow, float ratio_in, unsigned seed, unsigned step, unsigned e, unsigned& k,
                                      float (*out)[3]) {
-  auto U = [&]() -> float { return (float)(rbp_hash(seed, step, e, k++) >> 8) * (1.0f / 16777216.0f); };
+  auto U = [&]() -> float { return env_u01(seed, step, e, k++); };
   float hx[RA_MAXOBJ], hy[RA_MAXOBJ], cx[RA_MAXOBJ], cy[RA_MAXOBJ], px[RA_MAXOBJ], py[RA_MAXOBJ];
   const float width = a.area_size[0], height = a.area_size[1];
   for (int i = 0; i < N; i++) {
@@ -399,7 +390,7 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
     int st = a.stage[e], lf = a.left[e];
     int started = 0, ended = 0, regoal = 0, stabilised = 0;
     unsigned k = 0;
-    auto U = [&]() -> float { return (float)(rbp_hash(a.seed, a.step, (unsigned)e, k++) >> 8) * (1.0f / 16777216.0f); };
+    auto U = [&]() -> float { return env_u01(a.seed, a.step, (unsigned)e, k++); };
     a.episode_started[e] = 0;
     // ---- an env inside the recipe: this step counted
     if (st > 0) {
@@ -434,7 +425,7 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
     if (gy) {
       k = 0u;     // (the goal's placement draws from its own stream: an env can get a new goal and end its episode on the same step)
       const unsigned gseed = a.seed ^ 0x9E3779B9u;
-      auto UG = [&]() -> float { return (float)(rbp_hash(gseed, a.step, (unsigned)e, k++) >> 8) * (1.0f / 16777216.0f); };
+      auto UG = [&]() -> float { return env_u01(gseed, a.step, (unsigned)e, k++); };
       const int kind = a.goal_kind;
       F.moved = 0;
       if (kind <= 1) {
@@ -495,7 +486,7 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
         // the placement's draws however often that restarts
         k = 3000u;
         const unsigned grseed = a.seed ^ 0x85EBCA6Bu;
-        auto UR = [&]() -> float { return (float)(rbp_hash(grseed, a.step, (unsigned)e, k++) >> 8) * (1.0f / 16777216.0f); };
+        auto UR = [&]() -> float { return env_u01(grseed, a.step, (unsigned)e, k++); };
         int* grow = a.obj_group + (size_t)e * N;
         for (int first = 0, g = 0; first < N; g++) {
           const int rem = N - first;
@@ -584,7 +575,7 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
       const float c = fabsf(cosf(yw[lane])), s_ = fabsf(sinf(yw[lane]));
       float* so = a.static_obs + ((size_t)e * N + lane) * 7;
       so[0] = c * a.obj_half[lane][0] + s_ * a.obj_half[lane][1]; so[1] = s_ * a.obj_half[lane][0] + c * a.obj_half[lane][1]; so[2] = a.obj_half[lane][2];
-      for (int q = 0; q < 3; q++) so[3 + q] = (float)(rbp_hash(a.seed, a.step, (unsigned)e, 500u + 3u * lane + q) >> 8) * (1.0f / 16777216.0f);
+      for (int q = 0; q < 3; q++) so[3 + q] = env_u01(a.seed, a.step, (unsigned)e, 500u + 3u * lane + q);
       so[6] = 1.f;
     }
   }

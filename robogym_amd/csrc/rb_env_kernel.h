@@ -21,6 +21,7 @@
 // fp32 throughout; the gimbal-lock test of mat2euler uses 4 x FLT_EPSILON where the reference (float64) uses 4 x DBL_EPSILON.
 #pragma once
 #include "rb_types.h"
+#include "rg_env_common.h"
 
 namespace rgb {
 
@@ -150,14 +151,6 @@ __global__ void __launch_bounds__(64) rb_cube_ops_kernel(RbBatchDev bt, int nq, 
   for (int i = lane; i < RBC_BLOCK; i += 64) q[i] = c[i];
 }
 
-// counter-based generator (as rg_env_kernel.h)
-__device__ __forceinline__ unsigned rbp_hash(unsigned a, unsigned b, unsigned c, unsigned d) {
-  unsigned h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA77u;
-  h ^= h >> 15; h *= 0xC2B2AE3Du; h ^= (c + 0x165667B1u) * 0x27D4EB2Fu; h ^= h >> 13; h *= 0x9E3779B1u;
-  h ^= (d + 0xD6E8FEB8u) * 0x85EBCA77u; h ^= h >> 16; h *= 0xC2B2AE3Du; h ^= h >> 15; h *= 0x27D4EB2Fu; h ^= h >> 13;
-  return h;
-}
-
 struct RbPostLds {
   float c[RBC_BLOCK + 2];
   float gq[4], gf[6], delta;
@@ -191,14 +184,15 @@ __global__ void __launch_bounds__(64) rb_post_step_kernel(const RbModelDev* mp, 
   float* qrow = bt.qpos + (size_t)e * nq;
   const float* S = bt.scratch + (size_t)e * m.scratch_words;
   float* g = a.goal + (size_t)e * RB_GOAL_WORDS;
-  auto U = [&](int k) -> float { return a.draws ? a.draws[(size_t)e * RB_POST_NDRAW + k] : (float)(rbp_hash(a.seed, a.step, (unsigned)e, (unsigned)k) >> 8) * (1.0f / 16777216.0f); };
+  auto U = [&](int k) -> float { return a.draws ? a.draws[(size_t)e * RB_POST_NDRAW + k] : env_u01(a.seed, a.step, (unsigned)e, (unsigned)k); };
   if (lane == 0) {
     const int crash = (bt.status[e] & RG_STATUS_BAD_STATE) != 0;
     float quat[4], face[6], dist[2] = {0.f, 0.f};
     for (int k = 0; k < 4; k++) quat[k] = qrow[a.cube_quat_col + k];
     for (int k = 0; k < 6; k++) face[k] = qrow[a.cube_block_col + k];
     if (!crash) rbp_goal_distance(g, quat, face, dist, a.goal_mode);
-    int got = 0, trial = 0, timeout = 0, newgoal = forced, succ = 0;
+    EnvTracked tk = {0, 0, 0, 0, 0};
+    int newgoal = forced, succ = 0;
     const int ph0 = (a.pipelined && !forced) ? a.phase[e] : 0;
     const int resetting = ph0 > 0, live = !resetting;
     int done = 0;
@@ -214,49 +208,29 @@ __global__ void __launch_bounds__(64) rb_post_step_kernel(const RbModelDev* mp, 
       if (a.prev_valid[e] && !crash) gdr = (a.prev_dist[2 * e] - dist[0]) + (a.prev_dist[2 * e + 1] - dist[1]);
       a.prev_dist[2 * e] = dist[0]; a.prev_dist[2 * e + 1] = dist[1]; a.prev_valid[e] = 1;
       succ = !crash && dist[0] < a.quat_threshold && dist[1] < a.face_threshold;
-      // ---- MultiGoalTracker.process (multi_goal_tracker.py:157-241), dactyl settings
-      a.steps[e] += 1;
-      int ssl = a.steps_since_last_goal[e] + 1;
-      const int cons = succ ? a.consecutive[e] + 1 : 0;
-      got = cons >= 1;
-      if (got) a.successes_so_far[e] += 1;
-      timeout = !got && ssl >= a.max_timesteps_per_goal;
-      trial = got && a.successes_so_far[e] >= a.successes_needed;
-      if (trial) ssl = 0;
-      newgoal = got && !trial;
-      a.steps_since_last_goal[e] = ssl; a.consecutive[e] = cons;
+      tk = env_tracker_process(e, a.steps, a.steps_since_last_goal, a.successes_so_far, a.consecutive, a.max_timesteps_per_goal, a.successes_needed, succ);
+      newgoal = tk.newgoal;
       const int fallen = a.stop_on_fall && !crash && S[m.off[RB_O_SPOS] + 3 * a.center_site + 2] < 0.04f;   // cube_utils.on_palm
       float* rw = a.reward + 3 * (size_t)e;
-      rw[0] = 0.f; rw[1] = a.use_goal_distance_reward ? gdr : 0.f; rw[2] = got ? a.success_reward : 0.f;
+      rw[0] = 0.f; rw[1] = a.use_goal_distance_reward ? gdr : 0.f; rw[2] = tk.got ? a.success_reward : 0.f;
       a.goal_dist[2 * e] = dist[0]; a.goal_dist[2 * e + 1] = dist[1];
-      done = timeout || trial || crash || fallen;
+      done = tk.timeout || tk.trial || crash || fallen;
       a.done[e] = done;
-      a.trial_success[e] = trial; a.sub_goal_ok[e] = got; a.env_crash[e] = crash;
+      a.trial_success[e] = tk.trial; a.sub_goal_ok[e] = tk.got; a.env_crash[e] = crash;
     }
     // ---- reset recipe progression (pipelined mode)
     F.restart = 0; F.wiggle = 0;
     if (a.pipelined && !forced) {
-      const int ph = ph0 + resetting;
       const int n1 = a.reset_initial_steps, n2 = a.reset_initial_steps + a.n_random_initial_steps;
-      const int wiggle = resetting && ph == n1 + 1 && !crash;
-      const int finished = resetting && ph == n2 + 1 && !crash;
       const int on_palm = S[m.off[RB_O_SPOS] + 3 * a.center_site + 2] > 0.04f;      // (the launch's last forward is the one inside on_palm)
-      const int ok = finished && (on_palm || a.tries[e] + 1 >= a.max_pose_resets);
-      const int retry = (finished && !ok) || (crash && resetting);
-      const int start = done && live;
-      const int restart = retry || start;
-      a.tries[e] = start ? 0 : a.tries[e] + retry;
-      const int phase = restart ? 1 : (ok ? 0 : ph);
-      a.phase[e] = phase;
-      if (ok) {   // RobotEnv.reset tail (robot_env.py:787-792): tracker.reset, clock, then reset_goal below
-        a.steps[e] = 0; a.steps_since_last_goal[e] = 0; a.successes_so_far[e] = 0; a.goals_so_far[e] = 0; a.consecutive[e] = 0;
-        a.t[e] = 0; a.prev_valid[e] = 0;
-      }
-      newgoal = newgoal || ok;
-      a.resetting[e] = phase > 0; a.episode_started[e] = ok;
-      a.hold_next[e] = phase > 0;
-      a.nticks_next[e] = phase == 0 ? 3 : ((phase == n1 || phase == n2) ? 2 : 1);   // (the forwards after the state writes and inside on_palm: second ticks of recipe steps n1, n2)
-      F.restart = restart; F.wiggle = wiggle;
+      const EnvRecipeStep rs = env_recipe_advance(ph0, crash, on_palm, done, live, n1, n2, a.max_pose_resets, a.tries + e);
+      a.phase[e] = rs.phase;
+      if (rs.ok) env_episode_start(e, a.t, a.steps, a.steps_since_last_goal, a.successes_so_far, a.goals_so_far, a.consecutive, a.prev_valid);   // (then reset_goal below)
+      newgoal = newgoal || rs.ok;
+      a.resetting[e] = rs.phase > 0; a.episode_started[e] = rs.ok;
+      a.hold_next[e] = rs.phase > 0;
+      a.nticks_next[e] = env_nticks_next(rs.phase, n1, n2);
+      F.restart = rs.restart; F.wiggle = rs.wiggle;
     }
     int achieved = succ;
     F.rotate = 0; F.face = 0; F.delta = 0.f;
@@ -319,7 +293,7 @@ __global__ void __launch_bounds__(64) rb_post_step_kernel(const RbModelDev* mp, 
       g[10] = rotate ? 1.f : 0.f; g[11] = (float)axis; g[12] = asgn;
       F.rotate = rotate;
       // ---- reset_goal (robot_env.py:893-909): goal counters, _previous_goal_distance = None -> the re-observation sets it to the current distance
-      a.goals_so_far[e] += 1; a.steps_since_last_goal[e] = 0; a.consecutive[e] = 0;
+      env_reset_goal_counters(e, a.goals_so_far, a.steps_since_last_goal, a.consecutive);
       float nd2[2] = {0.f, 0.f};
       if (!crash) rbp_goal_distance(g, quat, face, nd2, a.goal_mode);
       a.prev_dist[2 * e] = nd2[0]; a.prev_dist[2 * e + 1] = nd2[1]; a.prev_valid[e] = 1;
@@ -375,8 +349,8 @@ __global__ void __launch_bounds__(64) rb_post_step_kernel(const RbModelDev* mp, 
   if (a.pipelined && !forced) {
     const int nv = m.nv;
     auto RD = [&](int k) -> float { return a.reset_draws[(size_t)e * RB_RESET_NDRAW + k]; };
-    auto HU = [&](int k) -> float { return (float)(rbp_hash(a.seed ^ 0x5bd1e995u, a.step, (unsigned)e, (unsigned)k) >> 8) * (1.0f / 16777216.0f); };
-    auto HN = [&](int k) -> float { const float u1 = fmaxf(HU(200 + 2 * k), 1e-7f), u2 = HU(201 + 2 * k); return sqrtf(-2.0f * logf(u1)) * cosf(6.2831853f * u2); };
+    auto HU = [&](int k) -> float { return env_u01(a.seed ^ 0x5bd1e995u, a.step, (unsigned)e, (unsigned)k); };
+    auto HN = [&](int k) -> float { return env_normal(a.seed ^ 0x5bd1e995u, a.step, (unsigned)e, (unsigned)(200 + 2 * k), (unsigned)(201 + 2 * k)); };
     if (F.wiggle) {   // full_perpendicular.py:311-332 after the settling steps
       if (lane < 3) qrow[a.cube_pos_col + lane] += (a.reset_draws ? RD(lane) : HN(lane)) * a.wiggle_std;
       if (lane == 3) {   // rotation.uniform_quat: four normals, normalised, w >= 0
@@ -414,15 +388,14 @@ __global__ void __launch_bounds__(64) rb_post_step_kernel(const RbModelDev* mp, 
       for (int i = lane; i < RBC_BLOCK; i += 64) qrow[a.cube_block_col + i] = F.c[i];
       if (lane < nu) {   // the random action's ctrl, absolute (denormalize_position_control with its default relative_action = False)
         const float lo = a.ctrl_lo[lane], hi = a.ctrl_hi[lane], act = a.reset_draws ? RD(66 + lane) : 2.f * HU(80 + lane) - 1.f;
-        bt.ctrl[(size_t)e * nu + lane] = fminf(fmaxf(0.5f * (hi + lo) + act * 0.5f * (hi - lo), lo), hi);
+        bt.ctrl[(size_t)e * nu + lane] = env_ctrl_of_action(lo, hi, act);
       }
     }
     if (F.restart) {   // mujoco_simulation.reset() of this env + the recipe's first ctrl (zero action)
-      for (int i = lane; i < nq; i += 64) qrow[i] = a.qpos0[i];
-      for (int i = lane; i < nv; i += 64) { bt.qvel[(size_t)e * nv + i] = 0.f; bt.qacc_warmstart[(size_t)e * nv + i] = 0.f; }
-      for (int i = lane; i < 3 * nu; i += 64) bt.pid[(size_t)e * 3 * nu + i] = 0.f;
+      // mj_resetData also clears xfrc_applied: NOT done here -- with per-env parameter rows a wrench survives the episode boundary until the host rewrites it
+      // (whoever wires a per-step wind writer rewrites the row every step).  rg_post_step_kernel's restart does clear its env's row.
+      env_restart_rows(lane, qrow, a.qpos0, nq, bt.qvel + (size_t)e * nv, bt.qacc_warmstart + (size_t)e * nv, nv, bt.pid + (size_t)e * 3 * nu, nu, bt.time + e, bt.status + e);
       for (int u = lane; u < nu; u += 64) bt.ctrl[(size_t)e * nu + u] = 0.5f * (a.ctrl_lo[u] + a.ctrl_hi[u]);
-      if (lane == 0) { bt.time[e] = 0.f; bt.status[e] = 0; }
     }
   }
   // ---- goal part of the observation row (written last: a new goal of this step is part of it); a crashed env returns a zero row

@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from robogym_amd import _native
+from robogym_amd.envs.dactyl._cube_env import BatchedCubeEnvBase
 from robogym_amd.envs.dactyl.locked import FINGERTIP_SITE_NAMES, MODEL_DIR, REFERENCE_SITE_NAMES
 from robogym_amd.mujoco.large_simulation import LargeModelSimulation
 from robogym_amd.mujoco.mjcf_compiler import CompiledModel
@@ -283,7 +284,7 @@ class FullPerpendicularEnvConstants:
 _GOAL_MODES = {"face_free": 0, "full_unconstrained": 1, "face_curr": 2}
 
 
-class BatchedFullPerpendicularEnv:
+class BatchedFullPerpendicularEnv(BatchedCubeEnvBase):
     """B independent dactyl/full_perpendicular envs stepped in lock-step on one GPU (see the module docstring)."""
 
     def __init__(self, batch_size: int, device="cuda:0", constants: Optional[FullPerpendicularEnvConstants] = None, starting_seed: Optional[int] = None,
@@ -294,7 +295,6 @@ class BatchedFullPerpendicularEnv:
         `set_constants_on_reset` (needs the per-env rows): every reset recomputes the `_invweight0` rows of the envs it resets from their current rows before the
         recipe starts (`mujoco_simulation.set_constants()` in CubeEnv._reset, cube_env.py:346-349; `sim.set_constants(mask)`, rb_setconst_kernel).  Off (the default):
         the rows stay what the caller left there.  Not available with `pipelined_reset=True`, whose episode restarts happen inside the step launches."""
-        from robogym_amd.utils.multi_goal_tracker import BatchedMultiGoalTracker
         from robogym_amd.utils.rotation import parallel_quats_np
 
         self.constants = c = constants or FullPerpendicularEnvConstants()
@@ -316,14 +316,11 @@ class BatchedFullPerpendicularEnv:
         self.batch_size, self.device, self.num_actions = sim.batch_size, sim.device, sim.nu
         B, dev = self.batch_size, self.device
         f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
         self.n_hand = len(sim.qpos_idxs["hand_angle"])
         self.obs_dim = 13 + self.n_hand + 15 + 13
-        self._obs_buf, self._goal, self._reward, self._goal_dist, self._prev_dist = f32(B, self.obs_dim), f32(B, _native.RB_GOAL_WORDS), f32(B, 3), f32(B, 2), f32(B, 2)
+        self._obs_buf, self._goal, self._goal_dist, self._prev_dist = f32(B, self.obs_dim), f32(B, _native.RB_GOAL_WORDS), f32(B, 2), f32(B, 2)
         self._goal[:, 0] = 1
-        self._prev_valid, self._is_successful, self._info_ssl, self.t = i32(B), i32(B), i32(B), i32(B)
-        self._flags = {k: torch.zeros(B, dtype=torch.bool, device=dev) for k in ("done", "goal_reset", "trial_success", "sub_goal_ok", "env_crash")}
-        self.multi_goal_tracker = BatchedMultiGoalTracker(B, dev, c.max_timesteps_per_goal, c.success_reward, c.successes_needed, c.use_goal_distance_reward)
+        self._alloc_episode_buffers()
         self.face_up_quats_np = face_up_quats(self.model, parallel_quats_np())
         self._face_up_quats = torch.tensor(self.face_up_quats_np, dtype=torch.float32, device=dev).contiguous()
         self._qpos0_rows = torch.tensor(np.asarray(self.model.arrays["qpos0"]), dtype=torch.float32, device=dev).repeat(B, 1)
@@ -334,14 +331,10 @@ class BatchedFullPerpendicularEnv:
         # counter in rb_post_step_kernel, include/rgstep.h) -- the other envs never wait for a reset.  Off: `done` envs are the caller's to
         # `reset(mask)` (reference API)
         self.pipelined_reset = bool(pipelined_reset)
-        self._phase, self._tries, self._hold = i32(B), i32(B), i32(B)
-        self._nticks = torch.full((B,), 3, dtype=torch.int32, device=dev)
-        self._flags.update({k: torch.zeros(B, dtype=torch.bool, device=dev) for k in ("resetting", "episode_started")})
+        self._hold = torch.zeros(B, dtype=torch.int32, device=dev)
         self._pipe_draws = None      # test hook: [B, RB_RESET_NDRAW] draws of the in-step recipe instead of the hash generator
         self._draws = None
         self._reset_draws = None
-        self._step_count = 0
-        self._needs_reset = True
         self._trace = None            # test hook: a list that receives qpos after the recipe's settling steps and after its state writes
         self._physics_events = None   # bench hook: a (start, end) pair of torch.cuda.Event recorded around the physics launch of `step`
         self.seed(starting_seed)
@@ -451,37 +444,28 @@ class BatchedFullPerpendicularEnv:
 
     # ------------------------------------------------------------------ step
     def _post(self, force=None):
-        sim, c, tr, F = self.mujoco_simulation, self.constants, self.multi_goal_tracker, self._flags
+        sim, c = self.mujoco_simulation, self.constants
         a = _native.RbPostArgs()
         P = lambda t: t.data_ptr()
+        self._fill_episode_args(a)
         a.obs, a.obs_dim = P(self._obs_buf), self.obs_dim
-        a.t, a.steps, a.steps_since_last_goal, a.successes_so_far = P(self.t), P(tr.steps), P(tr.steps_since_last_goal), P(tr.successes_so_far)
-        a.goals_so_far, a.consecutive = P(tr.goals_so_far), P(tr.consecutive_success)
-        a.prev_dist, a.prev_valid, a.is_successful, a.goal, a.reward, a.goal_dist = P(self._prev_dist), P(self._prev_valid), P(self._is_successful), P(self._goal), P(self._reward), P(self._goal_dist)
-        for k, t in F.items():
-            setattr(a, k, P(t))
-        a.info_ssl = P(self._info_ssl)
+        a.prev_dist, a.goal, a.goal_dist = P(self._prev_dist), P(self._goal), P(self._goal_dist)
         a.force_new_goal = None if force is None else P(force)
         a.draws = None if self._draws is None else P(self._draws)
-        a.seed, a.step = self._seed & 0xFFFFFFFF, self._step_count & 0xFFFFFFFF
         a.cube_tab, a.face_up_quats = P(sim.cube_tab), P(self._face_up_quats)
         a.face_geom = (ctypes.c_int * 6)(*sim.face_geoms); a.tip_site = (ctypes.c_int * 5)(*sim.tip_sites); a.ref_site = (ctypes.c_int * 3)(*sim.ref_sites)
         a.center_site = sim.center_site
         a.cube_pos_col, a.cube_quat_col = int(sim.qpos_idxs["cube_position"][0]), int(sim.qpos_idxs["cube_rotation"][0])
         a.cube_block_col, a.target_block_col, a.hand_col, a.n_hand = sim.cube_col, sim.target_col, int(sim.qpos_idxs["hand_angle"][0]), self.n_hand
         a.quat_threshold, a.face_threshold = float(c.success_threshold["cube_quat"]), float(c.success_threshold["cube_face_angle"])
-        a.success_reward, a.p_face_flip, a.round_target_face = float(c.success_reward), float(c.p_face_flip), float(c.round_target_face)
+        a.p_face_flip, a.round_target_face = float(c.p_face_flip), float(c.round_target_face)
         a.directions = (1 if "cw" in c.goal_directions else 0) | (2 if "ccw" in c.goal_directions else 0)
         a.goal_mode = _GOAL_MODES[c.goal_generation]
-        a.max_timesteps_per_goal, a.successes_needed, a.use_goal_distance_reward, a.stop_on_fall = int(c.max_timesteps_per_goal), int(c.successes_needed), int(c.use_goal_distance_reward), int(self.stop_on_fall)
         a.pipelined = int(self.pipelined_reset and force is None)
         if a.pipelined:
-            a.phase, a.tries, a.nticks_next, a.hold_next = P(self._phase), P(self._tries), P(self._nticks), P(self._hold)
-            a.resetting, a.episode_started = P(F["resetting"]), P(F["episode_started"])
+            a.hold_next = P(self._hold)
             a.reset_draws = None if self._pipe_draws is None else P(self._pipe_draws)
             a.qpos0, a.ctrl_lo, a.ctrl_hi = P(self._qpos0_rows), P(self._ctrl_lo), P(self._ctrl_hi)
-            a.wiggle_std = float(c.cube_position_wiggle_std)
-            a.reset_initial_steps, a.n_random_initial_steps, a.max_pose_resets = int(c.reset_initial_steps), int(c.n_random_initial_steps), int(c.max_pose_resets)
             a.num_scramble_steps, a.scramble_face_angles, a.randomize_face_angles = int(c.num_scramble_steps), int(c.scramble_face_angles), int(c.randomize_face_angles)
         stream = None if sim._emul else ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         self._keep_post = (force, self._draws, self._pipe_draws)
@@ -491,9 +475,7 @@ class BatchedFullPerpendicularEnv:
     def step(self, action: torch.Tensor):
         """RobotEnv.step (robot_env.py:804-844): returns (obs dict, reward [B, 3], done [B], info dict); every tensor is a view of a
         buffer the two launches wrote."""
-        if self._needs_reset:
-            raise RuntimeError("call reset() before step()")
-        action = torch.as_tensor(action, dtype=torch.float32, device=self.device).reshape(self.batch_size, self.num_actions).contiguous()
+        action = self._action_rows(action)
         ev = self._physics_events
         if ev is not None:
             ev[0].record()
@@ -502,12 +484,8 @@ class BatchedFullPerpendicularEnv:
         if ev is not None:
             ev[1].record()
         self._post()
-        F, tr = self._flags, self.multi_goal_tracker
-        info = {"goal_dist": {"cube_quat": self._goal_dist[:, 0], "cube_face_angle": self._goal_dist[:, 1]}, "goal_achieved": F["sub_goal_ok"],
-                "sub_goal_is_successful": F["sub_goal_ok"], "trial_success": F["trial_success"], "goal_reset": F["goal_reset"], "successes_so_far": tr.successes_so_far,
-                "steps_since_last_goal": self._info_ssl, "goals_so_far": tr.goals_so_far, "env_crash": F["env_crash"], "sim_status": self.mujoco_simulation.status,
-                "resetting": F["resetting"], "episode_started": F["episode_started"]}
-        return self.observe(), self._reward, F["done"], info
+        info = self._step_info({"cube_quat": self._goal_dist[:, 0], "cube_face_angle": self._goal_dist[:, 1]}, self.mujoco_simulation.status)
+        return self.observe(), self._reward, self._flags["done"], info
 
     def observe(self) -> Dict[str, torch.Tensor]:
         """Keys and shapes of `FullPerpendicularEnv._default_observation_map` (full_perpendicular.py:177-192); views of the observation row

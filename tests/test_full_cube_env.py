@@ -525,6 +525,31 @@ def test_pipelined_reset_phase_machine_emul(full_model, emul_lib):
     sim.scratch("site_xpos")[:, 3 * sim.center_site + 2] = 0.0
     env._post()
     assert (env._phase == 0).all() and F["episode_started"].all()           # third pass: taken as it is (cube_env.py:336-355 leaves the loop)
+    # a simulation that crashes (BAD_STATE; the reference raises MujocoException, warning_buffer.py:15-24) while live ends the episode; inside the recipe it
+    # restarts the recipe and counts as a pass; a live env whose cube drops below the palm ends its episode under stop_on_fall.  Env 0 is the control
+    from robogym_amd import _native
+    status = sim.view(_native.RG_F_STATUS)
+    tr = env.multi_goal_tracker
+    env.multi_goal_tracker.max_timesteps_per_goal = env.constants.max_timesteps_per_goal = 100      # (no time-out below)
+    env._phase[:] = 0; env._tries[:] = 0
+    sim.forward()
+    status[1] = _native.RG_STATUS_BAD_STATE
+    steps_before = tr.steps.clone()
+    env._post()
+    assert F["done"].tolist() == [False, True, False] and F["env_crash"].tolist() == [False, True, False] and env._phase.tolist() == [0, 1, 0] and env._tries.tolist() == [0, 0, 0]
+    assert (tr.steps == steps_before + 1).all() and (env._reward[1] == 0).all() and int(status[1]) == 0        # (the restart is MjSim.reset: the status word is cleared)
+    env._phase[:] = torch.tensor([0, 3, 0], dtype=torch.int32); env._tries[:] = torch.tensor([0, 1, 0], dtype=torch.int32)
+    sim.forward()
+    status[1] = _native.RG_STATUS_BAD_STATE
+    env._post()
+    assert not F["done"].any() and F["env_crash"].tolist() == [False, True, False] and env._phase.tolist() == [0, 1, 0] and env._tries.tolist() == [0, 2, 0]
+    assert F["resetting"].tolist() == [False, True, False] and not F["episode_started"].any()
+    env._phase[:] = 0; env._tries[:] = 0
+    env.stop_on_fall = True
+    sim.forward()
+    sim.scratch("site_xpos")[2, 3 * sim.center_site + 2] = 0.0
+    env._post()
+    assert F["done"].tolist() == [False, False, True] and not F["env_crash"].any() and env._phase.tolist() == [0, 0, 1]
 
 
 @pytest.mark.gpu

@@ -190,6 +190,69 @@ def test_pipelined_reset_state_machine(locked_model, emul_lib):
     assert (0.2 + obs["cube_pos"][:, 2] > 0.04).all()                                  # the cube rests in the hand
 
 
+def test_episode_bookkeeping_branches(locked_model, emul_lib):
+    """Every branch of the episode bookkeeping in rg_post_step_kernel (MultiGoalTracker.process, the pipelined recipe's phase machine, stop_on_fall), driven
+    without physics: the step launch is replaced by scripted goal distances, status words and cube heights.  max_timesteps_per_goal 3, successes_needed 2,
+    recipe 1 + 1 steps, max_pose_resets 2.  Env 0 times out; env 1 reaches its goal (new goal), then again (trial success); env 2 crashes while live and again
+    inside the recipe; env 3's cube is below the palm throughout: it falls (stop_on_fall), its recipe ends off the palm (retry) and is accepted on the second
+    pass (max_pose_resets).  The flag and phase tables below are written out by hand from robot_env.py:804-844 and cube_env.py:330-355 (an episode that ends on
+    step s runs the recipe on steps s + 1, s + 2 and starts on s + 2 if accepted); the counters come from BatchedMultiGoalTracker (multi_goal_tracker.py)."""
+    from robogym_amd import _native
+    from robogym_amd.envs.dactyl.locked import BatchedLockedEnv, LockedEnvConstants
+    from robogym_amd.utils.multi_goal_tracker import BatchedMultiGoalTracker
+
+    B, S = 4, 8
+    c = LockedEnvConstants(max_timesteps_per_goal=3, successes_needed=2, reset_initial_steps=1, n_random_initial_steps=1, max_pose_resets=2, mujoco_substeps=1)
+    env = BatchedLockedEnv(B, constants=c, model=locked_model, lib=emul_lib, starting_seed=3, pipelined_reset=True)
+    env.stop_on_fall = True
+    env._needs_reset = False
+    sim = env.mujoco_simulation
+    dist = np.full((S, B), 1.0, np.float32); dist[0:2, 1] = 0.1                 # success threshold 0.4 rad
+    crash = np.zeros((S, B), bool); crash[0:2, 2] = True
+    z = np.array([0.1, 0.1, 0.1, 0.0], np.float32)                              # cube:center height; on the palm: > 0.04
+    k = [0]
+
+    def scripted_step(**kw):      # what the physics launch leaves behind for the env kernel
+        env._goal_dist.copy_(torch.as_tensor(dist[k[0]]))
+        env._obs_buf[:, 2] = torch.as_tensor(z - sim.cube_body_z)
+        sim.view(_native.RG_F_STATUS)[:, 0] = torch.as_tensor(crash[k[0]].astype(np.int32) * _native.RG_STATUS_BAD_STATE)
+
+    sim.env_step = scripted_step
+    T = lambda rows: np.array(rows).T       # rows per env -> [S, B]
+    phase = T([[0, 0, 1, 2, 0, 0, 0, 1], [0, 1, 2, 0, 0, 0, 1, 2], [1, 1, 2, 0, 0, 0, 1, 2], [1, 2, 1, 2, 0, 1, 2, 1]])
+    tries = T([[0] * 8, [0] * 8, [0, 1, 1, 1, 1, 1, 0, 0], [0, 0, 1, 1, 1, 0, 0, 1]])
+    at = lambda *steps: [i + 1 in steps for i in range(S)]
+    done = T([at(3, 8), at(2, 7), at(1, 7), at(1, 6)])
+    started = T([at(5), at(4), at(4), at(5)])
+    sub_goal_ok, goal_reset, trial = T([at(), at(1, 2), at(), at()]), T([at(), at(1), at(), at()]), T([at(), at(2), at(), at()])
+    ref = BatchedMultiGoalTracker(B, "cpu", c.max_timesteps_per_goal, c.success_reward, c.successes_needed, c.use_goal_distance_reward)
+    clock = np.zeros(B, np.int64)
+    live = np.ones(B, bool)
+    for s in range(S):
+        k[0] = s
+        obs, reward, dn, info = env.step(torch.zeros((B, 20)))
+        succ = torch.as_tensor(live & ~crash[s] & (dist[s] < 0.4))
+        _, _, new_goal, _ = ref.process(succ, torch.zeros(B), torch.as_tensor(live))
+        assert new_goal.tolist() == goal_reset[s].tolist(), s
+        ref.reset_goal_steps(new_goal)
+        st = torch.as_tensor(started[s])
+        ref.reset(st); ref.reset_goal_steps(st)        # RobotEnv.reset's tail: tracker.reset, then the first goal
+        clock = np.where(started[s], 0, clock + live)
+        for name, want in (("done", done), ("episode_started", started), ("sub_goal_is_successful", sub_goal_ok), ("goal_achieved", sub_goal_ok), ("goal_reset", goal_reset),
+                           ("trial_success", trial), ("env_crash", crash), ("resetting", phase > 0)):
+            got = dn if name == "done" else info[name]
+            assert got.tolist() == want[s].astype(bool).tolist(), (s, name, got.tolist())
+        assert env._phase.tolist() == phase[s].tolist() and env._tries.tolist() == tries[s].tolist(), (s, env._phase.tolist(), env._tries.tolist())
+        assert env._nticks.tolist() == [3 if p == 0 else 2 for p in phase[s]], s           # recipe steps 1 and 2 both carry a second forward here
+        tr = env.multi_goal_tracker
+        for a, b in ((tr.steps, ref.steps), (tr.steps_since_last_goal, ref.steps_since_last_goal), (tr.successes_so_far, ref.successes_so_far),
+                     (tr.goals_so_far, ref.goals_so_far), (tr.consecutive_success, ref.consecutive_success), (info["steps_since_last_goal"], ref.steps_since_last_goal)):
+            assert a.tolist() == b.tolist(), (s, a.tolist(), b.tolist())
+        assert env.t.tolist() == clock.tolist(), (s, env.t.tolist())
+        assert reward[:, 2].tolist() == [c.success_reward * float(g) for g in sub_goal_ok[s]] and (reward[:, 0] == 0).all()
+        live = phase[s] == 0
+
+
 def test_model_blob_is_validated(emul_lib, locked_model):
     """The C ABI refuses blobs whose directory points outside the buffer (and says why) instead of reading past it."""
     import ctypes
