@@ -521,6 +521,13 @@ typedef struct ra_post_args {
    * ObjectStateGoal.relative_goal (goals/object_state.py:520-554) matches objects to goals inside each group greedily by position distance, and the relative goal,
    * both distances and the success count go through that match.  goal_obj_pos / goal_obj_rot / qpos_goal stay indexed by goal.  Kinds 0-2 only. */
   const int* obj_group;
+  /* rotation distance modes (appended; zero-filled = "full", the path above).  rot_dist_type 0: full -- quat2euler(q_goal conj(q_obj)); 1: mod90, 2: mod180 --
+   * euler_angle_difference_single_pair (goals/object_state.py:25-64): of diff_p = quat_difference(q_goal p, q_obj) over the 24 (mod90) or 4 (mod180) parallel quaternions
+   * p, in the table's order, the first with the smallest quat_magnitude; the relative rotation is its Euler angles, the distance its angle.  Without the reference's
+   * np.allclose(q_goal, q_obj) -> zeros shortcut (p = identity gives the same zeros).  The tables are the caller's: device pointers to EXACTLY 24 x 4 and 4 x 4 floats (the kernel reads those lengths, nothing carries them)
+   * (robogym_amd/utils/rotation.py parallel_quat_table), NULL allowed for a mode that is not selected.  Group matching stays position-only. */
+  const float *parallel_quats, *parallel_quats_180;
+  int rot_dist_type;
 } ra_post_args;
 int ra_env_post_step(rb_batch* main, rb_batch* solver, const ra_post_args* args, void* stream);
 int ra_post_args_size(void);
@@ -576,6 +583,15 @@ typedef struct ra_recipe_args {
    * tower of 2..N objects (a random subset, the first stays, the h-th other gets its x, y and + object_size * (h + 1) * 2 in z). */
   const float* goal_distance_ratio;              /* [B], NULL = 1 */
   float goal_distance_min, pickup_proba, stacking_proba;
+  /* goal orientation (appended; zero-filled = the goal keeps the yaw it has).  randomize_goal_rot 1: randomize_quaternion_along_z (goals/object_state.py:80-85) for every
+   * goal the kernel makes -- the goal's yaw = the yaw it had + U(0, 2 pi) per object, drawn BEFORE the positions (_update_simulation_for_next_goal, :333-358), which are
+   * then placed with the boxes rotated by the goal's yaws; draws (seed ^ 0xC2B2AE35, step, env, object): a stream of their own.
+   * goal kind 6, DominoStateGoal (goals/dominos.py:20-150; recipe only: ra_post_args scores it as kind 0): per attempt offset = u pi, delta = u pi / 4 - pi / 8; goal
+   * yaws k delta + offset + delta / 2 (absolute: they replace the goal's yaw); the chain starts at the origin and steps by object_size * domino_distance_mul along
+   * (cos, sin)(k delta + offset), k = 1 ..; accepted when its extent with the yawed half sizes is strictly inside the placement area, then shifted by a uniform offset
+   * inside what is left; at most 1000 attempts (MAX_RETRY), after which the goal positions are zero and placement_failed is raised. */
+  int randomize_goal_rot;
+  float domino_distance_mul;
 } ra_recipe_args;
 int ra_env_recipe_step(rb_batch* main, rb_batch* solver, const ra_recipe_args* args, void* stream);
 int ra_recipe_args_size(void);

@@ -93,7 +93,8 @@ def _ra_post_fields():
             + [(n, _i) for n in ("max_timesteps_per_goal", "successes_needed", "use_goal_distance_reward")]
             + [("solver_qpos", _p), ("solver_ctrl", _p), ("solver_nq", _i), ("solver_nu", _i), ("solver_grip_qposadr", _i), ("solver_grip_act", _i), ("frozen", _p), ("reward_clip", _f)]
             + [("goal_kind", _i), ("grip_site", _i), ("goal_dist_extra", _p)]
-            + [("obj_group", _p)])
+            + [("obj_group", _p)]
+            + [("parallel_quats", _p), ("parallel_quats_180", _p), ("rot_dist_type", _i)])
 
 
 class RaPostArgs(ctypes.Structure):
@@ -113,7 +114,8 @@ def _ra_recipe_fields():
                ("n_random_initial_steps", _i), ("settle_steps", _i), ("seed", ctypes.c_uint), ("step", ctypes.c_uint)]
             + [("goal_kind", _i), ("height_range", _f * 2), ("object_size", _f), ("fixed_order", _i), ("target_height", _f), ("det_points", (_f * 3) * 2), ("goal_index", _p)]
             + [("obj_group", _p), ("group_mode", _i), ("sample_lam", _f * 2)]
-            + [("goal_distance_ratio", _p), ("goal_distance_min", _f), ("pickup_proba", _f), ("stacking_proba", _f)])
+            + [("goal_distance_ratio", _p), ("goal_distance_min", _f), ("pickup_proba", _f), ("stacking_proba", _f)]
+            + [("randomize_goal_rot", _i), ("domino_distance_mul", _f)])
 
 
 class RaRecipeArgs(ctypes.Structure):

@@ -8,7 +8,7 @@
 //                                                                 robot/ur16e/mujoco/simulation/base.py:142-167 (gripper - table plane)
 //   check_objects_off_table                                       envs/rearrange/simulation/base.py:805-832
 //   reward / done                                                 envs/rearrange/common/base.py:768-795, 824-848
-//   ObjectStateGoal.relative_goal / goal_distance                 envs/rearrange/goals/object_state.py:492-599 (rot_dist_type "full"; duplicated-object groups: ra_group_match)
+//   ObjectStateGoal.relative_goal / goal_distance                 envs/rearrange/goals/object_state.py:492-599 (rot_dist_type full / mod90 / mod180; duplicated-object groups: ra_group_match)
 //   _get_goal_info, MultiGoalTracker.process                      robot_env.py:577-625, utils/multi_goal_tracker.py:157-241
 //   JointControlledTcpArm.on_observations_updated                 robot/ur16e/mujoco/joint_controlled_tcp_arm.py:114-129 (gripper state -> solver world)
 // Rotation helpers follow robogym/utils/rotation.py (mat2euler, quat2mat, normalize_angles) as rb_env_kernel.h's rbc_* do.
@@ -105,7 +105,24 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
     const float* gm = a.goal + ((size_t)e * N + mgoal) * 7;
     float qc[4] = {xquat[4 * b], -xquat[4 * b + 1], -xquat[4 * b + 2], -xquat[4 * b + 3]}, qd[4], Md[9], rel[3];
     if (reach) { qc[0] = 1.f; qc[1] = qc[2] = qc[3] = 0.f; }      // ObjectReachGoal.current_state: the achieved rotation is zero
-    rbc_qmul(gm + 3, qc, qd);                 // subtract_euler(goal, current) = quat2euler(q_goal conj(q_obj))
+    if (a.rot_dist_type == 0) {
+      rbc_qmul(gm + 3, qc, qd);               // subtract_euler(goal, current) = quat2euler(q_goal conj(q_obj))
+    } else {
+      // mod90 / mod180, euler_angle_difference_single_pair (goals/object_state.py:25-64): diff_p = quat_difference(q_goal p, q_obj) over the table's parallel
+      // quaternions p (24 / 4 of them: fixed lengths, include/rgstep.h), the first with the smallest quat_magnitude = with the largest |w| (2 acos(w) falls with w; the
+      // strict > keeps the first among equals); its Euler angles and its angle then come out of the lines below, which do not see the quaternion's sign
+      const float* tab = a.rot_dist_type == 1 ? a.parallel_quats : a.parallel_quats_180;
+      const int np_ = a.rot_dist_type == 1 ? 24 : 4;
+      float best = -1.f;
+      qd[0] = 1.f; qd[1] = qd[2] = qd[3] = 0.f;
+      for (int c = 0; c < np_; c++) {
+        float gp_[4], d[4];
+        rbc_qmul(gm + 3, tab + 4 * c, gp_);
+        rbc_qmul(gp_, qc, d);
+        const float w = fabsf(d[0]);
+        if (w > best) { best = w; qd[0] = d[0]; qd[1] = d[1]; qd[2] = d[2]; qd[3] = d[3]; }
+      }
+    }
     rbc_quat2mat(qd, Md); rbc_mat2euler(Md, rel);
     for (int k = 0; k < 3; k++) rel[k] = rbc_wrap(rel[k]);
     const float* ach = reach ? grip : xpos + 3 * b;                // ... and the achieved position the grip site's
@@ -262,7 +279,8 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
 //   RearrangeEnv._reset, _randomize_robot_initial_position        envs/rearrange/common/base.py:897-932, 498-510
 //   place_objects_in_grid / place_objects_with_no_constraint       envs/rearrange/common/utils.py:719-829 / 829-880 (_place_objects :623-716)
 //   get_placement_area                                             envs/rearrange/simulation/base.py:980-1010
-//   ObjectStateGoal.next_goal                                      envs/rearrange/goals/object_state.py:355-418
+//   ObjectStateGoal.next_goal                                      envs/rearrange/goals/object_state.py:355-418 (randomize_goal_rot: randomize_quaternion_along_z, :80-85)
+//   DominoStateGoal                                                envs/rearrange/goals/dominos.py:20-150
 struct RaRecipeLds { int started, ended, regoal, moved; float pos[RA_MAXOBJ][3], gpos[RA_MAXOBJ][3], gyaw[RA_MAXOBJ], opos[3]; };
 
 // One placement of the first N objects (rotated about z by yaw[i]) inside the placement area: body origins in world coordinates.  Returns false when the rejection
@@ -376,6 +394,37 @@ __device__ inline bool ra_place_near(const RaRecipeArgs& a, int N, const float* 
   return ok;
 }
 
+// DominoStateGoal._create_new_domino_position_and_rotation / _adjust_and_check_fit / _sample_next_goal_positions (goals/dominos.py:20-150): per attempt offset = u pi and
+// delta = u pi / 4 - pi / 8; domino k gets the yaw k delta + offset + delta / 2 and stands where the chain of steps object_size * domino_distance_mul along
+// (cos, sin)(j delta + offset), j = 1 .. k, ends (the first at the origin); an attempt is taken when the chain's extent with the yawed half sizes is STRICTLY smaller than
+// the placement area, and is then shifted by a uniform offset inside what is left.  z: the box's half height on the table top.  Returns false after MAX_RETRY = 1000
+// attempts, with zero positions as the reference returns them (gyaw = the last attempt's).  Two passes over the chain per attempt instead of per-domino arrays.
+__device__ inline bool ra_domino_arc(const RaRecipeArgs& a, int N, unsigned seed, unsigned step, unsigned e, unsigned& k, float* gyaw, float (*out)[3]) {
+  auto U = [&]() -> float { return env_u01(seed, step, e, k++); };
+  const float dist = a.object_size * a.domino_distance_mul, width = a.area_size[0], height = a.area_size[1];
+  for (int attempt = 0; attempt < 1000; attempt++) {
+    const float offset = U() * RBC_PI, delta = U() * (0.25f * RBC_PI) - 0.125f * RBC_PI;
+    float x = 0.f, y = 0.f, min_x = INFINITY, min_y = INFINITY, max_x = -INFINITY, max_y = -INFINITY;
+    for (int i = 0; i < N; i++) {
+      if (i > 0) { const float t = (float)i * delta + offset; x += cosf(t) * dist; y += sinf(t) * dist; }
+      const float yw = (float)i * delta + (offset + 0.5f * delta);
+      const float c = fabsf(cosf(yw)), s_ = fabsf(sinf(yw));
+      const float hx = c * a.obj_half[i][0] + s_ * a.obj_half[i][1], hy = s_ * a.obj_half[i][0] + c * a.obj_half[i][1];      // rotate_bounding_box
+      gyaw[i] = yw; out[i][0] = x; out[i][1] = y;
+      min_x = fminf(min_x, x - hx); max_x = fmaxf(max_x, x + hx); min_y = fminf(min_y, y - hy); max_y = fmaxf(max_y, y + hy);
+    }
+    const float size_x = max_x - min_x, size_y = max_y - min_y;
+    if (size_x < width && size_y < height) {
+      const float dx = -min_x + U() * (width - size_x) + a.area_offset[0] - a.table_size[0] + a.table_pos[0];
+      const float dy = -min_y + U() * (height - size_y) + a.area_offset[1] - a.table_size[1] + a.table_pos[1];
+      for (int i = 0; i < N; i++) { out[i][0] += dx; out[i][1] += dy; out[i][2] = a.obj_half[i][2] + a.table_size[2] + a.table_pos[2]; }
+      return true;
+    }
+  }
+  for (int i = 0; i < N; i++) out[i][0] = out[i][1] = out[i][2] = 0.f;
+  return false;
+}
+
 __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbBatchDev bt, const RbModelDev* sp, RbBatchDev sb, RaRecipeArgs a) {
 #ifdef RG_EMUL
   RaRecipeLds& F = *(RaRecipeLds*)emul_lds();
@@ -428,6 +477,11 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
       auto UG = [&]() -> float { return env_u01(gseed, a.step, (unsigned)e, k++); };
       const int kind = a.goal_kind;
       F.moved = 0;
+      // the goal's yaws: the ones it has, or -- randomize_quaternion_along_z, drawn before the positions -- those turned by U(0, 2 pi) each; the placements below work
+      // with the boxes rotated by THESE
+      for (int i = 0; i < N; i++) F.gyaw[i] = gy[i * gstride];
+      if (a.randomize_goal_rot) for (int i = 0; i < N; i++) F.gyaw[i] += 2.f * RBC_PI * env_u01(a.seed ^ 0xC2B2AE35u, a.step, (unsigned)e, (unsigned)i);
+      gy = F.gyaw; gstride = 1;
       if (kind <= 1) {
         if (!ra_place(a, N, false, gy, gstride, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
         if (kind == 1) {                                               // move_one_object_to_the_air: height first, then the object
@@ -463,6 +517,8 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
             }
           }
         }
+      } else if (kind == 6) {                                          // DominoStateGoal (goals/dominos.py:53-150): the dominos on a circle arc
+        if (!ra_domino_arc(a, N, gseed, a.step, (unsigned)e, k, F.gyaw, F.gpos)) a.placement_failed[e] += 1;
       } else {                                                         // reach: the object goes to the placement, the goal target_height above it
         if (kind == 3) {
           if (!ra_place(a, 1, true, gy, gstride, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
@@ -475,7 +531,6 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
         F.gpos[0][2] += a.target_height;
         F.moved = 1;
       }
-      for (int i = 0; i < N; i++) F.gyaw[i] = gy[i * gstride];
     }
     // ---- an episode that ended on this step: its recipe begins (the returned observation / reward / done are the terminal ones)
     if (!started && st == 0 && a.done[e]) {

@@ -1517,6 +1517,8 @@ int ra_env_post_step(rb_batch* b, rb_batch* solver, const ra_post_args* args, vo
   if (a.goal_kind == 2 && !a.goal_dist_extra) return fail("ra_env_post_step: the stack goal needs goal_dist_extra");
   if (a.goal_kind >= 3 && a.num_objects != 1) return fail("ra_env_post_step: the reach goals take exactly one object");
   if (a.obj_group && a.goal_kind >= 3) return fail("ra_env_post_step: obj_group with a reach goal (one object: nothing to match)");
+  if (a.rot_dist_type < 0 || a.rot_dist_type > 2) return fail("ra_env_post_step: rot_dist_type out of range (0 full, 1 mod90, 2 mod180)");
+  if ((a.rot_dist_type == 1 && !a.parallel_quats) || (a.rot_dist_type == 2 && !a.parallel_quats_180)) return fail("ra_env_post_step: rot_dist_type mod90 / mod180 needs its table of parallel quaternions");
   if (solver) {
     if (solver->dev.B != b->dev.B || solver->device != b->device) return fail("ra_env_post_step: the two batches must have the same size and device");
     const RbModelDev& ds = solver->model->dev;
@@ -1546,7 +1548,9 @@ int ra_env_recipe_step(rb_batch* b, rb_batch* solver, const ra_recipe_args* args
   for (int k = 0; k < 6; k++) if (a.arm_qposadr[k] < 0 || a.arm_qposadr[k] >= d.nq) return fail("ra_env_recipe_step: arm joint address out of range");
   if (!(a.area_size[0] > 0.f) || !(a.area_size[1] > 0.f)) return fail("ra_env_recipe_step: empty placement area");
   if (a.stabilize_steps < 0 || a.n_random_initial_steps < 0 || a.settle_steps < 0) return fail("ra_env_recipe_step: negative step count");
-  if (a.goal_kind < 0 || a.goal_kind > 5) return fail("ra_env_recipe_step: goal_kind out of range (0 object state, 1 pick-and-place, 2 stack, 3 reach, 4 deterministic reach, 5 train)");
+  if (a.goal_kind < 0 || a.goal_kind > 6) return fail("ra_env_recipe_step: goal_kind out of range (0 object state, 1 pick-and-place, 2 stack, 3 reach, 4 deterministic reach, 5 train, 6 dominos)");
+  if (a.goal_kind == 6 && !(a.object_size > 0.f && a.domino_distance_mul > 0.f)) return fail("ra_env_recipe_step: the domino goal needs object_size > 0 and domino_distance_mul > 0");
+  if (a.randomize_goal_rot < 0 || a.randomize_goal_rot > 1) return fail("ra_env_recipe_step: randomize_goal_rot is 0 or 1");
   if ((a.goal_kind == 1 || a.goal_kind == 5) && !(a.height_range[0] <= a.height_range[1])) return fail("ra_env_recipe_step: empty height_range");
   if ((a.goal_kind == 3 || a.goal_kind == 4) && a.num_objects != 1) return fail("ra_env_recipe_step: the reach goals take exactly one object");
   if (a.goal_kind == 5 && !(a.goal_distance_min >= 0.f && a.pickup_proba >= 0.f && a.stacking_proba >= 0.f && a.pickup_proba + a.stacking_proba <= 1.f))

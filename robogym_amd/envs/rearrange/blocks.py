@@ -48,7 +48,11 @@ JOINT_DRIFT_THRESHOLD = float(np.deg2rad(1))
 FLAG_FULL_FORWARD = 32
 #: the goal generators of the rearrange block tasks (ra_post_args.goal_kind): ObjectStateGoal (goals/object_state.py), PickAndPlaceGoal (goals/pickandplace.py),
 #: ObjectStackGoal (goals/object_stack_goal.py), ObjectReachGoal / DeterministicReachGoal (goals/object_reach_goal.py)
-GOAL_KINDS = {"object_state": 0, "pickandplace": 1, "stack": 2, "reach": 3, "det-reach": 4, "train": 5}      # (train: TrainStateGoal, goals/train_state.py)
+GOAL_KINDS = {"object_state": 0, "pickandplace": 1, "stack": 2, "reach": 3, "det-reach": 4, "train": 5, "dominos": 6}      # (train: TrainStateGoal, goals/train_state.py; dominos: DominoStateGoal, goals/dominos.py)
+#: GoalArgs.rot_dist_type (goals/object_state.py:127-131) -> ra_post_args.rot_dist_type; "icp" is not built
+ROT_DIST_TYPES = {"full": 0, "mod90": 1, "mod180": 2}
+#: DominoStateGoal's attempts per goal (goals/dominos.py:10)
+DOMINO_MAX_RETRY = 1000
 #: DeterministicReachGoal's two object positions (goals/object_reach_goal.py:65-66)
 DET_REACH_POINTS = np.array([[1.50253879, 0.36960144, 0.5170952], [1.32253879, 0.53960144, 0.5170952]])
 #: lambda range of `sample_group_counts` (common/utils.py:47-49, the function's own defaults)
@@ -168,6 +172,47 @@ def move_one_object_to_the_air_with_restrictions(random_state, placement, height
     return placement
 
 
+def randomize_yaw_along_z(random_state, yaw):
+    """`randomize_quaternion_along_z` (goals/object_state.py:71-85) on yaw angles, draw for draw: one `uniform(0, 2 pi, size=N)`; the goal's new orientation is that z
+    rotation times the one it has, i.e. the sum of the two yaws.  `yaw` [N] -> [N]."""
+    yaw = np.asarray(yaw, dtype=np.float64)
+    return yaw + random_state.uniform(low=0.0, high=2.0 * np.pi, size=yaw.shape[-1])
+
+
+def domino_goal(random_state, obj_half, object_distance, table_pos, table_size, area_offset, area_size, max_retry=DOMINO_MAX_RETRY):
+    """`DominoStateGoal._sample_next_goal_positions` (goals/dominos.py:20-150), draw for draw: per attempt offset = u pi and delta = u pi / 4 - pi / 8; domino k is turned
+    by k delta + offset + delta / 2 about z and stands at the end of k steps of `object_distance` along (cos, sin)(j delta + offset), j = 1..k; the attempt is taken when the
+    chain with the yawed half extents (`obj_half` [N, 3] at the identity orientation: boxes) is strictly smaller than the placement area, and then lands at a uniform
+    offset inside what is left (two more draws).  Returns ([N, 3] body origins in world coordinates, [N] yaws, valid); after `max_retry` attempts zeros, the last
+    attempt's yaws -- the reference leaves the targets turned by them -- and False."""
+    obj_half = np.asarray(obj_half, dtype=np.float64)
+    N = len(obj_half)
+    table_pos, table_size = np.asarray(table_pos, dtype=np.float64), np.asarray(table_size, dtype=np.float64)
+    width, height = area_size[0], area_size[1]
+    ks = np.arange(N)
+    yaws = np.zeros(N)
+    for _ in range(max_retry):
+        offset = random_state.random_sample() * np.pi
+        delta = random_state.random_sample() * (np.pi / 4.0) - (np.pi / 8.0)
+        yaws = ks * delta + (offset + delta / 2)
+        between = (ks + 1) * delta + offset
+        pos = np.zeros((N, 3))
+        pos[1:, 0] = (np.cumsum(np.cos(between)) * object_distance)[:N - 1]
+        pos[1:, 1] = (np.cumsum(np.sin(between)) * object_distance)[:N - 1]
+        c, s_ = np.abs(np.cos(yaws)), np.abs(np.sin(yaws))
+        half = np.stack([c * obj_half[:, 0] + s_ * obj_half[:, 1], s_ * obj_half[:, 0] + c * obj_half[:, 1], obj_half[:, 2]], -1)      # rotate_bounding_box
+        pos[:, 2] = half[:, 2]
+        max_x, max_y, _ = np.max(pos + half, axis=0)
+        min_x, min_y, _ = np.min(pos - half, axis=0)
+        size_x, size_y = max_x - min_x, max_y - min_y
+        if size_x < width and size_y < height:
+            dx = -min_x + random_state.random_sample() * (width - size_x)
+            dy = -min_y + random_state.random_sample() * (height - size_y)
+            start = table_pos - table_size
+            return pos + [dx + start[0] + area_offset[0], dy + start[1] + area_offset[1], table_pos[2] + table_size[2]], yaws, True
+    return np.zeros((N, 3)), yaws, False
+
+
 def _parse_object_groups(object_groups, num_objects):
     """`object_groups` -> (mode, counts): "distinct" (None), "single", "sample" (counts drawn per env and episode), or explicit counts -- a list of ints or of the
     reference's `ObjectGroupConfig` fields as dicts, of which `count` alone is built."""
@@ -205,7 +250,7 @@ class BatchedBlockRearrangeEnv:
                  stabilize_object_damping: float = 1.0e-3, control_mode: str = "tcp+roll+yaw", device_reset: bool = False, tcp_solver_mode: str = "mocap_ik",
                  goal_kind: str = "object_state", height_range=(0.05, 0.25), object_size: float = 0.0254, fixed_order: bool = False, target_height: float = 0.1,
                  object_groups="distinct", sample_lam=SAMPLE_LAM, goal_distance_ratio=1.0, goal_distance_min: float = 0.06, pickup_proba: float = 0.0,
-                 stacking_proba: float = 0.0):
+                 stacking_proba: float = 0.0, rot_dist_type: str = "full", randomize_goal_rot: bool = False, model=None, domino_distance_mul: float = 4.0):
         """`per_env_parameters`: every env carries its own copy of the randomisable model fields (`self.sim.params`, LargeModelSimulation(env_params=True)) -- what
         the reference's simulation randomizers and `stabilize_objects` write into `sim.model`.  On by default (measured cost: 0.7 % of the step,
         profiles/r05_ab_rb_env_params.txt); off: the model's own arrays, no randomizers, no damping change while the objects stabilise.
@@ -218,11 +263,23 @@ class BatchedBlockRearrangeEnv:
         "distinct" (default: no row, every object its own goal), "single" (one group; envs/rearrange/blocks_duplicate.py), "sample" (`sample_group_counts` with
         `sample_lam` per env at every episode start, host recipe and device recipe alike) or explicit counts that sum to `num_objects`.
         goal_kind "train" (envs/rearrange/blocks_train.py): `goal_distance_ratio` (a scalar or [B]: `self.goal_distance_ratio`, a device row a curriculum may write per
-        env), `goal_distance_min`, `pickup_proba`, `stacking_proba`, with `height_range` and `object_size`."""
+        env), `goal_distance_min`, `pickup_proba`, `stacking_proba`, with `height_range` and `object_size`.
+        `rot_dist_type` (GoalArgs, goals/object_state.py:127-131): "full" (default), "mod90" or "mod180" -- the rotation distance of the env kernel
+        (ra_post_args.rot_dist_type; the tables of parallel quaternions are device tensors built from utils/rotation.py).  `randomize_goal_rot`: every goal's yaw is the
+        previous one plus U(0, 2 pi) per object (`rot_randomize_type` "z_axis"), its placement made with the boxes turned by the new yaws.
+        `model`: a compiled main world in place of `load_blocks_model(num_objects)` (envs/rearrange/dominos.py: the domino world); goal_kind "dominos" places the goals on a
+        circle arc, `object_size * domino_distance_mul` apart, with per-object goal yaws (DominoStateGoal)."""
         self.B, self.N = int(batch_size), int(num_objects)
         if goal_kind not in GOAL_KINDS:
             raise ValueError("goal_kind %r is not one of %s" % (goal_kind, ", ".join(GOAL_KINDS)))
         self.goal_kind_name, self.goal_kind = goal_kind, GOAL_KINDS[goal_kind]
+        if rot_dist_type not in ROT_DIST_TYPES:
+            if rot_dist_type == "icp":
+                raise NotImplementedError("rot_dist_type \"icp\" is not implemented by the batched rearrange env (full, mod90, mod180)")
+            raise ValueError("rot_dist_type %r is not one of %s" % (rot_dist_type, ", ".join(ROT_DIST_TYPES)))
+        self.rot_dist_type, self.randomize_goal_rot, self.domino_distance_mul = rot_dist_type, bool(randomize_goal_rot), float(domino_distance_mul)
+        if self.goal_kind == 6 and not (float(object_size) > 0 and self.domino_distance_mul > 0):
+            raise ValueError("goal_kind dominos needs object_size > 0 and domino_distance_mul > 0 (got %r, %r)" % (object_size, domino_distance_mul))
         self.reach = self.goal_kind in (3, 4)
         self.goal_distance_min, self.pickup_proba, self.stacking_proba = float(goal_distance_min), float(pickup_proba), float(stacking_proba)
         if not (self.goal_distance_min >= 0 and self.pickup_proba >= 0 and self.stacking_proba >= 0 and self.pickup_proba + self.stacking_proba <= 1.0):
@@ -246,6 +303,12 @@ class BatchedBlockRearrangeEnv:
         self.action_dim = 5 if self.wrist_only else AD          # the env's action width
         self.launch_action_dim = AD
         self.max_position_change = float(max_position_change)
+        if model is not None and main_model is not None:
+            raise ValueError("model and main_model name the same thing: pass one")
+        if self.goal_kind == 6 and model is None and main_model is None:
+            raise ValueError("goal_kind \"dominos\" is DominoStateGoal, the goal generator of the domino world only (goals/dominos.py:13-17): pass model=load_dominos_model(...), "
+                             "as envs/rearrange/dominos.py make_env does")
+        main_model = model if model is not None else main_model
         main = main_model if main_model is not None else load_blocks_model(self.N)   # (main_model: the same world with other objects, envs/rearrange/ycb.py)
         # TcpSolverMode.MOCAP (robot_interface.py:22-29): the MAIN world's arm hangs on the mocap weld itself -- MujocoIdealURGripperCompositeRobot, one world, no joint actuators
         self.tcp_solver_mode = _solver_mode_name(tcp_solver_mode)
@@ -368,7 +431,12 @@ class BatchedBlockRearrangeEnv:
         a.safety_stop_force = 150.0                                      # robot/ur16e/arm_interface.py:46
         a.max_timesteps_per_goal, a.successes_needed, a.use_goal_distance_reward = max_timesteps_per_goal_per_obj * N, successes_needed, int(use_goal_distance_reward)
         a.solver_grip_qposadr, a.solver_grip_act = self.solver_grip_q, self.solver_grip_act
-        a.goal_kind, a.grip_site, a.goal_dist_extra = (0 if self.goal_kind == 5 else self.goal_kind), main.names["site"].index("robot0:grip"), P(self.goal_dist_extra)
+        a.goal_kind, a.grip_site, a.goal_dist_extra = (0 if self.goal_kind in (5, 6) else self.goal_kind), main.names["site"].index("robot0:grip"), P(self.goal_dist_extra)
+        a.rot_dist_type = ROT_DIST_TYPES[rot_dist_type]
+        if a.rot_dist_type:      # the tables euler_angle_difference_single_pair walks, in the reference's order (constant data: built once on the host)
+            from robogym_amd.utils.rotation import parallel_quat_table
+            self.parallel_quats = {m: torch.tensor(parallel_quat_table(m), dtype=torch.float32, device=dev).contiguous() for m in ("mod90", "mod180")}
+            a.parallel_quats, a.parallel_quats_180 = P(self.parallel_quats["mod90"]), P(self.parallel_quats["mod180"])
         self._grip_site = int(a.grip_site)
         self.obj_group = None
         if self.group_mode != "distinct":      # ("sample": all distinct until the first reset draws the rows)
@@ -452,6 +520,7 @@ class BatchedBlockRearrangeEnv:
             if self.obj_group is not None:
                 r.obj_group, r.group_mode = P(self.obj_group), int(self.group_mode == "sample")
                 r.sample_lam[0], r.sample_lam[1] = self.sample_lam
+            r.randomize_goal_rot, r.domino_distance_mul = int(self.randomize_goal_rot), self.domino_distance_mul
 
     # ------------------------------------------------------------------ launches
     def _stream(self):
@@ -650,10 +719,32 @@ class BatchedBlockRearrangeEnv:
         width, height = 0.5 * tsx * portion, 0.38 * tsy * portion
         return (0.5 * tsx - width / 2.0, 0.44 * tsy - height / 2.0, 2 * self.table_size[2]), (width, height, 0.26)
 
+    def _next_goal(self, rows, yaw):
+        """`_update_simulation_for_next_goal` (goals/object_state.py:333-358) for the envs `rows`, whose goals have the yaws `yaw` [len(rows), N]: with
+        `randomize_goal_rot` new yaws first (per env, in the reference's draw order), then the positions for boxes turned by them; the domino goal sets yaws of its
+        own.  -> (positions, yaws): `_write_goal`'s arguments."""
+        if self.randomize_goal_rot and len(rows):
+            yaw = np.stack([randomize_yaw_along_z(self._rng, y) for y in yaw])
+        if self.goal_kind == 6:
+            return self._domino_goals(len(rows))
+        return self._goal_positions(rows, yaw), yaw
+
+    def _domino_goals(self, R):
+        """DominoStateGoal for `R` envs (host numpy; ra_domino_arc does the same on the device): the dominos on a circle arc -> ([R, N, 3], yaws [R, N])"""
+        offset, size = self.placement_area()
+        pos, yaws = np.zeros((R, self.N, 3)), np.zeros((R, self.N))
+        for r in range(R):
+            pos[r], yaws[r], ok = domino_goal(self._rng, self.obj_half, self.object_size * self.domino_distance_mul, self.table_pos, self.table_size, offset, size)
+            if not ok:
+                self.host_placement_failed += 1
+        return pos, yaws
+
     def _goal_positions(self, rows, yaw):
         """`_sample_next_goal_positions` of the env's goal generator for the envs `rows` (host numpy; ra_recipe_kernel does the same on the device): [len(rows), N, 3].
         Reach also moves the object itself (`set_object_pos`: position only) -- the caller's forward makes the observation see it."""
         R, N, kind = len(rows), self.N, self.goal_kind
+        if kind == 6:          # (the arc's positions; its yaws go with them through _next_goal)
+            return self._domino_goals(R)[0]
         if kind == 5:          # TrainStateGoal: goals near the objects' current positions, then one in the air or a tower (goals/train_state.py:81-113)
             idx = torch.as_tensor(rows, device=self.device, dtype=torch.long)
             qpos = self.sim.qpos[idx].cpu().numpy().astype(np.float64)
@@ -818,12 +909,12 @@ class BatchedBlockRearrangeEnv:
                 self._recipe_physics(act, active)
             for _ in range(self.settle_steps):
                 self._recipe_physics(self._zero_action, active)
-        # tracker reset and the first goal (robot_env.py:780-792; ObjectStateGoal.next_goal with randomize_goal_rot = False)
+        # tracker reset and the first goal (robot_env.py:780-792; ObjectStateGoal.next_goal; randomize_goal_rot: _next_goal)
         for f in (self.t, self.steps, self.ssl, self.successes, self.consecutive, self.ema_t):
             f[idx] = 0
         self.ema_value[idx] = 0; self.action_ema[idx] = 0          # SmoothActionWrapper.reset: a fresh filter, action_ema = 0
         self._randomize_simulation(idx)                               # simulation_randomizer.randomize AFTER _reset (robot_env.py:779-783)
-        self._write_goal(rows, self._goal_positions(rows, yaw), yaw)
+        self._write_goal(rows, *self._next_goal(rows, yaw))
         self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=active)       # the forward of _observe_sync
         # the first observation of the new episodes: the env kernel for exactly those rows (observation + gripper hand-over, zeroed reward / done, the success count
         # the first step's goal reward is measured from); the rows of everybody else -- and the reward / done / info tensors their last step() returned -- stay
@@ -886,13 +977,12 @@ class BatchedBlockRearrangeEnv:
             self.frozen[idx] = 0; self.solver_active[idx] = 1; self.hold_ctrl[idx] = 0
             self.resetting[idx] = False; self.episode_started[idx] = True
             self._randomize_simulation(idx)
-            yaw = self._yaw[rows]
-            self._write_goal(rows, self._goal_positions(rows, yaw), yaw)
+            self._write_goal(rows, *self._next_goal(rows, self._yaw[rows]))
         # ---- live envs with a reached goal: ObjectStateGoal.next_goal (what reset_goals() does on request)
         grows = np.nonzero(newgoal.astype(bool) & (st == 0) & ~done.astype(bool))[0]     # (an episode that ends on the same step keeps the reached goal's entries in its terminal observation: ra_recipe_kernel)
         if len(grows):
             yaw = self.goal_rot[torch.as_tensor(grows, device=dev, dtype=torch.long), :, 2].cpu().numpy().astype(np.float64)
-            self._write_goal(grows, self._goal_positions(grows, yaw), yaw)
+            self._write_goal(grows, *self._next_goal(grows, yaw))
         if self.reach:
             self._forward_rows(np.concatenate(started + [grows]))
         self._reobserve(np.concatenate(started) if started else np.zeros(0, dtype=np.int64), grows)
@@ -974,7 +1064,7 @@ class BatchedBlockRearrangeEnv:
         if len(rows) == 0:
             return
         yaw = self.goal_rot[torch.as_tensor(rows, device=self.device, dtype=torch.long), :, 2].cpu().numpy().astype(np.float64)
-        self._write_goal(rows, self._goal_positions(rows, yaw), yaw)
+        self._write_goal(rows, *self._next_goal(rows, yaw))
         if self.reach:
             self._forward_rows(rows)
         self._reobserve(np.zeros(0, dtype=np.int64), rows)      # robot_env.py:893-909: the observation returned after a goal reset carries the new goal
@@ -1076,6 +1166,27 @@ def _check_supported(parameters, sp, rc, constants):
     _solver_mode_name(rc.get("tcp_solver_mode", "mocap_ik"))
 
 
+def goal_rot_args(goal_args, where="constants.goal_args", other=()):
+    """The constructor's keywords from the `GoalArgs` keys that concern the goal's orientation (goals/object_state.py:122-139): `rot_dist_type` (full / mod90 / mod180),
+    `randomize_goal_rot`, `rot_randomize_type` ("z_axis" only: "block" and "full" need goal boxes for orientations that are no yaw).  A key outside these and `other`
+    raises, named."""
+    goal_args = dict(goal_args or {})
+    known = {"rot_dist_type", "randomize_goal_rot", "rot_randomize_type"} | set(other)
+    unknown = sorted(set(goal_args) - known)
+    if unknown:
+        raise NotImplementedError("%s: %s not implemented by the batched rearrange env (supported: %s)" % (where, ", ".join(unknown), ", ".join(sorted(known))))
+    out = {}
+    if "rot_dist_type" in goal_args:
+        if goal_args["rot_dist_type"] not in ROT_DIST_TYPES:
+            raise NotImplementedError("%s.rot_dist_type %r is not implemented by the batched rearrange env (%s)" % (where, goal_args["rot_dist_type"], ", ".join(ROT_DIST_TYPES)))
+        out["rot_dist_type"] = goal_args["rot_dist_type"]
+    if goal_args.get("rot_randomize_type", "z_axis") != "z_axis":
+        raise NotImplementedError("%s.rot_randomize_type %r is not implemented by the batched rearrange env (z_axis)" % (where, goal_args["rot_randomize_type"]))
+    if "randomize_goal_rot" in goal_args:
+        out["randomize_goal_rot"] = bool(goal_args["randomize_goal_rot"])
+    return out
+
+
 def group_args(sp, constants):
     """The constructor's group keywords from `simulation_params.object_groups` ("distinct" / "single" / "sample" / counts) and `constants.sample_lam_low / _high`."""
     out = {}
@@ -1089,9 +1200,10 @@ def group_args(sp, constants):
 def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants=None, starting_seed: int = 0, apply_wrappers: bool = True, **kw):
     """`BlockRearrangeEnv.build` surface (robot_env.py:1081-1089) for the batched env; `apply_wrappers` (default True, as in the reference) = the rearrange
     wrapper stack of common/base.py:986-996 (MultiDiscrete actions of `constants.n_action_bins` = 11 bins, action smoothing, reward clipping).  `parameters` / `constants` accept the subset this env
-    implements (`SUPPORTED_*` below); any other name raises NotImplementedError."""
+    implements (`SUPPORTED_*` below, and `constants.goal_args` {rot_dist_type, randomize_goal_rot, rot_randomize_type}: `goal_rot_args`); any other name raises NotImplementedError."""
     parameters, constants = dict(parameters or {}), dict(constants or {})
     sp, rc = dict(parameters.get("simulation_params", {})), dict(parameters.get("robot_control_params", {}))
+    rot_args = goal_rot_args(constants.pop("goal_args", None))      # constants.goal_args: rot_dist_type, randomize_goal_rot (the task modules take their own keys out first)
     _check_supported(parameters, sp, rc, constants)
     args = dict(num_objects=sp.get("num_objects", 5), max_position_change=rc.get("max_position_change", 0.1), arm_reset_controller_error=rc.get("arm_reset_controller_error", True),
                 n_random_initial_steps=parameters.get("n_random_initial_steps", 10), starting_seed=starting_seed, wrappers=bool(apply_wrappers),
@@ -1105,6 +1217,7 @@ def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants
         if k in sp:
             args[k] = sp[k]
     args.update(group_args(sp, constants))
+    args.update(rot_args)
     for k in ("goal_distance_ratio", "goal_distance_min"):
         if k in sp:
             args[k] = sp[k]

@@ -18,7 +18,7 @@ HEIGHT_RANGE = (0.05, 0.25)
 
 def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants=None, starting_seed: int = 0, apply_wrappers: bool = True, **kw):
     """`BlockTrainRearrangeEnv.build`: blocks.make_env with goal_kind "train", five blocks, sampled groups; simulation_params.goal_distance_ratio / goal_distance_min,
-    constants.goal_args {pickup_proba, stacking_proba, height_range}, constants.use_cuboid, constants.goal_generation ("train" only)."""
+    constants.goal_args {pickup_proba, stacking_proba, height_range, rot_dist_type (full / mod90 / mod180), randomize_goal_rot}, constants.use_cuboid, constants.goal_generation ("train" only)."""
     parameters, constants, task = split_task_args(parameters, constants, num_objects_default=5, constant_names=("goal_args", "use_cuboid", "goal_generation"))
     check_block_count(parameters["simulation_params"]["num_objects"])
     if task.get("goal_generation", "train") != "train":
@@ -28,13 +28,11 @@ def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants
         raise NotImplementedError(("use_cuboid with object_scale_low / object_scale_high != 0: per-axis block sizes need per-env geom sizes" if task.get("use_cuboid")
                                    else "object_scale_low / object_scale_high != 0: per-env object sizes") + " are not implemented by the batched rearrange env")
     goal_args = dict(task.get("goal_args") or {})
-    unknown = sorted(set(goal_args) - {"pickup_proba", "stacking_proba", "height_range"})
-    if unknown:
-        raise NotImplementedError("constants.goal_args: %s not implemented by blocks_train (pickup_proba, stacking_proba, height_range)" % ", ".join(unknown))
+    rot_args = blocks.goal_rot_args(goal_args, other=("pickup_proba", "stacking_proba", "height_range"))      # (raises on any other key, and on rot_dist_type "icp")
     parameters["simulation_params"].setdefault("object_groups", "sample")
     return blocks.make_env(batch_size, device=device, parameters=parameters, constants=constants, starting_seed=starting_seed, apply_wrappers=apply_wrappers,
                            goal_kind="train", object_size=OBJECT_SIZE, height_range=tuple(goal_args.get("height_range", HEIGHT_RANGE)),
-                           pickup_proba=float(goal_args.get("pickup_proba", 0.0)), stacking_proba=float(goal_args.get("stacking_proba", 0.0)), **kw)
+                           pickup_proba=float(goal_args.get("pickup_proba", 0.0)), stacking_proba=float(goal_args.get("stacking_proba", 0.0)), **rot_args, **kw)
 
 
 def make_simple_env(*a, **kw):

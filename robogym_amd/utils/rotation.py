@@ -108,3 +108,36 @@ def vectors2quat_to_z(v: torch.Tensor) -> torch.Tensor:
 def normalize_angles(a: torch.Tensor) -> torch.Tensor:
     """rotation.normalize_angles (utils/rotation.py:372-378): into [-pi, pi)."""
     return (a + np.pi) % (2 * np.pi) - np.pi
+
+
+def parallel_quat_table(mode: str = "mod90") -> np.ndarray:
+    """The table `euler_angle_difference_single_pair` walks (goals/object_state.py:19-64), in the REFERENCE's order -- the order decides which of two equally near
+    candidates is taken: `get_parallel_rotations` / `get_parallel_rotations_180` (utils/rotation.py:393-424) go through the Euler triples over (0, pi/2, -pi/2, pi)
+    ("mod90": 24 rotations) or (0, pi) ("mod180": 4) in product order and keep the first triple of every distinct rotation.  Restated on quaternions: q = qx(e0) qy(e1)
+    qz(e2) (euler2quat's convention), distinct = not equal up to sign; components snapped to the exact 0, 1/2, sqrt(1/2), 1 and the sign fixed to w >= 0 (first non-zero
+    component positive), which quat_difference does not see.  [24, 4] / [4, 4] float64; tests/golden/rearrange_dominos.npz holds the reference's own tables."""
+    import itertools
+
+    if mode not in ("mod90", "mod180"):
+        raise ValueError("parallel_quat_table: mode %r is not mod90 or mod180" % (mode,))
+    angles = (0.0, np.pi / 2, -np.pi / 2, np.pi) if mode == "mod90" else (0.0, np.pi)
+
+    def mul(a, b):
+        return np.array([a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3], a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
+                         a[0] * b[2] + a[2] * b[0] + a[3] * b[1] - a[1] * b[3], a[0] * b[3] + a[3] * b[0] + a[1] * b[2] - a[2] * b[1]])
+
+    def axis_quat(axis, angle):
+        q = np.zeros(4); q[0] = np.cos(angle / 2); q[1 + axis] = np.sin(angle / 2)
+        return q
+
+    exact = np.array([0.0, 0.5, np.sqrt(0.5), 1.0])
+    out = []
+    for e in itertools.product(angles, repeat=3):
+        q = mul(mul(axis_quat(0, e[0]), axis_quat(1, e[1])), axis_quat(2, e[2]))
+        q = np.sign(q) * exact[np.abs(np.abs(q)[:, None] - exact[None, :]).argmin(1)]
+        q = q * np.sign(q[np.nonzero(q)[0][0]])
+        if all(abs(float(q @ p)) < 0.999 for p in out):
+            out.append(q)
+    out = np.array(out)
+    assert out.shape == ((24, 4) if mode == "mod90" else (4, 4))
+    return out
