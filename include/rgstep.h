@@ -592,6 +592,14 @@ typedef struct ra_recipe_args {
    * inside what is left; at most 1000 attempts (MAX_RETRY), after which the goal positions are zero and placement_failed is raised. */
   int randomize_goal_rot;
   float domino_distance_mul;
+  /* fixed placements (appended; recipe only: ra_post_args scores both as kind 0).  goal kind 8, ObjectFixedStateGoal (goals/object_state_fixed.py) over
+   * place_targets_with_fixed_position (common/utils.py:884-919): object i's body origin at fixed_xy[i] * (width, height) of the placement area (each in [0, 1]), z from its
+   * box on the table top, goal yaw fixed_yaw[i] (init_quats: z rotations) -- the same goal every time; randomize_goal_rot has no effect (the reference sets the target
+   * quaternions after it randomised them).  goal kind 7, AttachedBlockStateGoal (goals/attached_block_state.py): num_objects = 8, object_size > 0 (the half size); the
+   * eight cells of the 2-4-2 lattice, 2 object_size apart, handed to the blocks by a Fisher-Yates permutation, the lattice's origin uniform in
+   * [object_size / (width, height), 1 - extent - object_size / (width, height)], then the same placement; goal yaws 0.  Draws from the goal's stream, as the other kinds'. */
+  float fixed_xy[RA_MAXOBJ][2];
+  float fixed_yaw[RA_MAXOBJ];
 } ra_recipe_args;
 int ra_env_recipe_step(rb_batch* main, rb_batch* solver, const ra_recipe_args* args, void* stream);
 int ra_recipe_args_size(void);

@@ -115,7 +115,8 @@ def _ra_recipe_fields():
             + [("goal_kind", _i), ("height_range", _f * 2), ("object_size", _f), ("fixed_order", _i), ("target_height", _f), ("det_points", (_f * 3) * 2), ("goal_index", _p)]
             + [("obj_group", _p), ("group_mode", _i), ("sample_lam", _f * 2)]
             + [("goal_distance_ratio", _p), ("goal_distance_min", _f), ("pickup_proba", _f), ("stacking_proba", _f)]
-            + [("randomize_goal_rot", _i), ("domino_distance_mul", _f)])
+            + [("randomize_goal_rot", _i), ("domino_distance_mul", _f)]
+            + [("fixed_xy", (_f * 2) * RA_MAXOBJ), ("fixed_yaw", _f * RA_MAXOBJ)])
 
 
 class RaRecipeArgs(ctypes.Structure):

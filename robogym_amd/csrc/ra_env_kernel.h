@@ -281,6 +281,8 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
 //   get_placement_area                                             envs/rearrange/simulation/base.py:980-1010
 //   ObjectStateGoal.next_goal                                      envs/rearrange/goals/object_state.py:355-418 (randomize_goal_rot: randomize_quaternion_along_z, :80-85)
 //   DominoStateGoal                                                envs/rearrange/goals/dominos.py:20-150
+//   place_targets_with_fixed_position                              envs/rearrange/common/utils.py:884-919 (ObjectFixedStateGoal, goals/object_state_fixed.py)
+//   AttachedBlockStateGoal                                         envs/rearrange/goals/attached_block_state.py:17-68
 struct RaRecipeLds { int started, ended, regoal, moved; float pos[RA_MAXOBJ][3], gpos[RA_MAXOBJ][3], gyaw[RA_MAXOBJ], opos[3]; };
 
 // One placement of the first N objects (rotated about z by yaw[i]) inside the placement area: body origins in world coordinates.  Returns false when the rejection
@@ -425,6 +427,38 @@ __device__ inline bool ra_domino_arc(const RaRecipeArgs& a, int N, unsigned seed
   return false;
 }
 
+// place_targets_with_fixed_position (common/utils.py:884-919) = _place_objects_trial without its collision check: object i's BODY ORIGIN at rel[i] * (width, height)
+// inside the placement area -- no bounding-box-centre correction in x and y --, z from the box's half height and centre on the table top.  Always valid.
+__device__ inline void ra_place_fixed(const RaRecipeArgs& a, int N, const float (*rel)[2], float (*out)[3]) {
+  for (int i = 0; i < N; i++) {
+    out[i][0] = rel[i][0] * a.area_size[0] + a.area_offset[0] - a.table_size[0] + a.table_pos[0];
+    out[i][1] = rel[i][1] * a.area_size[1] + a.area_offset[1] - a.table_size[1] + a.table_pos[1];
+    out[i][2] = a.obj_half[i][2] + 2.f * a.table_size[2] - a.obj_center[i][2] - a.table_size[2] + a.table_pos[2];
+  }
+}
+
+// AttachedBlockStateGoal._sample_next_goal_positions (goals/attached_block_state.py:17-68): eight blocks tightly attached in the lattice
+//      [ ][ ]
+//   [ ][ ][ ][ ]
+//      [ ][ ]
+// of cells 2 object_size apart (object_size: the HALF size).  Block i goes to cell order[i] of a random permutation (Fisher-Yates); the lattice's origin is one uniform
+// draw in [rel, 1 - extent - rel] per axis, rel = object_size / (width, height): the outermost boxes stay inside the placement area.  `rel`: the table ra_place_fixed takes.
+#define RA_ATTACHED_N 8
+__device__ inline void ra_attached_table(const RaRecipeArgs& a, unsigned seed, unsigned step, unsigned e, unsigned& k, float (*rel)[2]) {
+  auto U = [&]() -> float { return env_u01(seed, step, e, k++); };
+  const int cell_x[RA_ATTACHED_N] = {1, 2, 0, 1, 2, 3, 1, 2}, cell_y[RA_ATTACHED_N] = {0, 0, 1, 1, 1, 1, 2, 2};
+  int order[RA_ATTACHED_N];
+  for (int i = 0; i < RA_ATTACHED_N; i++) order[i] = i;
+  for (int i = RA_ATTACHED_N - 1; i > 0; i--) { int j = (int)(U() * (float)(i + 1)); j = j > i ? i : j; const int tmp = order[i]; order[i] = order[j]; order[j] = tmp; }
+  const float rel_w = a.object_size / a.area_size[0], rel_h = a.object_size / a.area_size[1];
+  const float margin_w = 1.f - 6.f * rel_w - rel_w, margin_h = 1.f - 4.f * rel_h - rel_h;      // 1 - config extent (3 and 2 cells of 2 rel) - rel
+  const float ori_x = rel_w + U() * (margin_w - rel_w), ori_y = rel_h + U() * (margin_h - rel_h);
+  for (int i = 0; i < RA_ATTACHED_N; i++) {
+    rel[i][0] = ori_x + 2.f * rel_w * (float)cell_x[order[i]];
+    rel[i][1] = ori_y + 2.f * rel_h * (float)cell_y[order[i]];
+  }
+}
+
 __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbBatchDev bt, const RbModelDev* sp, RbBatchDev sb, RaRecipeArgs a) {
 #ifdef RG_EMUL
   RaRecipeLds& F = *(RaRecipeLds*)emul_lds();
@@ -481,6 +515,9 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
       // with the boxes rotated by THESE
       for (int i = 0; i < N; i++) F.gyaw[i] = gy[i * gstride];
       if (a.randomize_goal_rot) for (int i = 0; i < N; i++) F.gyaw[i] += 2.f * RBC_PI * env_u01(a.seed ^ 0xC2B2AE35u, a.step, (unsigned)e, (unsigned)i);
+      // (the fixed placements call set_target_quat inside _sample_next_goal_positions, after the randomisation: their goals have init_quats' yaws, always)
+      if (kind == 7) for (int i = 0; i < N; i++) F.gyaw[i] = 0.f;
+      if (kind == 8) for (int i = 0; i < N; i++) F.gyaw[i] = a.fixed_yaw[i];
       gy = F.gyaw; gstride = 1;
       if (kind <= 1) {
         if (!ra_place(a, N, false, gy, gstride, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
@@ -519,6 +556,12 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
         }
       } else if (kind == 6) {                                          // DominoStateGoal (goals/dominos.py:53-150): the dominos on a circle arc
         if (!ra_domino_arc(a, N, gseed, a.step, (unsigned)e, k, F.gyaw, F.gpos)) a.placement_failed[e] += 1;
+      } else if (kind == 7) {                                          // AttachedBlockStateGoal: a permutation and an origin, then the fixed placement (N = 8: the host checks)
+        float rel[RA_ATTACHED_N][2];
+        ra_attached_table(a, gseed, a.step, (unsigned)e, k, rel);
+        ra_place_fixed(a, RA_ATTACHED_N, rel, F.gpos);
+      } else if (kind == 8) {                                          // ObjectFixedStateGoal: the caller's table
+        ra_place_fixed(a, N, a.fixed_xy, F.gpos);
       } else {                                                         // reach: the object goes to the placement, the goal target_height above it
         if (kind == 3) {
           if (!ra_place(a, 1, true, gy, gstride, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;

@@ -1548,7 +1548,14 @@ int ra_env_recipe_step(rb_batch* b, rb_batch* solver, const ra_recipe_args* args
   for (int k = 0; k < 6; k++) if (a.arm_qposadr[k] < 0 || a.arm_qposadr[k] >= d.nq) return fail("ra_env_recipe_step: arm joint address out of range");
   if (!(a.area_size[0] > 0.f) || !(a.area_size[1] > 0.f)) return fail("ra_env_recipe_step: empty placement area");
   if (a.stabilize_steps < 0 || a.n_random_initial_steps < 0 || a.settle_steps < 0) return fail("ra_env_recipe_step: negative step count");
-  if (a.goal_kind < 0 || a.goal_kind > 6) return fail("ra_env_recipe_step: goal_kind out of range (0 object state, 1 pick-and-place, 2 stack, 3 reach, 4 deterministic reach, 5 train, 6 dominos)");
+  if (a.goal_kind < 0 || a.goal_kind > 8)
+    return fail("ra_env_recipe_step: goal_kind out of range (0 object state, 1 pick-and-place, 2 stack, 3 reach, 4 deterministic reach, 5 train, 6 dominos, 7 attached, 8 fixed)");
+  if (a.goal_kind == 7 && !(a.num_objects == 8 && a.object_size > 0.f)) return fail("ra_env_recipe_step: the attached goal needs num_objects == 8 and object_size > 0");
+  if (a.goal_kind == 7 && !(8.f * a.object_size <= a.area_size[0] && 6.f * a.object_size <= a.area_size[1])) return fail("ra_env_recipe_step: the attached goal's lattice does not fit the placement area");
+  if (a.goal_kind == 8)
+    for (int k = 0; k < a.num_objects; k++)
+      if (!(a.fixed_xy[k][0] >= 0.f && a.fixed_xy[k][0] <= 1.f && a.fixed_xy[k][1] >= 0.f && a.fixed_xy[k][1] <= 1.f) || !(fabsf(a.fixed_yaw[k]) <= 1.0e4f))
+        return fail("ra_env_recipe_step: the fixed goal needs fixed_xy in [0, 1] and finite fixed_yaw");
   if (a.goal_kind == 6 && !(a.object_size > 0.f && a.domino_distance_mul > 0.f)) return fail("ra_env_recipe_step: the domino goal needs object_size > 0 and domino_distance_mul > 0");
   if (a.randomize_goal_rot < 0 || a.randomize_goal_rot > 1) return fail("ra_env_recipe_step: randomize_goal_rot is 0 or 1");
   if ((a.goal_kind == 1 || a.goal_kind == 5) && !(a.height_range[0] <= a.height_range[1])) return fail("ra_env_recipe_step: empty height_range");

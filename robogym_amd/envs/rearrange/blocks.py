@@ -48,7 +48,11 @@ JOINT_DRIFT_THRESHOLD = float(np.deg2rad(1))
 FLAG_FULL_FORWARD = 32
 #: the goal generators of the rearrange block tasks (ra_post_args.goal_kind): ObjectStateGoal (goals/object_state.py), PickAndPlaceGoal (goals/pickandplace.py),
 #: ObjectStackGoal (goals/object_stack_goal.py), ObjectReachGoal / DeterministicReachGoal (goals/object_reach_goal.py)
-GOAL_KINDS = {"object_state": 0, "pickandplace": 1, "stack": 2, "reach": 3, "det-reach": 4, "train": 5, "dominos": 6}      # (train: TrainStateGoal, goals/train_state.py; dominos: DominoStateGoal, goals/dominos.py)
+#: (train: TrainStateGoal, goals/train_state.py; dominos: DominoStateGoal, goals/dominos.py; attached: AttachedBlockStateGoal, goals/attached_block_state.py; fixed:
+#: ObjectFixedStateGoal, goals/object_state_fixed.py)
+GOAL_KINDS = {"object_state": 0, "pickandplace": 1, "stack": 2, "reach": 3, "det-reach": 4, "train": 5, "dominos": 6, "attached": 7, "fixed": 8}
+#: AttachedBlockStateGoal's cells (goals/attached_block_state.py:34-49), in steps of one block: a row of 2, a row of 4, a row of 2
+ATTACHED_LATTICE = np.array([[1, 0], [2, 0], [0, 1], [1, 1], [2, 1], [3, 1], [1, 2], [2, 2]], dtype=np.float64)
 #: GoalArgs.rot_dist_type (goals/object_state.py:127-131) -> ra_post_args.rot_dist_type; "icp" is not built
 ROT_DIST_TYPES = {"full": 0, "mod90": 1, "mod180": 2}
 #: DominoStateGoal's attempts per goal (goals/dominos.py:10)
@@ -213,6 +217,46 @@ def domino_goal(random_state, obj_half, object_distance, table_pos, table_size, 
     return np.zeros((N, 3)), yaws, False
 
 
+def fixed_goal(relative_placements, obj_center, obj_half, table_pos, table_size, area_offset, area_size):
+    """`place_targets_with_fixed_position` (common/utils.py:884-919) = `_place_objects_trial` (:653-716) with `run_collision_check=False`: object i's BODY ORIGIN at
+    `relative_placements[i] * [width, height]` inside the placement area -- the proposal is not corrected by the bounding box's centre in x and y --, z from the box's
+    half height and centre (`obj_center`, `obj_half` [N, 3]) on the table top.  Returns ([N, 3] body origins in world coordinates, True): always valid."""
+    rel = np.asarray(relative_placements, dtype=np.float64)
+    obj_center, obj_half = np.asarray(obj_center, dtype=np.float64), np.asarray(obj_half, dtype=np.float64)
+    table_pos, table_size = np.asarray(table_pos, dtype=np.float64), np.asarray(table_size, dtype=np.float64)
+    prop = rel * [area_size[0], area_size[1]]
+    z = obj_half[:, 2] + 2 * table_size[2] - obj_center[:, 2]
+    placement = np.concatenate([prop, z[:, None]], -1)
+    return placement + [area_offset[0], area_offset[1], 0.0] - table_size + table_pos, True
+
+
+def attached_goal(random_state, obj_center, obj_half, object_size, table_pos, table_size, area_offset, area_size):
+    """`AttachedBlockStateGoal._sample_next_goal_positions` (goals/attached_block_state.py:17-68), draw for draw: a `permutation` of the eight lattice rows (block i
+    goes to the i-th row of the result), one `uniform(low=(rel_w, rel_h), high=(margin_w, margin_h))` for the lattice's origin, then the fixed placement.  `object_size`
+    is the blocks' HALF size; rel_w, rel_h = object_size / (width, height).  Returns ([8, 3], True)."""
+    width, height = area_size[0], area_size[1]
+    rel_w, rel_h = object_size / width, object_size / height
+    block_config = random_state.permutation(ATTACHED_LATTICE * [rel_w * 2, rel_h * 2])
+    config_w, config_h = block_config.max(axis=0)
+    margin_w, margin_h = 1.0 - config_w - rel_w, 1.0 - config_h - rel_h
+    ori_x, ori_y = random_state.uniform(low=(rel_w, rel_h), high=(margin_w, margin_h))
+    block_config = block_config + np.array([[ori_x, ori_y]])
+    return fixed_goal(block_config, obj_center, obj_half, table_pos, table_size, area_offset, area_size)
+
+
+def z_rotation_yaws(init_quats, num_objects):
+    """`init_quats` [N, 4] (w, x, y, z) of ObjectFixedStateGoal -> the yaw of each; the goal rows of this env hold rotations about z only: anything else raises."""
+    if init_quats is None:
+        return np.zeros(num_objects)
+    q = np.asarray(init_quats, dtype=np.float64)
+    if q.shape != (num_objects, 4):
+        raise ValueError("init_quats has shape %r, not (%d, 4)" % (q.shape, num_objects))
+    n = np.linalg.norm(q, axis=-1)
+    if not np.all(np.abs(n - 1.0) < 1e-6) or np.abs(q[:, 1:3]).max() > 1e-9:
+        raise NotImplementedError("init_quats: only unit quaternions of rotations about z are implemented by the batched rearrange env (the goal rows hold yaws), got %r" % (q.tolist(),))
+    return 2.0 * np.arctan2(q[:, 3], q[:, 0])
+
+
 def _parse_object_groups(object_groups, num_objects):
     """`object_groups` -> (mode, counts): "distinct" (None), "single", "sample" (counts drawn per env and episode), or explicit counts -- a list of ints or of the
     reference's `ObjectGroupConfig` fields as dicts, of which `count` alone is built."""
@@ -250,7 +294,8 @@ class BatchedBlockRearrangeEnv:
                  stabilize_object_damping: float = 1.0e-3, control_mode: str = "tcp+roll+yaw", device_reset: bool = False, tcp_solver_mode: str = "mocap_ik",
                  goal_kind: str = "object_state", height_range=(0.05, 0.25), object_size: float = 0.0254, fixed_order: bool = False, target_height: float = 0.1,
                  object_groups="distinct", sample_lam=SAMPLE_LAM, goal_distance_ratio=1.0, goal_distance_min: float = 0.06, pickup_proba: float = 0.0,
-                 stacking_proba: float = 0.0, rot_dist_type: str = "full", randomize_goal_rot: bool = False, model=None, domino_distance_mul: float = 4.0):
+                 stacking_proba: float = 0.0, rot_dist_type: str = "full", randomize_goal_rot: bool = False, model=None, domino_distance_mul: float = 4.0,
+                 relative_placements=None, init_quats=None):
         """`per_env_parameters`: every env carries its own copy of the randomisable model fields (`self.sim.params`, LargeModelSimulation(env_params=True)) -- what
         the reference's simulation randomizers and `stabilize_objects` write into `sim.model`.  On by default (measured cost: 0.7 % of the step,
         profiles/r05_ab_rb_env_params.txt); off: the model's own arrays, no randomizers, no damping change while the objects stabilise.
@@ -268,7 +313,11 @@ class BatchedBlockRearrangeEnv:
         (ra_post_args.rot_dist_type; the tables of parallel quaternions are device tensors built from utils/rotation.py).  `randomize_goal_rot`: every goal's yaw is the
         previous one plus U(0, 2 pi) per object (`rot_randomize_type` "z_axis"), its placement made with the boxes turned by the new yaws.
         `model`: a compiled main world in place of `load_blocks_model(num_objects)` (envs/rearrange/dominos.py: the domino world); goal_kind "dominos" places the goals on a
-        circle arc, `object_size * domino_distance_mul` apart, with per-object goal yaws (DominoStateGoal)."""
+        circle arc, `object_size * domino_distance_mul` apart, with per-object goal yaws (DominoStateGoal).
+        goal_kind "fixed" (ObjectFixedStateGoal): `relative_placements` [N, 2] in [0, 1], each object's body origin relative to the placement area, and `init_quats` [N, 4],
+        the goals' orientations (rotations about z; default identity) -- the same goal every time.  goal_kind "attached" (envs/rearrange/blocks_attached.py,
+        AttachedBlockStateGoal): eight blocks, `object_size` apart from their neighbours' faces, in a 2-4-2 lattice with a random assignment and a random origin.  Both set the
+        goal's orientation themselves: `randomize_goal_rot` has no effect on them, as in the reference."""
         self.B, self.N = int(batch_size), int(num_objects)
         if goal_kind not in GOAL_KINDS:
             raise ValueError("goal_kind %r is not one of %s" % (goal_kind, ", ".join(GOAL_KINDS)))
@@ -280,6 +329,18 @@ class BatchedBlockRearrangeEnv:
         self.rot_dist_type, self.randomize_goal_rot, self.domino_distance_mul = rot_dist_type, bool(randomize_goal_rot), float(domino_distance_mul)
         if self.goal_kind == 6 and not (float(object_size) > 0 and self.domino_distance_mul > 0):
             raise ValueError("goal_kind dominos needs object_size > 0 and domino_distance_mul > 0 (got %r, %r)" % (object_size, domino_distance_mul))
+        if self.goal_kind == 7 and not (self.N == 8 and float(object_size) > 0):
+            raise ValueError("goal_kind attached needs num_objects == 8 and object_size > 0 (got %r, %r)" % (num_objects, object_size))
+        if (relative_placements is not None or init_quats is not None) and self.goal_kind != 8:
+            raise ValueError("relative_placements / init_quats belong to goal_kind \"fixed\" (ObjectFixedStateGoal), not to %r" % (goal_kind,))
+        self.relative_placements, self.init_yaw = None, np.zeros(self.N)
+        if self.goal_kind == 8:
+            if relative_placements is None:
+                raise ValueError("goal_kind fixed needs relative_placements [N, 2]")
+            self.relative_placements = np.array(relative_placements, dtype=np.float64)
+            if self.relative_placements.shape != (self.N, 2) or not np.all((self.relative_placements >= 0.0) & (self.relative_placements <= 1.0)):
+                raise ValueError("relative_placements must be [%d, 2] with every entry in [0, 1], got %r" % (self.N, np.asarray(relative_placements).tolist()))
+            self.init_yaw = z_rotation_yaws(init_quats, self.N)
         self.reach = self.goal_kind in (3, 4)
         self.goal_distance_min, self.pickup_proba, self.stacking_proba = float(goal_distance_min), float(pickup_proba), float(stacking_proba)
         if not (self.goal_distance_min >= 0 and self.pickup_proba >= 0 and self.stacking_proba >= 0 and self.pickup_proba + self.stacking_proba <= 1.0):
@@ -431,7 +492,7 @@ class BatchedBlockRearrangeEnv:
         a.safety_stop_force = 150.0                                      # robot/ur16e/arm_interface.py:46
         a.max_timesteps_per_goal, a.successes_needed, a.use_goal_distance_reward = max_timesteps_per_goal_per_obj * N, successes_needed, int(use_goal_distance_reward)
         a.solver_grip_qposadr, a.solver_grip_act = self.solver_grip_q, self.solver_grip_act
-        a.goal_kind, a.grip_site, a.goal_dist_extra = (0 if self.goal_kind in (5, 6) else self.goal_kind), main.names["site"].index("robot0:grip"), P(self.goal_dist_extra)
+        a.goal_kind, a.grip_site, a.goal_dist_extra = (0 if self.goal_kind >= 5 else self.goal_kind), main.names["site"].index("robot0:grip"), P(self.goal_dist_extra)
         a.rot_dist_type = ROT_DIST_TYPES[rot_dist_type]
         if a.rot_dist_type:      # the tables euler_angle_difference_single_pair walks, in the reference's order (constant data: built once on the host)
             from robogym_amd.utils.rotation import parallel_quat_table
@@ -521,6 +582,9 @@ class BatchedBlockRearrangeEnv:
                 r.obj_group, r.group_mode = P(self.obj_group), int(self.group_mode == "sample")
                 r.sample_lam[0], r.sample_lam[1] = self.sample_lam
             r.randomize_goal_rot, r.domino_distance_mul = int(self.randomize_goal_rot), self.domino_distance_mul
+            if self.goal_kind == 8:
+                for i in range(N):
+                    r.fixed_xy[i][0], r.fixed_xy[i][1], r.fixed_yaw[i] = float(self.relative_placements[i, 0]), float(self.relative_placements[i, 1]), float(self.init_yaw[i])
 
     # ------------------------------------------------------------------ launches
     def _stream(self):
@@ -727,6 +791,8 @@ class BatchedBlockRearrangeEnv:
             yaw = np.stack([randomize_yaw_along_z(self._rng, y) for y in yaw])
         if self.goal_kind == 6:
             return self._domino_goals(len(rows))
+        if self.goal_kind in (7, 8):      # set_target_quat inside _sample_next_goal_positions, AFTER the randomisation: init_quats' yaws, always
+            yaw = np.tile(self.init_yaw, (len(rows), 1))
         return self._goal_positions(rows, yaw), yaw
 
     def _domino_goals(self, R):
@@ -745,6 +811,12 @@ class BatchedBlockRearrangeEnv:
         R, N, kind = len(rows), self.N, self.goal_kind
         if kind == 6:          # (the arc's positions; its yaws go with them through _next_goal)
             return self._domino_goals(R)[0]
+        if kind in (7, 8):     # the fixed placements: AttachedBlockStateGoal's lattice (a permutation and an origin per env) / ObjectFixedStateGoal's table
+            offset, size = self.placement_area()
+            where = (self.obj_center, self.obj_half, self.table_pos, self.table_size, offset, size)
+            if kind == 8:
+                return np.tile(fixed_goal(self.relative_placements, *where)[0], (R, 1, 1))
+            return np.array([attached_goal(self._rng, self.obj_center, self.obj_half, self.object_size, *where[2:])[0] for _ in range(R)]).reshape(R, N, 3)
         if kind == 5:          # TrainStateGoal: goals near the objects' current positions, then one in the air or a tower (goals/train_state.py:81-113)
             idx = torch.as_tensor(rows, device=self.device, dtype=torch.long)
             qpos = self.sim.qpos[idx].cpu().numpy().astype(np.float64)

@@ -13,14 +13,14 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
-from robogym_amd.envs.rearrange import blocks, blocks_pickandplace, blocks_reach, blocks_stack, blocks_train, dominos, ycb, ycb_pickandplace  # noqa: E402
+from robogym_amd.envs.rearrange import blocks, blocks_attached, blocks_pickandplace, blocks_reach, blocks_stack, blocks_train, dominos, ycb, ycb_pickandplace  # noqa: E402
 
 CASES = [("blocks (5)", blocks.make_env, {}), ("blocks_pickandplace (5)", blocks_pickandplace.make_env, {"num_objects": 5}),
          ("blocks_stack (5)", blocks_stack.make_env, {"num_objects": 5}), ("blocks_pickandplace (1, default)", blocks_pickandplace.make_env, {}),
          ("blocks_stack (2, default)", blocks_stack.make_env, {}), ("blocks_reach (1, state)", blocks_reach.make_env, {}),
          ("blocks_reach (1, det-state)", blocks_reach.make_env, {"goal_generation": "det-state"}), ("ycb (8)", ycb.make_env, {}),
          ("ycb_pickandplace (8)", ycb_pickandplace.make_env, {}), ("blocks_train (5)", blocks_train.make_env, {}), ("dominos (5, train goal)", dominos.make_env, {}),
-         ("dominos (5, holdout: arc goal)", dominos.make_env, {"is_holdout": True})]
+         ("dominos (5, holdout: arc goal)", dominos.make_env, {"is_holdout": True}), ("attached (8)", blocks_attached.make_env, {})]
 
 
 def main():
