@@ -358,6 +358,14 @@ int rg_debug_size(void);
 /* bytes of LDS one env occupies in the rollout configuration (diagnostic); rg_lds_bytes_cfg: any configuration */
 int rg_lds_bytes(void);
 int rg_lds_bytes_cfg(int config);
+/* persistent workgroups per CU of the substep-granular dispatch: min(LDS granules per CU / granules per env, 4 x the waves per SIMD
+ * the kernel's registers are budgeted for) */
+int rg_items_per_cu(void);
+/* The step kernel of a configuration as compiled and as the runtime places it: out[0] registers per lane (hipFuncAttributes.numRegs),
+ * out[1] static LDS bytes, out[2] dynamic LDS bytes of a launch, out[3] hipOccupancyMaxActiveBlocksPerMultiprocessor at that LDS size.
+ * config: RG_CFG_ROLLOUT / RG_CFG_LARGE (rg_step_kernel) or RG_CFG_ITEMS (rg_step_items_kernel, the rollout capacities). */
+enum { RG_CFG_ITEMS = 2 };
+int rg_kernel_resources(int config, int* out);
 /* ---- Large-model path (rb_kernel.h): models beyond the compile-time layout of the Shadow-hand kernel -- BASELINE.json
  * configs[2], dactyl/full_perpendicular (/root/reference/robogym/envs/dactyl/full_perpendicular.py:92-136: nv 168, 135 bodies,
  * condim-6 mesh hulls, njmax 2000 / nconmax 200 from cube_env.py:239-242).  Same blob format (plus the b_* tables of

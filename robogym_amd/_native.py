@@ -25,6 +25,7 @@ class StepArgs(ctypes.Structure):
 
 
 RG_CFG_ROLLOUT, RG_CFG_LARGE = 0, 1
+RG_CFG_ITEMS = 2   # rg_kernel_resources only: the substep-granular kernel of the rollout capacities
 RG_POST_NDRAW = 2 + 4 + 3 + 20
 
 
@@ -176,7 +177,7 @@ EXPORTS = [
     "rb_batch_field_ptr", "rb_batch_step", "rb_batch_step_ex", "rb_env_post_step", "rb_post_args_size", "rb_cube_ops", "rb_batch_step_tcp", "ra_env_post_step", "ra_post_args_size",
     "rg_blob_entry", "rg_model_blob_keys", "rb_model_blob_keys", "rg_compile_mjcf", "rb_compile_mjcf", "rg_compile_mjcf_blob", "rg_blob_free",
     "rb_model_enable_env_params", "rb_prm_layout", "rb_batch_set_action_limits", "ra_env_recipe_step", "ra_recipe_args_size", "rb_tcp_args_size", "rb_multi_begin", "rb_multi_launch",
-    "rg_wrap_layout", "rg_wrap_pre_step", "rg_wrap_post_step", "rg_wrap_args_size",
+    "rg_wrap_layout", "rg_wrap_pre_step", "rg_wrap_post_step", "rg_wrap_args_size", "rg_items_per_cu", "rg_kernel_resources",
 ]
 EXPORTS_SETCONST = ["rb_batch_set_constants"]      # include/rgstep_setconst.h (EXPORTS is what include/rgstep.h itself declares)
 
@@ -219,6 +220,8 @@ def bind(path):
     L.rg_lds_bytes.restype = ci
     L.rg_lds_bytes_cfg.restype = ci
     L.rg_lds_bytes_cfg.argtypes = [ci]
+    L.rg_items_per_cu.restype = ci
+    L.rg_kernel_resources.argtypes = [ci, ctypes.POINTER(ci)]
     L.rg_batch_enable_env_params.argtypes = [vp]
     L.rg_prm_layout.argtypes = [ctypes.POINTER(ci), ci]
     L.rg_xdata_layout.argtypes = [ctypes.POINTER(ci), ci]

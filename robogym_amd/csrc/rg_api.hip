@@ -150,7 +150,6 @@ struct DeviceGuard {
 #define RB_CONW 24           /* (= rb_types.h; the env kernels and the host code below see the large configuration's width unless they ask per model) */
 #include "rb_env_kernel.h"
 #include "ra_env_kernel.h"
-#define RG_WAVES_PER_SIMD_HOST 3   /* = RG_WAVES_PER_SIMD of rg_kernel.h (its default) */
 
 static thread_local std::string g_err;
 static int fail(const std::string& msg) { g_err = msg; return -1; }
@@ -269,6 +268,40 @@ const char* rg_last_error(void) { return g_err.c_str(); }
 int rg_debug_size(void) { return RG_DBG_SIZE; }
 int rg_lds_bytes(void) { return (int)rgs::rg_lds_launch_bytes(false); }
 int rg_lds_bytes_cfg(int config) { return (int)(config == RG_CFG_LARGE ? rgl::rg_lds_launch_bytes(false) : rgs::rg_lds_launch_bytes(false)); }
+// persistent workgroups per CU of the substep-granular dispatch: what the LDS image lets onto a CU (160 KiB in granules of 1280 B),
+// capped by the waves per SIMD the kernel's registers are budgeted for
+int rg_items_per_cu(void) {
+  const int granules = (int)((rgi::rg_lds_launch_bytes(false) + 1279) / 1280), per_cu_lds = (160 * 1024 / 1280) / granules;
+  return per_cu_lds < 4 * rgi::rg_waves_per_simd ? per_cu_lds : 4 * rgi::rg_waves_per_simd;
+}
+#if defined(RG_CAP_HIST) && !defined(RG_EMUL)
+// analysis build only (not part of the ABI): the capacity histograms of the rollout (0), large (1) and substep-granular (2) configurations, 192 words each
+int rg_cap_hist_read(int config, unsigned int* out) {
+  HIPCHK(config == 1 ? hipMemcpyFromSymbol(out, HIP_SYMBOL(rgl::rg_cap_hist), 192 * 4) : config == 2 ? hipMemcpyFromSymbol(out, HIP_SYMBOL(rgi::rg_cap_hist), 192 * 4)
+                                                                                                      : hipMemcpyFromSymbol(out, HIP_SYMBOL(rgs::rg_cap_hist), 192 * 4));
+  return 0;
+}
+#endif
+// what the compiler and the runtime say about a configuration's step kernel (RG_CFG_ROLLOUT, RG_CFG_LARGE, RG_CFG_ITEMS):
+// out = registers per lane, static LDS bytes, dynamic LDS bytes of a launch, resident workgroups per CU at that LDS size
+int rg_kernel_resources(int config, int* out) {
+#ifdef RG_EMUL
+  (void)config; (void)out;
+  return fail("rg_kernel_resources: the emulation harness has no compiled kernels");
+#else
+  if (!out) return fail("rg_kernel_resources: null output");
+  const void* fn = config == RG_CFG_ROLLOUT ? (const void*)rgs::rg_step_kernel : config == RG_CFG_LARGE ? (const void*)rgl::rg_step_kernel
+                 : config == RG_CFG_ITEMS ? (const void*)rgi::rg_step_items_kernel : nullptr;
+  if (!fn) return fail("rg_kernel_resources: unknown kernel configuration");
+  const size_t dyn = config == RG_CFG_LARGE ? rgl::rg_lds_launch_bytes(false) : config == RG_CFG_ITEMS ? rgi::rg_lds_launch_bytes(false) : rgs::rg_lds_launch_bytes(false);
+  hipFuncAttributes attr;
+  HIPCHK(hipFuncGetAttributes(&attr, fn));
+  int blocks = 0;
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, RG_WAVE, dyn));
+  out[0] = attr.numRegs; out[1] = (int)attr.sharedSizeBytes; out[2] = (int)dyn; out[3] = blocks;
+  return 0;
+#endif
+}
 
 rg_model* rg_model_create(const void* blob, size_t nbytes, char* err, int errlen) {
   auto bail = [&](const std::string& msg, rg_model* m) { return create_failed(msg, m, rg_model_free, err, errlen); };
@@ -593,9 +626,7 @@ static void rg_items_probe(rg_batch* b) {
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, b->device) != hipSuccess) return;
   const int cus = prop.multiProcessorCount;
-  // wave slots: LDS granules (1280 B) per CU / per workgroup, capped by the 3 waves per SIMD the kernel is compiled for
-  const int per_cu_lds = (160 * 1024) / (int)(((rgi::rg_lds_launch_bytes(false) + 1279) / 1280) * 1280);
-  const int per_cu = per_cu_lds < 4 * RG_WAVES_PER_SIMD_HOST ? per_cu_lds : 4 * RG_WAVES_PER_SIMD_HOST;
+  const int per_cu = rg_items_per_cu();   // wave slots per CU; the probe below launches the grid the dispatch will use
   int* counts = nullptr;
   if (hipMalloc((void**)&counts, 16 * 4) != hipSuccess) return;
   (void)hipMemset(counts, 0, 16 * 4);

@@ -78,7 +78,7 @@ typedef const RG_AS4 RgLaunch& RgLRef;
 #ifdef RG_EMUL
 #define RG_STAGE_BIG static inline
 #else
-#define RG_STAGE_BIG __device__ __forceinline__   /* the register-hungriest stages stay in the kernel body: a call would save/restore ~30 callee-saved VGPRs through scratch */
+#define RG_STAGE_BIG __device__ __forceinline__   /* stays in the kernel body: a call would save/restore ~30 callee-saved VGPRs through scratch (the collision stage; the solver is a call, see st_solve) */
 #endif
 // env handled by this workgroup: the launch may carry a permutation (longest-expected-first dispatch order)
 #ifdef RG_EMUL
@@ -344,7 +344,15 @@ static float rg_wchk_max = 0.f; static int rg_wchk_n = 0, rg_wchk_rows = 0;   //
 #ifndef RG_SENSORS
 #define RG_SENSORS 0   /* 1: this configuration evaluates data.sensordata (launch flag bit 5); its own instantiation so that the hot configurations carry none of it */
 #endif
+// Register budget of the step kernels, as resident waves per SIMD (3: <= 168 VGPRs, so that the LDS-permitted 12 envs per CU are also register-permitted; measured
+// +3 % over the 256-VGPR build at 8 per CU in spite of ~80 spilled registers, profiles/r02_ab.txt).  4 (<= 128 VGPRs) with an LDS image of 9 granules, 14 envs per CU,
+// was measured and not kept: the extra spills cost 6.7 %, the two further residents gave 6.3 % back, and the smaller contact capacities hand env.steps to the large
+// configuration (profiles/four_waves.txt).
+#ifndef RG_WAVES_PER_SIMD
+#define RG_WAVES_PER_SIMD 3
+#endif
 namespace RG_NS {
+enum { rg_waves_per_simd = RG_WAVES_PER_SIMD };   // (the host sizes the persistent grid with it)
 #define RG_MAXPYR (RG_MAXCON * 6)
 #define RG_PSLOTS ((RG_MAXPYR + RG_WAVE - 1) / RG_WAVE)   // pyramid rows a lane owns during a line search
 
@@ -418,6 +426,11 @@ struct RgLds {
   };
   float prof[RG_NPROF];   // LAST: launches without the profiling flag do not allocate it (rg_lds_launch_bytes)
 };
+#if defined(RG_CAP_HIST) && !defined(RG_EMUL)
+// analysis build (-DRG_CAP_HIST, profiles/four_waves.txt): what a substep asks of the contact capacities, counted over every launch of this configuration.
+// Words 0..63: contacts kept by the narrowphase (at most RG_MAXCON); words 64..191: Jacobian pool words they need, in bins of 16 (the last bin: 2032 and more).
+__device__ unsigned int rg_cap_hist[192];
+#endif
 // dynamic LDS bytes of a launch
 static inline size_t rg_lds_launch_bytes(bool profiling) { return profiling ? sizeof(RgLds) : offsetof(RgLds, prof); }
 
@@ -1653,6 +1666,10 @@ __device__ __forceinline__ void rg_make_constraint(RgM m, RgLds& s, const float*
   {
     int c = LANE, off = 0, sz = 0;
     if (c < ncon) { for (int q = 0; q < c; q++) off += nbasis(s.c_dim[q]) * s.c_nnz[q]; sz = nbasis(s.c_dim[c]) * s.c_nnz[c]; s.c_off[c] = off; }
+#if defined(RG_CAP_HIST) && !defined(RG_EMUL)
+    if (ncon > 0 && c == ncon - 1) { atomicAdd(rg_cap_hist + (ncon < 63 ? ncon : 63), 1u); const int bin = (off + sz) >> 4; atomicAdd(rg_cap_hist + 64 + (bin < 127 ? bin : 127), 1u); }
+    if (ncon == 0 && c == 0) { atomicAdd(rg_cap_hist, 1u); atomicAdd(rg_cap_hist + 64, 1u); }
+#endif
     int firstbad = wave_min_i((c < ncon && off + sz > RG_CPOOL) ? c : 0x7fffffff);
     if (firstbad < ncon) { ncon = firstbad; if (LANE == 0) { s.ncon = ncon; s.status |= RG_STATUS_CON_FULL; } }
   }
@@ -2889,7 +2906,11 @@ RG_STAGE void st_factor_smooth(RgCtx c) { RgLds& s = RG_S(); rg_ltdl_factor_solv
 #else
 #define RG_SOLVE_PRIO(level) do { } while (0)
 #endif
-RG_STAGE_BIG int st_solve(RgCtx c, float warm) { RgM m = RG_M(c); int nefc = 0; RG_SOLVE_PRIO(2); int it = rg_solve<false>(m, RG_S(), rg_prm(m, RG_L(c)), nefc, RG_L(c).flags, warm); RG_SOLVE_PRIO(0); return it | (nefc << 8); }
+// The solver is a real call although it is the register-hungriest stage: inlined, its ~18 k instructions shared one register allocation with the collision stage and the
+// kernel body, whose live values (state registers, launch scalars) were then spilled and reloaded INSIDE the Newton and line-search loops; as a call it pays the
+// callee-saved registers once per substep instead.  +4.0 % on the headline at the same 168 VGPRs, bit-identical results (profiles/four_waves.txt: the same move for the
+// collision stage, or for both, measured +0.2 % and +1.9 %).
+RG_STAGE int st_solve(RgCtx c, float warm) { RgM m = RG_M(c); int nefc = 0; RG_SOLVE_PRIO(2); int it = rg_solve<false>(m, RG_S(), rg_prm(m, RG_L(c)), nefc, RG_L(c).flags, warm); RG_SOLVE_PRIO(0); return it | (nefc << 8); }
 #if RG_SENSORS
 RG_STAGE_BIG int st_solve_sensors(RgCtx c, float warm) { RgM m = RG_M(c); int nefc = 0; RG_SOLVE_PRIO(2); int it = rg_solve<true>(m, RG_S(), rg_prm(m, RG_L(c)), nefc, RG_L(c).flags, warm); RG_SOLVE_PRIO(0); return it | (nefc << 8); }
 #endif
@@ -2911,11 +2932,6 @@ RG_STAGE void st_dump(RgCtx c, int which, int nefc, int iters) {
 #define RG_MAKE_CTX() RgCtx c{mp, &launch}
 #else
 #define RG_MAKE_CTX() RgCtx c{mp, (const void*)((const RG_AS4 char*)__builtin_amdgcn_kernarg_segment_ptr() + 8)}
-#endif
-// (RG_WAVES_PER_SIMD 3: <= 168 VGPRs, so that the LDS-permitted 9 envs per CU are also register-permitted; measured
-//  +3 % over the 256-VGPR build at 8 per CU in spite of ~80 spilled registers, profiles/r02_ab.txt)
-#ifndef RG_WAVES_PER_SIMD
-#define RG_WAVES_PER_SIMD 3
 #endif
 #if !RG_ITEMS
 __global__ void __launch_bounds__(RG_WAVE, RG_WAVES_PER_SIMD) rg_step_kernel(const RgModelDev* mp, RgLaunch launch) {
