@@ -660,15 +660,26 @@ __device__ __forceinline__ float rg_wrap(v3& w0, v3& w1, v3 x0, v3 x1, v3 gpos, 
 
 // tendon lengths and Jacobians on their static dof supports; actuator lengths
 __device__ __forceinline__ void rg_tendon(RgM m, RgLds& s) {
+  // the actuator words of the last loop are requested with the tendon's (RG_MAXU <= RG_WAVE: one actuator per lane), the joint
+  // position address of a joint transmission as soon as its id is there; a path record is requested one stretch ahead of its use
+  int a_id = 0, a_type = 1, a_qadr = 0; float a_gear = 0;
+  if (LANE < m.nu) { a_id = m.actuator_trnid[LANE]; a_type = m.actuator_trntype[LANE]; a_gear = m.actuator_gear[LANE]; }
+  int p_r0 = 0, p_r1 = 0, p_d0 = -1, p_d1 = -1, p_d2 = -1, p_d3 = -1;
+  if (LANE < m.ntendon) {
+    p_r0 = m.ten_path_adr[LANE]; p_r1 = m.ten_path_adr[LANE + 1];
+    const int* td = m.ten_dofs + 4 * LANE; p_d0 = td[0]; p_d1 = td[1]; p_d2 = td[2]; p_d3 = td[3];
+  }
+  if (LANE < m.nu && a_type == 0) a_qadr = m.jnt_qposadr[a_id];
   PFOR(t, m.ntendon) {
     // the tendon's path as static 8-word records (kernel_tables.py k_ten_path): one load per stretch, no index chains
-    int r0 = m.ten_path_adr[t], r1 = m.ten_path_adr[t + 1];
-    const int* td = m.ten_dofs + 4 * t;
-    int d0 = td[0], d1 = td[1], d2 = td[2], d3 = td[3];
+    int r0 = p_r0, r1 = p_r1;
+    int d0 = p_d0, d1 = p_d1, d2 = p_d2, d3 = p_d3;
     float J[4] = {0, 0, 0, 0}, L = 0;
+    rgf4 na, nb; na.x = na.y = na.z = na.w = 0.f; nb = na;
+    if (r0 < r1) { const rgf4* R = (const rgf4*)m.ten_path + 2 * r0; na = R[0]; nb = R[1]; }
     for (int r = r0; r < r1; r++) {
-      const rgf4* R = (const rgf4*)m.ten_path + 2 * r;
-      rgf4 ra = R[0], rb = R[1];
+      const rgf4 ra = na, rb = nb;
+      if (r + 1 < r1) { const rgf4* R = (const rgf4*)m.ten_path + 2 * (r + 1); na = R[0]; nb = R[1]; }
       int kind = __builtin_bit_cast(int, ra.x), w1 = __builtin_bit_cast(int, ra.y), w2 = __builtin_bit_cast(int, ra.z);
       if ((kind & 15) == 0) {   // fixed tendon: coef * joint position
         float coef = ra.w;
@@ -715,29 +726,58 @@ __device__ __forceinline__ void rg_tendon(RgM m, RgLds& s) {
     for (int e = 0; e < 4; e++) s.tenJ[4 * t + e] = J[e];
   }
   SYNC();
-  PFOR(u, m.nu) {
-    int id = m.actuator_trnid[u];
-    s.actlen[u] = m.actuator_gear[u] * (m.actuator_trntype[u] == 0 ? s.qpos[m.jnt_qposadr[id]] : s.tenlen[id]);
-  }
+  static_assert(RG_MAXU <= RG_WAVE && RG_MAXTEN <= RG_WAVE, "tendon stage: one lane per tendon / actuator");
+  PFOR(u, m.nu) s.actlen[u] = a_gear * (a_type == 0 ? s.qpos[a_qadr] : s.tenlen[a_id]);
   SYNC();
 }
 
 // composite inertias (subtree gathers), sparse M, tree-sparse L'DL factorisation
+// sum of base[STRIDE * i] over the set bits i of `bits`, added in ascending order of i starting from +0 (what the loop "one bit, one
+// LDS read, one add" computes, to the bit: the running sum starts at +0 and so never is -0, and adding the +0 of a slot past the
+// last bit changes no value).  The reads of up to eight terms are in flight together: one LDS round trip per eight, not per term.
+template <int STRIDE> __device__ __forceinline__ float rg_mask_sum(const float* base, uint32_t bits) {
+  float acc = 0;
+  while (bits) {
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) { const float x = base[STRIDE * (bits ? __builtin_ctz(bits) : 0)]; v[i] = bits ? x : 0.f; bits &= bits - 1; }
+#pragma unroll
+    for (int i = 0; i < 8; i++) acc += v[i];
+  }
+  return acc;
+}
 __device__ __forceinline__ void rg_crb(RgM m, RgLds& s, const float* P, const int* subtree_adr, const int* subtree) {
-  for (int w = LANE; w < m.nbody * 10; w += RG_WAVE) {
-    int b = w / 10, k = w - 10 * b;
-    float acc = 0;
-    for (uint32_t bits = (uint32_t)m.subtree_mask[b]; bits; bits &= bits - 1) acc += s.cinert[10 * __builtin_ctz(bits) + k];
-    s.crb[w] = acc;
+  // every round's subtree mask and inertia-matrix entry requested before the first sum, the armature of the diagonal entries as soon as
+  // the entry word says which they are (two waits on global memory for the stage, not one or two per round)
+  constexpr int NE = (RG_MAXNM + RG_WAVE - 1) / RG_WAVE;
+  const int nM = m.nM;
+  int ijb[NE]; float arm[NE];
+  {
+    constexpr int NR = (RG_MAXBODY * 10 + RG_WAVE - 1) / RG_WAVE;
+    const int n = m.nbody * 10;
+    uint32_t mask[NR];
+#pragma unroll
+    for (int r = 0; r < NR; r++) { const int w = LANE + RG_WAVE * r; mask[r] = w < n ? (uint32_t)m.subtree_mask[w / 10] : 0u; }
+#pragma unroll
+    for (int r = 0; r < NE; r++) { const int e = LANE + RG_WAVE * r; ijb[r] = e < nM ? m.M_ijb[e] : 0x0100; }   // (past the end: an off-diagonal entry, not used)
+#pragma unroll
+    for (int r = 0; r < NE; r++) { const int i = ijb[r] & 255, j = (ijb[r] >> 8) & 255; arm[r] = i == j ? P[RG_PRM_DOF_ARMATURE + i] : 0.f; }
+#pragma unroll
+    for (int r = 0; r < NR; r++) {
+      const int w = LANE + RG_WAVE * r, b = w / 10, k = w - 10 * b;
+      if (w < n) s.crb[w] = rg_mask_sum<10>(s.cinert + k, mask[r]);
+    }
   }
   SYNC();
-  PFOR(e, m.nM) {
-    const int ijb = m.M_ijb[e], i = ijb & 255, j = (ijb >> 8) & 255;
+#pragma unroll
+  for (int r = 0; r < NE; r++) {
+    const int e = LANE + RG_WAVE * r, i = ijb[r] & 255, j = (ijb[r] >> 8) & 255;
+    if (e >= nM) continue;
     float buf[6];
-    mul_inert_vec(buf, s.crb + 10 * (ijb >> 16), s.cdof + 6 * i);
+    mul_inert_vec(buf, s.crb + 10 * (ijb[r] >> 16), s.cdof + 6 * i);
     const float* c = s.cdof + 6 * j;
     float v = c[0] * buf[0] + c[1] * buf[1] + c[2] * buf[2] + c[3] * buf[3] + c[4] * buf[4] + c[5] * buf[5];
-    if (i == j) v += P[RG_PRM_DOF_ARMATURE + i];
+    if (i == j) v += arm[r];
     s.Msp[e] = v;
   }
   SYNC();
@@ -1477,41 +1517,92 @@ __device__ __forceinline__ void rg_collision(RgCtx c, RgM m, RgLds& s, const flo
 
 // ------------------------------------------------------------------------------------------------- velocity stage
 __device__ __forceinline__ void rg_velocity(RgM m, RgLds& s, const float* P, const uint32_t* dof_velmask, const int* subtree_adr, const int* subtree) {
+  // Every model word and parameter-row entry the stage reads is addressed by the lane alone (one trip of every per-dof, per-tendon and
+  // per-body loop: RG_MAXNV, RG_MAXTEN, RG_MAXBODY <= RG_WAVE), so all of it is requested here, ahead of the first use: the stage waits for
+  // global memory once for the lane-indexed words and once for the few whose address comes out of them (joint of the dof, bounding radii of
+  // the body's geoms, tendon entries of the dof), not once per read.
+  static_assert(RG_MAXNV <= RG_WAVE && RG_MAXTEN <= RG_WAVE && RG_MAXBODY <= RG_WAVE, "velocity stage: one lane per dof / tendon / body");
+  constexpr int NSUB = (RG_MAXBODY * 6 + RG_WAVE - 1) / RG_WAVE, NRB = 4 /* bounding radii requested ahead per body */, NDT = 2 /* tendon entries requested ahead per dof */;
+  const int nv = m.nv, nt = m.ntendon, nb = m.nbody, d = LANE, t = LANE, b = 1 + LANE;
+  int dj = 0; uint32_t vm[2] = {0u, 0u}; rgf4 dr0; dr0.x = dr0.y = dr0.z = dr0.w = 0.f; float spring_ref = 0, damping = 0;
+  if (d < nv) {
+    dj = m.dof_jntid[d]; dr0 = ((const rgf4*)m.dof_rec)[2 * d]; spring_ref = m.dof_rec[8 * d + 4];   // dof record: body, tendon entries, joint stiffness, qposadr | spring reference
+    vm[0] = dof_velmask[2 * d]; vm[1] = dof_velmask[2 * d + 1]; damping = P[RG_PRM_DOF_DAMPING + d];
+  }
+  int td[4] = {-1, -1, -1, -1}; float t_stiff = 0, t_spring = 0, t_damp = 0;
+  if (t < nt) {
+    for (int e = 0; e < 4; e++) td[e] = m.ten_dofs[4 * t + e];
+    t_stiff = m.tendon_stiffness[t]; t_spring = m.tendon_lengthspring[t]; t_damp = m.tendon_damping[t];
+  }
+  uint32_t bm[2] = {0u, 0u}; int ga = 0, gn = 0;
+  if (b < nb) { bm[0] = m.body_dofmask[2 * b]; bm[1] = m.body_dofmask[2 * b + 1]; ga = m.body_geomadr[b]; gn = m.body_geomnum[b]; }
+  uint32_t sub[NSUB];
+#pragma unroll
+  for (int k0 = 0; k0 < NSUB; k0++) { const int w = LANE + RG_WAVE * k0, sb = w / 6; sub[k0] = (w < nb * 6 && sb > 0) ? (uint32_t)m.subtree_mask[sb] : 0u; }
+  const int g0a = m.body_geomadr[0], g0n = m.body_geomnum[0];
+  const float grav0 = P[RG_PRM_GRAVITY], grav1 = P[RG_PRM_GRAVITY + 1], grav2 = P[RG_PRM_GRAVITY + 2], gsmax = fmaxf(P[RG_PRM_GEOM_SCALE], 1.f);
+  // second batch: the words whose address is one of the above
+  int jt = 0, jda = 0, dten[2 * NDT]; const int w0 = __builtin_bit_cast(int, dr0.x), tq0 = (w0 >> 8) & 255, tq1 = (w0 >> 16) & 255;
+#pragma unroll
+  for (int i = 0; i < 2 * NDT; i++) dten[i] = 0;
+  if (d < nv) {
+    jt = m.jnt_type[dj]; jda = m.jnt_dofadr[dj];
+#pragma unroll
+    for (int i = 0; i < NDT; i++) if (tq0 + i < tq1) { dten[2 * i] = m.dof_ten[2 * (tq0 + i)]; dten[2 * i + 1] = m.dof_ten[2 * (tq0 + i) + 1]; }
+  }
+  float rbound[NRB];
+#pragma unroll
+  for (int k = 0; k < NRB; k++) rbound[k] = k < gn ? m.geom_rbound[ga + k] : 0.f;
+
   // cdof_dot: spatial velocity accumulated over the dofs "before" d on its chain, crossed with cdof
-  PFOR(d, m.nv) {
+  if (d < nv) {
     float cv[6] = {0, 0, 0, 0, 0, 0};
     for (int h = 0; h < 2; h++) {
-      uint32_t bits = dof_velmask[2 * d + h];
-      while (bits) { int a = __builtin_ctz(bits) + 32 * h; bits &= bits - 1; float q = s.qvel[a]; for (int e = 0; e < 6; e++) cv[e] += s.cdof[6 * a + e] * q; }
+      uint32_t bits = vm[h];
+      while (bits) {   // four chain elements' LDS reads together, added in the chain's (ascending) order
+        float q[4], c[4][6]; bool on[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          on[i] = bits != 0; const int a = on[i] ? __builtin_ctz(bits) + 32 * h : 0; bits &= bits - 1;
+          q[i] = s.qvel[a]; for (int e = 0; e < 6; e++) c[i][e] = s.cdof[6 * a + e];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) if (on[i]) for (int e = 0; e < 6; e++) cv[e] += c[i][e] * q[i];
+      }
     }
-    int j = m.dof_jntid[d];
-    if (m.jnt_type[j] == RG_JNT_FREE && d - m.jnt_dofadr[j] < 3) { for (int e = 0; e < 6; e++) s.cdofdot[6 * d + e] = 0; }
+    if (jt == RG_JNT_FREE && d - jda < 3) { for (int e = 0; e < 6; e++) s.cdofdot[6 * d + e] = 0; }
     else cross_motion(s.cdofdot + 6 * d, cv, s.cdof + 6 * d);
   }
-  PFOR(t, m.ntendon) {
+  if (t < nt) {
     float v = 0;
-    for (int e = 0; e < 4; e++) { int d = m.ten_dofs[4 * t + e]; if (d >= 0) v += s.tenJ[4 * t + e] * s.qvel[d]; }
+    for (int e = 0; e < 4; e++) { int dd = td[e]; if (dd >= 0) v += s.tenJ[4 * t + e] * s.qvel[dd]; }
     s.tenvel[t] = v;
-    s.tenfrc[t] = m.tendon_stiffness[t] * (m.tendon_lengthspring[t] - s.tenlen[t]) - m.tendon_damping[t] * v;
+    s.tenfrc[t] = t_stiff * (t_spring - s.tenlen[t]) - t_damp * v;
   }
   SYNC();
   // body velocities / bias accelerations by chain gathers, then body forces
-  PFOR(k, m.body_geomnum[0]) s.gspeed[m.body_geomadr[0] + k] = 0;
-  for (int b = 1 + LANE; b < m.nbody; b += RG_WAVE) {
-    float cv[6] = {0, 0, 0, 0, 0, 0}, ca[6] = {0, 0, 0, -P[RG_PRM_GRAVITY], -P[RG_PRM_GRAVITY + 1], -P[RG_PRM_GRAVITY + 2]};
+  PFOR(k, g0n) s.gspeed[g0a + k] = 0;
+  if (b < nb) {
+    float cv[6] = {0, 0, 0, 0, 0, 0}, ca[6] = {0, 0, 0, -grav0, -grav1, -grav2};
     for (int h = 0; h < 2; h++) {
-      uint32_t bits = m.body_dofmask[2 * b + h];
-      while (bits) {
-        int a = __builtin_ctz(bits) + 32 * h; bits &= bits - 1; float q = s.qvel[a];
-        for (int e = 0; e < 6; e++) { cv[e] += s.cdof[6 * a + e] * q; ca[e] += s.cdofdot[6 * a + e] * q; }
+      uint32_t bits = bm[h];
+      while (bits) {   // two chain elements' LDS reads together
+        float q[2], c[2][6], cd[2][6]; bool on[2];
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+          on[i] = bits != 0; const int a = on[i] ? __builtin_ctz(bits) + 32 * h : 0; bits &= bits - 1;
+          q[i] = s.qvel[a]; for (int e = 0; e < 6; e++) { c[i][e] = s.cdof[6 * a + e]; cd[i][e] = s.cdofdot[6 * a + e]; }
+        }
+#pragma unroll
+        for (int i = 0; i < 2; i++) if (on[i]) for (int e = 0; e < 6; e++) { cv[e] += c[i][e] * q[i]; ca[e] += cd[i][e] * q[i]; }
       }
     }
     {  // speed bound of the body's geoms: |v(geom centre)| + |omega| * bounding radius (radius of a size-scaled geom: conservative factor for all)
-      const float gsmax = fmaxf(P[RG_PRM_GEOM_SCALE], 1.f);
       v3 w = mk3(cv[0], cv[1], cv[2]), vo = mk3(cv[3], cv[4], cv[5]), og = ld3(s.org + 3 * s.b2org[b]);
       float wn = norm(w);
-      int ga = m.body_geomadr[b], gn = m.body_geomnum[b];
-      for (int k = 0; k < gn; k++) s.gspeed[ga + k] = norm(vo + cross(w, ld3(s.gpos + 3 * (ga + k)) - og)) + wn * (m.geom_rbound[ga + k] * gsmax);
+#pragma unroll
+      for (int k = 0; k < NRB; k++) if (k < gn) s.gspeed[ga + k] = norm(vo + cross(w, ld3(s.gpos + 3 * (ga + k)) - og)) + wn * (rbound[k] * gsmax);
+      for (int k = NRB; k < gn; k++) s.gspeed[ga + k] = norm(vo + cross(w, ld3(s.gpos + 3 * (ga + k)) - og)) + wn * (m.geom_rbound[ga + k] * gsmax);
     }
     float t1[6], t2[6], t3[6];
     mul_inert_vec(t1, s.cinert + 10 * b, ca);
@@ -1521,26 +1612,25 @@ __device__ __forceinline__ void rg_velocity(RgM m, RgLds& s, const float* P, con
   }
   SYNC();
   {  // subtree sums in place: every lane gathers its (<= RG_MAXBODY * 6 / 64 = 3) sums first, then the wave overwrites
-    float acc[(RG_MAXBODY * 6 + RG_WAVE - 1) / RG_WAVE];
+    float acc[NSUB];
 #pragma unroll
-    for (int k0 = 0; k0 < (RG_MAXBODY * 6 + RG_WAVE - 1) / RG_WAVE; k0++) {
-      int w = LANE + RG_WAVE * k0, b = w / 6, k = w - 6 * b; float a = 0;
-      if (w < m.nbody * 6 && b > 0) for (uint32_t bits = (uint32_t)m.subtree_mask[b]; bits; bits &= bits - 1) a += s.cacc[6 * __builtin_ctz(bits) + k];
-      acc[k0] = a;
+    for (int k0 = 0; k0 < NSUB; k0++) {
+      const int w = LANE + RG_WAVE * k0, sb = w / 6, k = w - 6 * sb;
+      acc[k0] = rg_mask_sum<6>(s.cacc + k, sub[k0]);   // (mask 0 past the last body and for the world: sum 0)
     }
     SYNC();
 #pragma unroll
-    for (int k0 = 0; k0 < (RG_MAXBODY * 6 + RG_WAVE - 1) / RG_WAVE; k0++) { int w = LANE + RG_WAVE * k0; if (w < m.nbody * 6) s.cacc[w] = acc[k0]; }
+    for (int k0 = 0; k0 < NSUB; k0++) { int w = LANE + RG_WAVE * k0; if (w < nb * 6) s.cacc[w] = acc[k0]; }
   }
   SYNC();
-  PFOR(d, m.nv) {
-    const rgf4 dr0 = ((const rgf4*)m.dof_rec)[2 * d]; const float spring_ref = m.dof_rec[8 * d + 4];   // body, tendon entries, joint stiffness, qposadr | spring reference
-    const int w0 = __builtin_bit_cast(int, dr0.x);
+  if (d < nv) {
     const float *c = s.cdof + 6 * d, *f = s.cacc + 6 * (w0 & 255);
     s.qfrc_bias[d] = c[0] * f[0] + c[1] * f[1] + c[2] * f[2] + c[3] * f[3] + c[4] * f[4] + c[5] * f[5];
-    float pas = -P[RG_PRM_DOF_DAMPING + d] * s.qvel[d];
+    float pas = -damping * s.qvel[d];
     if (dr0.z != 0) pas -= dr0.z * (s.qpos[__builtin_bit_cast(int, dr0.w)] - spring_ref);
-    for (int q = (w0 >> 8) & 255; q < ((w0 >> 16) & 255); q++) { int tt = m.dof_ten[2 * q], sl = m.dof_ten[2 * q + 1]; pas += s.tenJ[4 * tt + sl] * s.tenfrc[tt]; }
+#pragma unroll
+    for (int i = 0; i < NDT; i++) if (tq0 + i < tq1) pas += s.tenJ[4 * dten[2 * i] + dten[2 * i + 1]] * s.tenfrc[dten[2 * i]];
+    for (int q = tq0 + NDT; q < tq1; q++) { int tt = m.dof_ten[2 * q], sl = m.dof_ten[2 * q + 1]; pas += s.tenJ[4 * tt + sl] * s.tenfrc[tt]; }
     s.qfrc_passive[d] = pas;
   }
   SYNC();
@@ -1550,11 +1640,15 @@ __device__ __forceinline__ void rg_velocity(RgM m, RgLds& s, const float* P, con
 static_assert(RG_MAXU <= RG_WAVE && RG_MAXNV <= RG_WAVE, "controller state / warm start: one lane per actuator / dof");
 __device__ __forceinline__ void rg_pid(RgM m, RgLds& s, const float* P, float* st /* this lane's actuator: integral, previous error, filtered derivative */) {
   float dt = P[RG_PRM_TIMESTEP];
-  PFOR(u, m.nu) {
-    const float* gp = P + RG_PRM_ACT_GAINPRM + 10 * u;
+  PFOR(u, m.nu) {   // (one trip: RG_MAXU <= RG_WAVE)
+    // every word of the actuator requested before the first branch on one of them
+    float gp[6];
+    for (int i = 0; i < 6; i++) gp[i] = P[RG_PRM_ACT_GAINPRM + 10 * u + i];
     float force;
     float lo = P[RG_PRM_ACT_FORCERANGE + 2 * u], hi = P[RG_PRM_ACT_FORCERANGE + 2 * u + 1];
-    if (m.actuator_biastype[u] == 2) {
+    const float clo = P[RG_PRM_ACT_CTRLRANGE + 2 * u], chi = P[RG_PRM_ACT_CTRLRANGE + 2 * u + 1];
+    const int biastype = m.actuator_biastype[u], ctrllimited = m.actuator_ctrllimited[u], forcelimited = m.actuator_forcelimited[u];
+    if (biastype == 2) {
       float err = s.ctrl[u] - s.actlen[u];
       if (fabsf(err) < gp[5]) err = 0;
       float integ = clampf(st[0] + err * dt, -gp[2], gp[2]);
@@ -1564,10 +1658,10 @@ __device__ __forceinline__ void rg_pid(RgM m, RgLds& s, const float* P, float* s
       if (lo != 0 || hi != 0) force = clampf(force, lo, hi);
     } else {
       float c = s.ctrl[u];
-      if (m.actuator_ctrllimited[u]) c = clampf(c, P[RG_PRM_ACT_CTRLRANGE + 2 * u], P[RG_PRM_ACT_CTRLRANGE + 2 * u + 1]);
+      if (ctrllimited) c = clampf(c, clo, chi);
       force = gp[0] * c;
     }
-    if (m.actuator_forcelimited[u]) force = clampf(force, lo, hi);
+    if (forcelimited) force = clampf(force, lo, hi);
     s.actfrc[u] = force;
   }
   SYNC();
@@ -1684,12 +1778,14 @@ __device__ __forceinline__ void rg_make_constraint(RgM m, RgLds& s, const float*
     if (k >= __popc(lo)) { k -= __popc(lo); bits = hi; base = 32; }
     for (int q = 0; q < k; q++) bits &= bits - 1;
     int d = base + __builtin_ctz(bits);
+    // the two bodies' chain words and the dof's compact index requested together (not one after the other behind the branches)
+    const uint32_t ch2 = m.body_dofmask[2 * b2 + (d >> 5)], ch1 = m.body_dofmask[2 * b1 + (d >> 5)]; const int cd = m.d2c[d];
     v3 pos = ld3(s.c_pos + 3 * c);
     v3 jp = mk3(0, 0, 0), jr = mk3(0, 0, 0);
-    if (in_chain(m, b2, d)) { jp = jp + jac_col(s, d, pos - ld3(s.org + 3 * s.b2org[b2])); jr = jr + ld3(s.cdof + 6 * d); }
-    if (in_chain(m, b1, d)) { jp = jp - jac_col(s, d, pos - ld3(s.org + 3 * s.b2org[b1])); jr = jr - ld3(s.cdof + 6 * d); }
+    if ((ch2 >> (d & 31)) & 1u) { jp = jp + jac_col(s, d, pos - ld3(s.org + 3 * s.b2org[b2])); jr = jr + ld3(s.cdof + 6 * d); }
+    if ((ch1 >> (d & 31)) & 1u) { jp = jp - jac_col(s, d, pos - ld3(s.org + 3 * s.b2org[b1])); jr = jr - ld3(s.cdof + 6 * d); }
     float f[9]; st3(f, ld3(s.c_normal + 3 * c)); make_frame(f);   // contact frame: normal, two tangents (mju_makeFrame)
-    s.c_idx[c * RG_W + sl] = (unsigned char)m.d2c[d];
+    s.c_idx[c * RG_W + sl] = (unsigned char)cd;
     float* Bc = s.c_pool + s.c_off[c]; int nb = nbasis(s.c_dim[c]);
     Bc[sl] = dot(ld3(f), jp);
     if (nb >= 3) { Bc[nnz + sl] = dot(ld3(f + 3), jp); Bc[2 * nnz + sl] = dot(ld3(f + 6), jp); }
@@ -1707,15 +1803,18 @@ __device__ __forceinline__ void rg_make_constraint(RgM m, RgLds& s, const float*
     // friction: element-wise max of its geoms' (engine_collision_driver: mj_contactParam)
     const int pg1 = hdr & 255, pg2 = (hdr >> 8) & 255;
     const float mix = m.pair_mix[p];
-    const float* r1 = P + RG_PRM_GEOM_SOLREF + 2 * pg1; const float* r2 = P + RG_PRM_GEOM_SOLREF + 2 * pg2;
-    const float* i1 = P + RG_PRM_GEOM_SOLIMP + 5 * pg1; const float* i2 = P + RG_PRM_GEOM_SOLIMP + 5 * pg2;
+    // (the geoms' rows copied out before the first branch on one of their entries: every read of the env's row in one batch)
+    float r1[2], r2[2], i1[5], i2[5];
+    for (int q = 0; q < 2; q++) { r1[q] = P[RG_PRM_GEOM_SOLREF + 2 * pg1 + q]; r2[q] = P[RG_PRM_GEOM_SOLREF + 2 * pg2 + q]; }
+    for (int q = 0; q < 5; q++) { i1[q] = P[RG_PRM_GEOM_SOLIMP + 5 * pg1 + q]; i2[q] = P[RG_PRM_GEOM_SOLIMP + 5 * pg2 + q]; }
+    const float fr_slide = fmaxf(P[RG_PRM_GEOM_FRICTION + 3 * pg1], P[RG_PRM_GEOM_FRICTION + 3 * pg2]), fr_spin = fmaxf(P[RG_PRM_GEOM_FRICTION + 3 * pg1 + 1], P[RG_PRM_GEOM_FRICTION + 3 * pg2 + 1]);
+    const float timestep = P[RG_PRM_TIMESTEP];
     float solref[2], solimp[5];
     if (r1[0] > 0 && r2[0] > 0) { solref[0] = mix * r1[0] + (1.f - mix) * r2[0]; solref[1] = mix * r1[1] + (1.f - mix) * r2[1]; }
     else { solref[0] = fminf(r1[0], r2[0]); solref[1] = fminf(r1[1], r2[1]); }
     for (int q = 0; q < 5; q++) solimp[q] = mix * i1[q] + (1.f - mix) * i2[q];
     float imp = impedance(solimp, dist, includemargin), K, B;
-    kb(P[RG_PRM_TIMESTEP], solref, solimp, K, B);
-    const float fr_slide = fmaxf(P[RG_PRM_GEOM_FRICTION + 3 * pg1], P[RG_PRM_GEOM_FRICTION + 3 * pg2]), fr_spin = fmaxf(P[RG_PRM_GEOM_FRICTION + 3 * pg1 + 1], P[RG_PRM_GEOM_FRICTION + 3 * pg2 + 1]);
+    kb(timestep, solref, solimp, K, B);
     float mu0 = fr_slide;  // friction[0]
     // first pyramid row: diagApprox = tran + mu0^2 * tran ; all rows get R = 2 mu^2 R_first, mu = friction[0]/sqrt(impratio)
     float R;
