@@ -126,7 +126,7 @@ int rg_batch_copy(rg_batch* b, int field, void* ptr, int to_batch, int ptr_is_de
 int rg_batch_reset(rg_batch* b);
 /* Masked row copy, device to device and asynchronous on `stream`: for every env e with mask_dev[e] != 0 the
  * columns [col0, col0 + ncols) of its `field` row are replaced by row e of src_dev ([B][ncols]; ncols <= 0: the
- * whole row, src_dev laid out as for rg_batch_copy).  Writing RG_F_QPOS voids the collision caches of those
+ * whole row, src_dev laid out as for rg_batch_copy).  Writing RG_F_QPOS or RG_F_QVEL voids the collision caches of those
  * envs only.  This is what a per-env `MjSim.set_state` / `mj_resetData` is for
  * a batch (simulation_interface.py:128-172, cube_env.py:330-355) without stalling the other envs. */
 int rg_batch_copy_rows(rg_batch* b, int field, const void* src_dev, const int* mask_dev, int col0, int ncols, void* stream);
@@ -206,7 +206,13 @@ enum { RG_CFG_ROLLOUT = 0, RG_CFG_LARGE = 1 };
 int rg_batch_step_ex(rg_batch* b, const rg_step_args* args);
 /* Device address of a field's [B][n] buffer inside the batch (library-owned; valid until rg_batch_free) and its
  * row length in 4-byte words: zero-copy views for callers that live on the same device (torch tensors over
- * `sim.data.*`, simulation_interface.py:128-172).  Writers of RG_F_QPOS must zero the env's RG_F_PAIRLB row. */
+ * `sim.data.*`, simulation_interface.py:128-172).  Writers of RG_F_QPOS must zero the env's RG_F_PAIRLB row, and so must writers of
+ * - the `geom_scale` word of the env's RG_F_ENVPRM row: a cached bound is a statement about the geometry it was computed for, and the
+ *   size factor is geometry as the pose is;
+ * - RG_F_QVEL: a substep takes what it subtracts from a carried bound from the stored qvel, as the joint rates that moved the pose
+ *   there since the previous collision pass (semi-implicit Euler); rates written from outside say nothing about that move.
+ * rg_batch_copy and rg_batch_copy_rows do it for RG_F_QPOS and RG_F_QVEL; BatchedSimulationInterface.set_field / set_qvel /
+ * set_geom_scale / touch_qpos do it on the Python side (tests/test_collision_bounds.py). */
 void* rg_batch_field_ptr(rg_batch* b, int field, int* row_words);
 /* number of static collision pairs (row length of RG_F_PAIRLB) */
 int rg_model_npair(const rg_model* m);

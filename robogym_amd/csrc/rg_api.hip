@@ -782,8 +782,9 @@ int rg_batch_copy(rg_batch* b, int field, void* ptr, int to_batch, int ptr_is_de
   HIPCHK(hipDeviceSynchronize());   // slow-path call: ordered after everything queued on any stream (the blocking copies below then complete before it returns)
   if (to_batch) {
     HIPCHK(hipMemcpy(p, ptr, bytes, ptr_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    // positions changed behind the kernel's back: the cached pair distance bounds are void
-    if (field == RG_F_QPOS) HIPCHK(hipMemset(s.pairlb, 0, (size_t)s.B * (d.npair > 0 ? d.npair : 1) * 4));
+    // positions changed behind the kernel's back: the cached pair distance bounds are void.  Velocities too: the next substep takes its decrement
+    // of a bound from the stored qvel, as the rate that carried the pose there from the previous collision pass
+    if (field == RG_F_QPOS || field == RG_F_QVEL) HIPCHK(hipMemset(s.pairlb, 0, (size_t)s.B * (d.npair > 0 ? d.npair : 1) * 4));
   }
   else HIPCHK(hipMemcpy(ptr, p, bytes, ptr_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
   return 0;
@@ -800,7 +801,7 @@ int rg_batch_copy_rows(rg_batch* b, int field, const void* src_dev, const int* m
   const int n = (int)words;
   if (ncols <= 0) { col0 = 0; ncols = n; }
   if (col0 < 0 || col0 + ncols > n) return fail("rg_batch_copy_rows: column range outside the row");
-  float* lb = field == RG_F_QPOS ? s.pairlb : nullptr;
+  float* lb = (field == RG_F_QPOS || field == RG_F_QVEL) ? s.pairlb : nullptr;   // (see rg_batch_copy)
   return launch(rgs::rg_copy_rows_kernel, s.B, RG_WAVE, 0, 0, stream, (float*)p, (const float*)src_dev, mask_dev, n, col0, ncols, lb, d.npair);   // (no LDS)
 }
 

@@ -1597,12 +1597,26 @@ __device__ __forceinline__ void rg_velocity(RgM m, RgLds& s, const float* P, con
         for (int i = 0; i < 2; i++) if (on[i]) for (int e = 0; e < 6; e++) { cv[e] += c[i][e] * q[i]; ca[e] += cd[i][e] * q[i]; }
       }
     }
-    {  // speed bound of the body's geoms: |v(geom centre)| + |omega| * bounding radius (radius of a size-scaled geom: conservative factor for all)
+    {  // Speed bound of the body's geoms (radius of a size-scaled geom: conservative factor for all).  The broadphase carries a pair's bound from
+      // the previous substep's pose to this one, i.e. over one substep of motion at THIS stage's joint rates, of which this pose is the END:
+      // a point p of the geom travelled at most  int |p'| dt <= h |p'(end)| + h^2/2 max |p''|.
+      // (Precondition: the stored qvel IS the rate of that move -- a qvel row written from outside voids the env's bounds, rg_batch_copy(_rows).)
+      //   p'(end)  = v_c + w x rho,               |rho| <= rbound:  |p'|  <= |v_c| + |w| rbound                 (v_c: the geom centre's velocity)
+      //   p''      = a_c + alpha x rho + w x (w x rho):             |p''| <= |a_c| + (|alpha| + |w|^2) rbound
+      //   a_c      = a_lin + alpha x r + w x v_c  at constant joint rates: (alpha, a_lin) = sum cdofdot qvel, the bias acceleration `ca` below
+      //              before gravity (gravity changes the rates, not the path at given rates), r = centre - origin of the spatial vectors.
+      // gspeed = first-order term + h * (second-order term at the end pose); rg_collision takes 1.5 h gspeed off the bound, three times the
+      // h^2/2 needed: the surplus h |p'|/2 + h^2 |p''| is what covers the change of p'' along the substep (h^3/6 max |p'''|).
       v3 w = mk3(cv[0], cv[1], cv[2]), vo = mk3(cv[3], cv[4], cv[5]), og = ld3(s.org + 3 * s.b2org[b]);
-      float wn = norm(w);
+      v3 al = mk3(ca[0], ca[1], ca[2]), alin = mk3(ca[3] + grav0, ca[4] + grav1, ca[5] + grav2);
+      const float wn = norm(w), hs = P[RG_PRM_TIMESTEP], rot2 = hs * (norm(al) + wn * wn);
+      auto speed = [&](int g, float rb) {
+        v3 r = ld3(s.gpos + 3 * g) - og, vc = vo + cross(w, r);
+        return norm(vc) + hs * norm(alin + cross(al, r) + cross(w, vc)) + (wn + rot2) * (rb * gsmax);
+      };
 #pragma unroll
-      for (int k = 0; k < NRB; k++) if (k < gn) s.gspeed[ga + k] = norm(vo + cross(w, ld3(s.gpos + 3 * (ga + k)) - og)) + wn * (rbound[k] * gsmax);
-      for (int k = NRB; k < gn; k++) s.gspeed[ga + k] = norm(vo + cross(w, ld3(s.gpos + 3 * (ga + k)) - og)) + wn * (m.geom_rbound[ga + k] * gsmax);
+      for (int k = 0; k < NRB; k++) if (k < gn) s.gspeed[ga + k] = speed(ga + k, rbound[k]);
+      for (int k = NRB; k < gn; k++) s.gspeed[ga + k] = speed(ga + k, m.geom_rbound[ga + k]);
     }
     float t1[6], t2[6], t3[6];
     mul_inert_vec(t1, s.cinert + 10 * b, ca);

@@ -111,7 +111,7 @@ class BatchedSimulationInterface:
     def view(self, field) -> torch.Tensor:
         """Zero-copy [B, n] tensor over the batch's own buffer of `field` (the batched `sim.data.<field>`):
         reads and in-place writes are ordinary stream-ordered torch ops, no host synchronisation, no copy.
-        Whoever writes qpos through a view must void the collision cache rows (`touch_qpos`)."""
+        Whoever writes qpos or qvel through a view must void the collision cache rows (`touch_qpos`)."""
         t = self._views.get(field)
         if t is None:
             n = ctypes.c_int(0)
@@ -130,11 +130,13 @@ class BatchedSimulationInterface:
         dtype = torch.int32 if field == _native.RG_F_STATUS else torch.float32
         value = torch.as_tensor(value, dtype=dtype, device=self.device).reshape(self.batch_size, self._ncols(field))
         self.view(field).copy_(value)
-        if field == _native.RG_F_QPOS:
+        if field in (_native.RG_F_QPOS, _native.RG_F_QVEL):      # (qvel: the next substep's decrement of a cached bound is taken from it, see touch_qpos)
             self.touch_qpos()
 
     def touch_qpos(self, mask: Optional[torch.Tensor] = None):
-        """qpos was written from outside the stepper: the cached pair distance bounds of those envs are void."""
+        """qpos was written from outside the stepper: the cached pair distance bounds of those envs are void.  The same holds for qvel (a
+        substep subtracts from a carried bound what the stored qvel, as the rates that moved the pose since the last collision pass, allows)
+        and for `params["geom_scale"]`: whoever writes either through a view owes this call."""
         lb = self.view(_native.RG_F_PAIRLB)
         if mask is None:
             lb.zero_()
@@ -195,6 +197,7 @@ class BatchedSimulationInterface:
 
     def set_qvel(self, group: str, value):
         self.view(_native.RG_F_QVEL)[:, self._group_idx(self.qvel_idxs, group)] = torch.as_tensor(value, dtype=torch.float32, device=self.device)
+        self.touch_qpos()
 
     # ------------------------------------------------------------------ sim.data fields in-tree callers read
     @property
@@ -220,6 +223,15 @@ class BatchedSimulationInterface:
         if self._params is None:
             self._params = EnvParams(self)
         return self._params
+
+    def set_geom_scale(self, scale, mask: Optional[torch.Tensor] = None):
+        """`params["geom_scale"]` <- scale (a number or [B]) for the envs of the bool `mask` (None: all).  The size factor changes the
+        geometry the cached pair distance bounds were computed for, exactly as a qpos write does: the rows of those envs are voided.
+        Whoever writes the row through `params["geom_scale"]` itself owes the same `touch_qpos(mask)`."""
+        row = self.params["geom_scale"]
+        new = torch.as_tensor(scale, dtype=torch.float32, device=self.device).expand(self.batch_size)[:, None]
+        row.copy_(new if mask is None else torch.where(mask.to(self.device).bool()[:, None], new, row))
+        self.touch_qpos(mask)
 
     def set_constants(self, mask: Optional[torch.Tensor] = None):
         """`SimulationInterface.set_constants` (simulation_interface.py:199-201 -> MjSim.set_constants -> mj_setConst), which the

@@ -211,6 +211,11 @@ class BatchedDactylCubeWrappers:
         A, N = m.arrays, m.names
         t = lambda a, dt=torch.float64: torch.as_tensor(np.asarray(a), dtype=dt, device=dev)   # the model's own values in double: the products are rounded once, on the write into the fp32 rows
         self._P = P
+        # the simulation's hook for "geometry changed behind the stepper's back" (BatchedSimulationInterface.touch_qpos).  Only an env scripted
+        # without a stepper may lack it (no collision stage, no pair distance cache); a simulation that steps must offer it
+        self._void_cache = getattr(sim, "touch_qpos", None)
+        if self._void_cache is None and hasattr(sim, "env_step"):
+            raise TypeError("randomize=True writes params['geom_scale']: the simulation must offer touch_qpos(mask) to void its cached pair distance bounds")
         self._orig = {k: t(A[src]) for k, src in (("body_inertia", "body_inertia"), ("geom_friction", "geom_friction"), ("gravity", "opt_gravity"),
                                                   ("dof_damping", "dof_damping"), ("tendon_range", "tendon_range"), ("site_pos", "site_pos"))}
         self._orig["kp"] = t(A["actuator_gainprm"][:, 0])
@@ -332,6 +337,8 @@ class BatchedDactylCubeWrappers:
         # RandomizedCubeSizeWrapper (cube.py:12-53): geom_size of the cube geoms times one factor
         scale = D.uniform(0.95, 1.05, (1,))
         self._put("geom_scale", mask, scale)
+        if self._void_cache is not None:
+            self._void_cache(mask)   # a new size factor voids the cached pair distance bounds, as a qpos write does (include/rgstep.h, rg_batch_field_ptr)
         # the observation entries these wrappers add, in the order the wrappers are stacked (innermost first)
         self._pending_delta = [("cube_size", self._cube_size0[None] * scale), ("body_inertia", inertia),
                                ("timestep_lambda", torch.stack([ts_new["pos_lambda"], ts_new["neg_lambda"]], dim=-1)),

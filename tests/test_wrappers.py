@@ -255,8 +255,9 @@ class RandomizedScriptedBatchedEnv(ScriptedBatchedEnv):
         con = g["script_contacts"]
         self._contacts = [con[con[:, 0] == t][:, 1:] for t in range(len(g["script_obs_qpos"]))]
         self.mujoco_simulation = types.SimpleNamespace(cube_body_z=0.2, n_substeps=10, model=model, params=self.params, pos_to_ctrl=g["pos_to_ctrl"],
-                                                       qpos_idxs={"hand_angle": hand_q}, qpos=None, data=types.SimpleNamespace(ncon=None, contact=None))
-        self.step_timestep, self.step_xfrc = [], []
+                                                       qpos_idxs={"hand_angle": hand_q}, qpos=None, data=types.SimpleNamespace(ncon=None, contact=None),
+                                                       touch_qpos=lambda mask=None: self.voided.append(mask))
+        self.step_timestep, self.step_xfrc, self.voided = [], [], []      # (voided: the cache rows the stack asks the simulation to void -- with every geom_scale write)
 
     def _emit(self):
         obs = super()._emit()
@@ -321,6 +322,7 @@ def _randomized_golden_replay(locked_model):
             inner.t = t
             check_obs(env.reset(), "reset before step %d" % t)
             r = resets_at.index(t)
+            assert len(inner.voided) >= r + 1      # a new cube size voids the cached pair distance bounds (include/rgstep.h, rg_batch_field_ptr)
             cube = N["geom"].index("cube:middle")
             for name, got in (("body_inertia", P["body_inertia"][0]), ("geom_friction", P["geom_friction"][0]), ("gravity", P["gravity"][0]), ("dof_damping", P["dof_damping"][0]),
                               ("actuator_kp", P["actuator_gainprm"][0, :, 0]), ("jnt_range", P["jnt_range"][0]), ("actuator_ctrlrange", P["actuator_ctrlrange"][0]),
