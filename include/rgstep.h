@@ -542,6 +542,15 @@ typedef struct ra_post_args {
    * (robogym_amd/utils/rotation.py parallel_quat_table), NULL allowed for a mode that is not selected.  Group matching stays position-only. */
   const float *parallel_quats, *parallel_quats_180;
   int rot_dist_type;
+  /* per-env object counts (appended; NULL = every env uses all num_objects objects, the path above).  num_active [B]: env e uses its first n = num_active[e] objects,
+   * 1 <= n <= num_objects (clamped); num_objects is then the reference's max_num_objects, the world's own count.  Slots n <= i < num_objects of every per-object
+   * observation key are zero (simulation/base.py:222-224, 1015-1024; goals/object_state.py:556-580), their distances are 0 and enter no goal_dist sum, they are never
+   * off the table (common/base.py:751-757), have no finger contacts and are matched with nobody (ra_group_match pairs active objects only).  is_goal_achieved and the
+   * tracker's success need the n active objects within both thresholds; the count the goal-distance reward is measured from includes the padded slots, which read
+   * 0 < threshold (RearrangeEnv._calculate_num_success, common/base.py:824-848 and its NOTE): n_within + (num_objects - n).  The tracker's time-out is
+   * max_timesteps_per_goal_per_obj * n (common/base.py:919-927); max_timesteps_per_goal is not read then.  qpos / qpos_goal keep the world's full nq. */
+  const int* num_active;
+  int max_timesteps_per_goal_per_obj;
 } ra_post_args;
 int ra_env_post_step(rb_batch* main, rb_batch* solver, const ra_post_args* args, void* stream);
 int ra_post_args_size(void);
@@ -614,6 +623,18 @@ typedef struct ra_recipe_args {
    * [object_size / (width, height), 1 - extent - object_size / (width, height)], then the same placement; goal yaws 0.  Draws from the goal's stream, as the other kinds'. */
   float fixed_xy[RA_MAXOBJ][2];
   float fixed_yaw[RA_MAXOBJ];
+  /* per-env object counts (appended; num_active NULL = none, every path above as it is).  num_active [B] is ra_post_args' row; when an env's episode ends the kernel
+   * latches num_active[e] = clamp(num_objects_next[e], 1, num_objects) (RearrangeEnv._reset re-creates the simulation with the current count, common/base.py:850-856,
+   * 904) -- a value written mid-episode waits for that -- and the initial placement, every goal placement (grid, rejection fallback, the train goal, the stack's tower,
+   * the pick-and-place raise) and sample_group_counts run over the first n objects; draws keep their streams and indices (n = num_objects draws what the path above
+   * draws).  Goal kinds 0, 1, 2 and 5.  The placement area follows the env's count: used_table_portion clipped to [0.1 n, 1] (simulation/base.py:980-1010), width =
+   * 0.5 * table width * portion, height = 0.38 * table depth * portion, centred at (0.5, 0.44) of the table -- area_offset / area_size are not read then.
+   * Objects n <= i < num_objects are parked: qpos and qpos_goal hold park_pose[i] (position, quaternion w x y z), the goal rows, yaw and static observation of those
+   * slots are zero, group ids -1.  The caller keeps them there (no gravity, damping: per-env parameter rows). */
+  int* num_active;
+  const int* num_objects_next;
+  float used_table_portion;
+  float park_pose[RA_MAXOBJ][7];
 } ra_recipe_args;
 int ra_env_recipe_step(rb_batch* main, rb_batch* solver, const ra_recipe_args* args, void* stream);
 int ra_recipe_args_size(void);

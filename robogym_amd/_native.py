@@ -95,7 +95,8 @@ def _ra_post_fields():
             + [("solver_qpos", _p), ("solver_ctrl", _p), ("solver_nq", _i), ("solver_nu", _i), ("solver_grip_qposadr", _i), ("solver_grip_act", _i), ("frozen", _p), ("reward_clip", _f)]
             + [("goal_kind", _i), ("grip_site", _i), ("goal_dist_extra", _p)]
             + [("obj_group", _p)]
-            + [("parallel_quats", _p), ("parallel_quats_180", _p), ("rot_dist_type", _i)])
+            + [("parallel_quats", _p), ("parallel_quats_180", _p), ("rot_dist_type", _i)]
+            + [("num_active", _p), ("max_timesteps_per_goal_per_obj", _i)])
 
 
 class RaPostArgs(ctypes.Structure):
@@ -117,7 +118,8 @@ def _ra_recipe_fields():
             + [("obj_group", _p), ("group_mode", _i), ("sample_lam", _f * 2)]
             + [("goal_distance_ratio", _p), ("goal_distance_min", _f), ("pickup_proba", _f), ("stacking_proba", _f)]
             + [("randomize_goal_rot", _i), ("domino_distance_mul", _f)]
-            + [("fixed_xy", (_f * 2) * RA_MAXOBJ), ("fixed_yaw", _f * RA_MAXOBJ)])
+            + [("fixed_xy", (_f * 2) * RA_MAXOBJ), ("fixed_yaw", _f * RA_MAXOBJ)]
+            + [("num_active", _p), ("num_objects_next", _p), ("used_table_portion", _f), ("park_pose", (_f * 7) * RA_MAXOBJ)])
 
 
 class RaRecipeArgs(ctypes.Structure):

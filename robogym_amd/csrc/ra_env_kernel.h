@@ -11,6 +11,7 @@
 //   ObjectStateGoal.relative_goal / goal_distance                 envs/rearrange/goals/object_state.py:492-599 (rot_dist_type full / mod90 / mod180; duplicated-object groups: ra_group_match)
 //   _get_goal_info, MultiGoalTracker.process                      robot_env.py:577-625, utils/multi_goal_tracker.py:157-241
 //   JointControlledTcpArm.on_observations_updated                 robot/ur16e/mujoco/joint_controlled_tcp_arm.py:114-129 (gripper state -> solver world)
+//   per-env object counts (num_active: zero padding to max_num_objects) envs/rearrange/simulation/base.py:73-74, 222-224, 1015-1024; common/base.py:751-757, 919-927
 // Rotation helpers follow robogym/utils/rotation.py (mat2euler, quat2mat, normalize_angles) as rb_env_kernel.h's rbc_* do.
 #pragma once
 #include "rb_env_kernel.h"
@@ -26,14 +27,16 @@ namespace rgb {
 // does, its objects being listed in increasing id); rounds of different groups commute.  Every group of size n receives exactly n of the N picks.
 // Squared distances are compared (the square root is monotone).  Pair p = i * N + j lives on lane p % 64, slot p / 64 (N <= 16: at most 4 per lane); the wiped
 // rows / columns are two 16-bit masks, the same on every lane.  A distance that is not finite is never picked: such an object keeps its own goal.
-__device__ inline int ra_group_match(const int* grp, const float* xpos, const int* obj_body, const float* goal, int N, int lane) {
+// `n` <= N: the env's active objects (ra_post_args.num_active) -- a pair with an inactive member is at +inf like a pair across groups, so no active object is ever
+// measured against an inactive slot's goal; n = N is the matching above.
+__device__ inline int ra_group_match(const int* grp, const float* xpos, const int* obj_body, const float* goal, int N, int n, int lane) {
   float d[4];
   for (int s = 0; s < 4; s++) {
     const int p = lane + 64 * s;
     d[s] = INFINITY;
     if (p < N * N) {
       const int i = p / N, j = p - i * N;
-      if (grp[i] == grp[j]) {
+      if (grp[i] == grp[j] && i < n && j < n) {
         const float* x = xpos + 3 * obj_body[i]; const float* g = goal + 7 * j;
         const float dx = x[0] - g[0], dy = x[1] - g[1], dz = x[2] - g[2];
         d[s] = dx * dx + dy * dy + dz * dz;
@@ -69,6 +72,9 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
   if (e >= bt.B) return;
   if (a.frozen && a.frozen[e] == 2) return;      // not this env's turn (re-observation of selected envs only)
   const int nq = m.nq, N = a.num_objects;
+  // per-env object count: the env's first n objects are in use, slots n .. N - 1 are padding (zeros in every per-object key, no part in any sum, flag or match)
+  int n = N;
+  if (a.num_active) { n = a.num_active[e]; n = n < 1 ? 1 : (n > N ? N : n); }
   const float* qrow = bt.qpos + (size_t)e * nq;
   const float* vrow = bt.qvel + (size_t)e * m.nv;
   const float* crow = bt.ctrl + (size_t)e * m.nu;
@@ -93,8 +99,8 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
   const int reach = a.goal_kind >= 3;
   const float* grip = S + m.off[RB_O_SPOS] + 3 * a.grip_site;      // (kinds 2-4 only)
   int mgoal = lane;                              // the goal this lane's object is measured against: its own, or its match inside its group of duplicates
-  if (a.obj_group) mgoal = ra_group_match(a.obj_group + (size_t)e * N, xpos, a.obj_body, a.goal + (size_t)e * N * 7, N, lane);
-  if (lane < N) {
+  if (a.obj_group) mgoal = ra_group_match(a.obj_group + (size_t)e * N, xpos, a.obj_body, a.goal + (size_t)e * N * 7, N, n, lane);
+  if (lane < n) {
     const int b = a.obj_body[lane];
     float M[9], eul[3], vp[3], vr[3];
     rbc_quat2mat(xquat + 4 * b, M);
@@ -164,6 +170,16 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
     const float* so = a.static_obs + ((size_t)e * N + lane) * 7;
     for (int k = 0; k < 3; k++) o[g0 + 14 * N + 1 + 3 * lane + k] = so[k];
     for (int k = 0; k < 4; k++) o[g0 + 17 * N + 1 + 4 * lane + k] = so[3 + k];
+  } else if (lane < N) {      // a padded slot: zeros (simulation/base.py:222-224, 1015-1024; goals/object_state.py:556-580)
+    float* o = row;
+    const int g0 = 15 * N + 15 + 2 * nq;
+    for (int k = 0; k < 3; k++) {
+      o[3 * lane + k] = 0.f; o[3 * N + 3 * lane + k] = 0.f; o[6 * N + 3 * lane + k] = 0.f; o[9 * N + 3 * lane + k] = 0.f; o[12 * N + 3 * lane + k] = 0.f;
+      o[g0 + 3 * lane + k] = 0.f; o[g0 + 3 * N + 3 * lane + k] = 0.f; o[g0 + 6 * N + 1 + 3 * lane + k] = 0.f; o[g0 + 9 * N + 1 + 3 * lane + k] = 0.f;
+      o[g0 + 14 * N + 1 + 3 * lane + k] = 0.f;
+    }
+    o[g0 + 12 * N + 1 + 2 * lane] = 0.f; o[g0 + 12 * N + 1 + 2 * lane + 1] = 0.f;
+    for (int k = 0; k < 4; k++) o[g0 + 17 * N + 1 + 4 * lane + k] = 0.f;
   }
   const unsigned long long okmask = __ballot(ok_obj), offmask = __ballot(off_obj);
   const int nsucc = __popcll(okmask), any_off = offmask != 0;
@@ -173,7 +189,8 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
   if (a.goal_kind == 2) for (int o = 32; o > 0; o >>= 1) { dgrip += __shfl_xor(dgrip, o); grasp += __shfl_xor(grasp, o); }
   // what the goal-distance reward is measured from: the count of objects within both thresholds (RearrangeEnv._calculate_num_success), for reach the summed obj_pos
   // distance (BlocksReachEnv._calculate_goal_distance_reward: its decrease)
-  const float gscore = reach ? sp : (float)nsucc * a.goal_reward_per_object;
+  // (a padded slot reads distance 0 < threshold in _calculate_num_success, common/base.py:824-848 and its NOTE: N - n more, which cancel in the reward's difference)
+  const float gscore = reach ? sp : (float)(nsucc + (N - n)) * a.goal_reward_per_object;
   // ---- robot read-outs and the copied blocks
   {
     float* o = row + 15 * N;
@@ -205,7 +222,7 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
   const int frozen = a.frozen ? a.frozen[e] : 0;
   if (lane == 0 && frozen == 3) {                  // 3: observation entries only (a live env whose goal was just replaced): reward / done / flags / counters untouched
     const int g0 = 15 * N + 15 + 2 * nq;
-    row[g0 + 6 * N] = (float)(!crash && nsucc == N);
+    row[g0 + 6 * N] = (float)(!crash && nsucc == n);
     // reset_goal -> _observe_sync -> update_goal_info (robot_env.py:893-909, 586-593): the re-observation under the new goal is what the next step's
     // goal-distance reward is measured from
     a.prev_nsucc[e] = gscore; a.prev_valid[e] = 1;
@@ -246,8 +263,10 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
     a.t[e] += 1;
     const float gdr = (a.prev_valid[e] && !crash) ? (reach ? a.prev_nsucc[e] - gscore : gscore - a.prev_nsucc[e]) : 0.f;
     a.prev_nsucc[e] = gscore; a.prev_valid[e] = 1;
-    const int succ = !crash && nsucc == N;
-    EnvTracked tk = env_tracker_process(e, a.steps, a.steps_since_last_goal, a.successes_so_far, a.consecutive, a.max_timesteps_per_goal, a.successes_needed, succ);
+    const int succ = !crash && nsucc == n;
+    // (max_timesteps_per_goal follows the env's own count, common/base.py:919-927)
+    const int max_t = a.num_active ? a.max_timesteps_per_goal_per_obj * n : a.max_timesteps_per_goal;
+    EnvTracked tk = env_tracker_process(e, a.steps, a.steps_since_last_goal, a.successes_so_far, a.consecutive, max_t, a.successes_needed, succ);
     // reset_goal's reset_goal_steps and _previous_goal_distance = None (robot_env.py:893-909) inline: the goal itself comes from ra_recipe_kernel or the host
     if (tk.newgoal) { tk.ssl = 0; a.steps_since_last_goal[e] = 0; a.prev_valid[e] = 0; }
     float* rw = a.reward + 3 * (size_t)e;
@@ -283,12 +302,31 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
 //   DominoStateGoal                                                envs/rearrange/goals/dominos.py:20-150
 //   place_targets_with_fixed_position                              envs/rearrange/common/utils.py:884-919 (ObjectFixedStateGoal, goals/object_state_fixed.py)
 //   AttachedBlockStateGoal                                         envs/rearrange/goals/attached_block_state.py:17-68
-struct RaRecipeLds { int started, ended, regoal, moved; float pos[RA_MAXOBJ][3], gpos[RA_MAXOBJ][3], gyaw[RA_MAXOBJ], opos[3]; };
+struct RaRecipeLds { int started, ended, regoal, moved; float pos[RA_MAXOBJ][3], gpos[RA_MAXOBJ][3], gyaw[RA_MAXOBJ], opos[3]; int n; };
+
+// get_placement_area (simulation/base.py:980-1010) of one env: offset from the table's low corner and size.  Without per-env object counts the launch constants.
+// With them the area follows the env's own count n: used_table_portion clipped to [0.1 n, 1], width = 0.5 x table width x portion, height = 0.38 x table depth x
+// portion, centred at (0.5, 0.44) of the table.  An env whose clipped portion is the one the launch constants were made with (n = num_objects among them) reads
+// those, bit for bit.
+struct RaArea { float off[2], size[2]; };
+__device__ inline RaArea ra_area(const RaRecipeArgs& a, int n) {
+  RaArea A;
+  A.off[0] = a.area_offset[0]; A.off[1] = a.area_offset[1]; A.size[0] = a.area_size[0]; A.size[1] = a.area_size[1];
+  if (a.num_active) {
+    const float p_all = fminf(fmaxf(a.used_table_portion, 0.1f * (float)a.num_objects), 1.f), p = fminf(fmaxf(a.used_table_portion, 0.1f * (float)n), 1.f);
+    if (p != p_all) {
+      const float tsx = 2.f * a.table_size[0], tsy = 2.f * a.table_size[1];
+      A.size[0] = 0.5f * tsx * p; A.size[1] = 0.38f * tsy * p;
+      A.off[0] = 0.5f * tsx - 0.5f * A.size[0]; A.off[1] = 0.44f * tsy - 0.5f * A.size[1];
+    }
+  }
+  return A;
+}
 
 // One placement of the first N objects (rotated about z by yaw[i]) inside the placement area: body origins in world coordinates.  Returns false when the rejection
 // sampling ran out of restarts (out = its last proposal).  `k`: this env's running draw index.  `no_grid`: place_objects_with_no_constraint even where the grid
-// has cells enough (the stack and reach goals' own placement).
-__device__ inline bool ra_place(const RaRecipeArgs& a, int N, bool no_grid, const float* yaw, int ystride, unsigned seed, unsigned step, unsigned e, unsigned& k, float (*out)[3]) {
+// has cells enough (the stack and reach goals' own placement).  `ar`: the env's placement area (ra_area).
+__device__ inline bool ra_place(const RaRecipeArgs& a, const RaArea& ar, int N, bool no_grid, const float* yaw, int ystride, unsigned seed, unsigned step, unsigned e, unsigned& k, float (*out)[3]) {
   auto U = [&]() -> float { return env_u01(seed, step, e, k++); };
   float hx[RA_MAXOBJ], hy[RA_MAXOBJ], xy[RA_MAXOBJ][2];
   float mx = 0.f, my = 0.f;
@@ -297,7 +335,7 @@ __device__ inline bool ra_place(const RaRecipeArgs& a, int N, bool no_grid, cons
     hx[i] = c * a.obj_half[i][0] + s_ * a.obj_half[i][1]; hy[i] = s_ * a.obj_half[i][0] + c * a.obj_half[i][1];
     mx = fmaxf(mx, hx[i]); my = fmaxf(my, hy[i]);
   }
-  const float width = a.area_size[0], height = a.area_size[1];
+  const float width = ar.size[0], height = ar.size[1];
   const int ncol = (int)floorf(width / (2.f * mx)), nrow = (int)floorf(height / (2.f * my));
   const int M = ncol * nrow;
   bool ok = true;
@@ -344,8 +382,8 @@ __device__ inline bool ra_place(const RaRecipeArgs& a, int N, bool no_grid, cons
   for (int i = 0; i < N; i++) {      // the body origin, from the centre of its bounding box
     const float c = cosf(yaw[i * ystride]), s_ = sinf(yaw[i * ystride]);
     const float ccx = c * a.obj_center[i][0] - s_ * a.obj_center[i][1], ccy = s_ * a.obj_center[i][0] + c * a.obj_center[i][1];
-    out[i][0] = xy[i][0] + a.area_offset[0] - a.table_size[0] + a.table_pos[0] - ccx;
-    out[i][1] = xy[i][1] + a.area_offset[1] - a.table_size[1] + a.table_pos[1] - ccy;
+    out[i][0] = xy[i][0] + ar.off[0] - a.table_size[0] + a.table_pos[0] - ccx;
+    out[i][1] = xy[i][1] + ar.off[1] - a.table_size[1] + a.table_pos[1] - ccy;
     out[i][2] = a.obj_half[i][2] + 2.f * a.table_size[2] - a.table_size[2] + a.table_pos[2] - a.obj_center[i][2];
   }
   return ok;
@@ -355,11 +393,11 @@ __device__ inline bool ra_place(const RaRecipeArgs& a, int N, bool no_grid, cons
 // its bounding box inside the placement area, pulled toward the object's own position (`qrow`: the env's qpos row) by clip(ratio, dmin / dist if dist >= dmin else 0, 1),
 // rejected while its box overlaps a goal already placed; an object that runs out of its 1 + 20 proposals restarts the set, up to 100 sets.  Returns false when those ran
 // out (out = the last proposals).
-__device__ inline bool ra_place_near(const RaRecipeArgs& a, int N, const float* yaw, int ystride, const float* qrow, float ratio_in, unsigned seed, unsigned step, unsigned e, unsigned& k,
+__device__ inline bool ra_place_near(const RaRecipeArgs& a, const RaArea& ar, int N, const float* yaw, int ystride, const float* qrow, float ratio_in, unsigned seed, unsigned step, unsigned e, unsigned& k,
                                      float (*out)[3]) {
   auto U = [&]() -> float { return env_u01(seed, step, e, k++); };
   float hx[RA_MAXOBJ], hy[RA_MAXOBJ], cx[RA_MAXOBJ], cy[RA_MAXOBJ], px[RA_MAXOBJ], py[RA_MAXOBJ];
-  const float width = a.area_size[0], height = a.area_size[1];
+  const float width = ar.size[0], height = ar.size[1];
   for (int i = 0; i < N; i++) {
     const float c = cosf(yaw[i * ystride]), s_ = sinf(yaw[i * ystride]);
     hx[i] = fabsf(c) * a.obj_half[i][0] + fabsf(s_) * a.obj_half[i][1]; hy[i] = fabsf(s_) * a.obj_half[i][0] + fabsf(c) * a.obj_half[i][1];
@@ -371,8 +409,8 @@ __device__ inline bool ra_place_near(const RaRecipeArgs& a, int N, const float* 
     ok = true;
     for (int i = 0; i < N && ok; i++) {
       // the object's box centre relative to the placement area
-      const float x = qrow[a.obj_qposadr[i]] - a.area_offset[0] + a.table_size[0] - a.table_pos[0] + cx[i];
-      const float y = qrow[a.obj_qposadr[i] + 1] - a.area_offset[1] + a.table_size[1] - a.table_pos[1] + cy[i];
+      const float x = qrow[a.obj_qposadr[i]] - ar.off[0] + a.table_size[0] - a.table_pos[0] + cx[i];
+      const float y = qrow[a.obj_qposadr[i] + 1] - ar.off[1] + a.table_size[1] - a.table_pos[1] + cy[i];
       bool placed = false;
       for (int trial = 0; trial <= 20 && !placed; trial++) {
         float gx = hx[i] + U() * (width - 2.f * hx[i]), gy = hy[i] + U() * (height - 2.f * hy[i]);
@@ -389,8 +427,8 @@ __device__ inline bool ra_place_near(const RaRecipeArgs& a, int N, const float* 
     }
   }
   for (int i = 0; i < N; i++) {
-    out[i][0] = px[i] - cx[i] + a.area_offset[0] - a.table_size[0] + a.table_pos[0];
-    out[i][1] = py[i] - cy[i] + a.area_offset[1] - a.table_size[1] + a.table_pos[1];
+    out[i][0] = px[i] - cx[i] + ar.off[0] - a.table_size[0] + a.table_pos[0];
+    out[i][1] = py[i] - cy[i] + ar.off[1] - a.table_size[1] + a.table_pos[1];
     out[i][2] = a.obj_half[i][2] + 2.f * a.table_size[2] - a.table_size[2] + a.table_pos[2] - a.obj_center[i][2];
   }
   return ok;
@@ -474,6 +512,9 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
     int started = 0, ended = 0, regoal = 0, stabilised = 0;
     unsigned k = 0;
     auto U = [&]() -> float { return env_u01(a.seed, a.step, (unsigned)e, k++); };
+    // per-env object counts: the env's first n objects are in use (latched below when an episode ends); without them n = N and every line is the one it was
+    int n = N;
+    if (a.num_active) { n = a.num_active[e]; n = n < 1 ? 1 : (n > N ? N : n); }
     a.episode_started[e] = 0;
     // ---- an env inside the recipe: this step counted
     if (st > 0) {
@@ -514,41 +555,43 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
       // the goal's yaws: the ones it has, or -- randomize_quaternion_along_z, drawn before the positions -- those turned by U(0, 2 pi) each; the placements below work
       // with the boxes rotated by THESE
       for (int i = 0; i < N; i++) F.gyaw[i] = gy[i * gstride];
-      if (a.randomize_goal_rot) for (int i = 0; i < N; i++) F.gyaw[i] += 2.f * RBC_PI * env_u01(a.seed ^ 0xC2B2AE35u, a.step, (unsigned)e, (unsigned)i);
+      if (a.randomize_goal_rot) for (int i = 0; i < n; i++) F.gyaw[i] += 2.f * RBC_PI * env_u01(a.seed ^ 0xC2B2AE35u, a.step, (unsigned)e, (unsigned)i);
       // (the fixed placements call set_target_quat inside _sample_next_goal_positions, after the randomisation: their goals have init_quats' yaws, always)
       if (kind == 7) for (int i = 0; i < N; i++) F.gyaw[i] = 0.f;
       if (kind == 8) for (int i = 0; i < N; i++) F.gyaw[i] = a.fixed_yaw[i];
       gy = F.gyaw; gstride = 1;
+      const RaArea ar = ra_area(a, n);
+      // (kinds 0, 1, 2 and 5 place the env's n active objects; the others are built without per-env counts: n = N)
       if (kind <= 1) {
-        if (!ra_place(a, N, false, gy, gstride, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
+        if (!ra_place(a, ar, n, false, gy, gstride, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
         if (kind == 1) {                                               // move_one_object_to_the_air: height first, then the object
           const float h = a.height_range[0] + UG() * (a.height_range[1] - a.height_range[0]);
-          int i = (int)(UG() * (float)N); i = i > N - 1 ? N - 1 : i;
+          int i = (int)(UG() * (float)n); i = i > n - 1 ? n - 1 : i;
           F.gpos[i][2] += h;
         }
       } else if (kind == 2) {                                          // ObjectStackGoal: object 0's box placed, the others on top of it in block order
         float bot[1][3];
-        if (!ra_place(a, 1, true, gy, gstride, gseed, a.step, (unsigned)e, k, bot)) a.placement_failed[e] += 1;
+        if (!ra_place(a, ar, 1, true, gy, gstride, gseed, a.step, (unsigned)e, k, bot)) a.placement_failed[e] += 1;
         int order[RA_MAXOBJ];
-        for (int i = 0; i < N; i++) order[i] = i;
+        for (int i = 0; i < n; i++) order[i] = i;
         if (!a.fixed_order)
-          for (int i = N - 1; i > 0; i--) { int j = (int)(UG() * (float)(i + 1)); j = j > i ? i : j; const int tmp = order[i]; order[i] = order[j]; order[j] = tmp; }
-        for (int i = 0; i < N; i++) { F.gpos[order[i]][0] = bot[0][0]; F.gpos[order[i]][1] = bot[0][1]; F.gpos[order[i]][2] = bot[0][2] + (float)i * 2.f * a.object_size; }
+          for (int i = n - 1; i > 0; i--) { int j = (int)(UG() * (float)(i + 1)); j = j > i ? i : j; const int tmp = order[i]; order[i] = order[j]; order[j] = tmp; }
+        for (int i = 0; i < n; i++) { F.gpos[order[i]][0] = bot[0][0]; F.gpos[order[i]][1] = bot[0][1]; F.gpos[order[i]][2] = bot[0][2] + (float)i * 2.f * a.object_size; }
       } else if (kind == 5) {                                          // TrainStateGoal (goals/train_state.py:81-113): goals near the objects, then one in the air or a tower
         const float ratio = a.goal_distance_ratio ? a.goal_distance_ratio[e] : 1.f;
-        if (!ra_place_near(a, N, gy, gstride, bt.qpos + (size_t)e * nq, ratio, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
+        if (!ra_place_near(a, ar, n, gy, gstride, bt.qpos + (size_t)e * nq, ratio, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
         if (a.pickup_proba + a.stacking_proba > 0.f) {                 // move_one_object_to_the_air_with_restrictions (:13-78)
           const float p = UG();
           if (p > a.pickup_proba + a.stacking_proba) {
           } else if (p < a.pickup_proba) {
             const float h = a.height_range[0] + UG() * (a.height_range[1] - a.height_range[0]);
-            int i = (int)(UG() * (float)N); i = i > N - 1 ? N - 1 : i;
+            int i = (int)(UG() * (float)n); i = i > n - 1 ? n - 1 : i;
             F.gpos[i][2] += h * ratio;
-          } else if (N >= 2) {                                         // a tower of 2..N objects: a random subset in random order, from this env's stream
-            int tower = 2 + (int)(UG() * (float)(N - 1)); tower = tower > N ? N : tower;
+          } else if (n >= 2) {                                         // a tower of 2..n objects: a random subset in random order, from this env's stream
+            int tower = 2 + (int)(UG() * (float)(n - 1)); tower = tower > n ? n : tower;
             int order[RA_MAXOBJ];
-            for (int i = 0; i < N; i++) order[i] = i;
-            for (int t = 0; t < tower; t++) { int j = t + (int)(UG() * (float)(N - t)); j = j > N - 1 ? N - 1 : j; const int tmp = order[t]; order[t] = order[j]; order[j] = tmp; }
+            for (int i = 0; i < n; i++) order[i] = i;
+            for (int t = 0; t < tower; t++) { int j = t + (int)(UG() * (float)(n - t)); j = j > n - 1 ? n - 1 : j; const int tmp = order[t]; order[t] = order[j]; order[j] = tmp; }
             for (int h = 1; h < tower; h++) {
               F.gpos[order[h]][0] = F.gpos[order[0]][0]; F.gpos[order[h]][1] = F.gpos[order[0]][1]; F.gpos[order[h]][2] += a.object_size * (float)h * 2.f;
             }
@@ -564,7 +607,7 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
         ra_place_fixed(a, N, a.fixed_xy, F.gpos);
       } else {                                                         // reach: the object goes to the placement, the goal target_height above it
         if (kind == 3) {
-          if (!ra_place(a, 1, true, gy, gstride, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
+          if (!ra_place(a, ar, 1, true, gy, gstride, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
         } else {
           const int gi = (a.goal_index[e] + 1) & 1;
           a.goal_index[e] = gi;
@@ -578,6 +621,8 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
     // ---- an episode that ended on this step: its recipe begins (the returned observation / reward / done are the terminal ones)
     if (!started && st == 0 && a.done[e]) {
       ended = 1;
+      // the count of the episode that begins: RearrangeEnv._reset re-creates the simulation with the current num_objects (common/base.py:850-856, 904)
+      if (a.num_active) { n = a.num_objects_next[e]; n = n < 1 ? 1 : (n > N ? N : n); a.num_active[e] = n; }
       if (a.obj_group && a.group_mode == 1) {                          // _randomize_object_groups, the first act of RearrangeEnv._reset: sample_group_counts
         // (common/utils.py:47-73) -- until the objects are used up: lam ~ U(sample_lam), a count c in 1..remaining with probability proportional to exp(-c lam)
         // (the inverse of its cumulative sum at a second uniform); group g = the next c objects.  A stream of its own (seed ^ constant, as the goal's): disjoint from
@@ -586,8 +631,9 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
         const unsigned grseed = a.seed ^ 0x85EBCA6Bu;
         auto UR = [&]() -> float { return env_u01(grseed, a.step, (unsigned)e, k++); };
         int* grow = a.obj_group + (size_t)e * N;
-        for (int first = 0, g = 0; first < N; g++) {
-          const int rem = N - first;
+        for (int i = n; i < N; i++) grow[i] = -1;                       // (a padded slot belongs to no group)
+        for (int first = 0, g = 0; first < n; g++) {
+          const int rem = n - first;
           const float lam = a.sample_lam[0] + UR() * (a.sample_lam[1] - a.sample_lam[0]);
           const float q = expf(-lam);
           float total = 0.f, w = 1.f;                                  // weights exp(-(c - 1) lam): the common factor exp(-lam) cancels
@@ -601,8 +647,9 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
       }
       k = 1000u;
       float* yw = a.yaw + (size_t)e * N;
-      for (int i = 0; i < N; i++) yw[i] = 2.f * RBC_PI * U();
-      if (!ra_place(a, N, false, yw, 1, a.seed, a.step, (unsigned)e, k, F.pos)) a.placement_failed[e] += 1;
+      for (int i = 0; i < n; i++) yw[i] = 2.f * RBC_PI * U();
+      for (int i = n; i < N; i++) yw[i] = 0.f;
+      if (!ra_place(a, ra_area(a, n), n, false, yw, 1, a.seed, a.step, (unsigned)e, k, F.pos)) a.placement_failed[e] += 1;
       st = 1; lf = a.stabilize_steps > 0 ? a.stabilize_steps : 1;
       a.hold[e] = 1; a.hold_ctrl[e] = 1; a.frozen[e] = 4; a.solver_active[e] = 0; a.resetting[e] = 1;
       for (int d = 0; d < AD; d++) a.scripted[(size_t)e * AD + d] = 0.f;
@@ -614,26 +661,36 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
     a.stage[e] = st; a.left[e] = lf;
     a.reobserve[e] = started ? 1 : (regoal ? 3 : 2);
     a.ended[e] = (unsigned char)ended; a.stabilised[e] = (unsigned char)stabilised;
-    F.started = started; F.ended = ended; F.regoal = regoal;
+    F.started = started; F.ended = ended; F.regoal = regoal; F.n = n;
   }
   __syncthreads();
   // ---- goal rows (goals/object_state.py:381-418): position, orientation (a z rotation, as Euler angles and as a quaternion), qpos_goal = the current qpos with
   // the objects at their goals; the previous success count is void
   if (F.started || F.regoal) {
     if (F.moved && lane < 3) bt.qpos[(size_t)e * nq + a.obj_qposadr[0] + lane] = F.opos[lane];      // set_object_pos: the position only
-    if (lane < N) {
+    const int n = F.n;
+    if (lane < n) {
       const float ez = rbc_wrap(F.gyaw[lane]);        // mat2euler of a z rotation, normalised
       float* g = a.goal + ((size_t)e * N + lane) * 7;
       g[0] = F.gpos[lane][0]; g[1] = F.gpos[lane][1]; g[2] = F.gpos[lane][2];
       g[3] = cosf(0.5f * ez); g[4] = 0.f; g[5] = 0.f; g[6] = sinf(0.5f * ez);
       float* gr = a.goal_rot + ((size_t)e * N + lane) * 3;
       gr[0] = 0.f; gr[1] = 0.f; gr[2] = ez;
+    } else if (lane < N) {                            // a padded slot: a zero goal (identity orientation)
+      float* g = a.goal + ((size_t)e * N + lane) * 7;
+      for (int c = 0; c < 7; c++) g[c] = c == 3 ? 1.f : 0.f;
+      float* gr = a.goal_rot + ((size_t)e * N + lane) * 3;
+      gr[0] = 0.f; gr[1] = 0.f; gr[2] = 0.f;
     }
     for (int i = lane; i < nq; i += 64) {
       float v = bt.qpos[(size_t)e * nq + i];
-      for (int o = 0; o < N; o++) {
+      for (int o = 0; o < n; o++) {
         const int d = i - a.obj_qposadr[o];
         if (d >= 0 && d < 7) { const float ez = rbc_wrap(F.gyaw[o]); v = d < 3 ? F.gpos[o][d] : (d == 3 ? cosf(0.5f * ez) : (d == 6 ? sinf(0.5f * ez) : 0.f)); }
+      }
+      for (int o = n; o < N; o++) {                   // (a parked object keeps its parked pose in qpos_goal)
+        const int d = i - a.obj_qposadr[o];
+        if (d >= 0 && d < 7) v = a.park_pose[o][d];
       }
       a.qpos_goal[(size_t)e * nq + i] = v;
     }
@@ -643,12 +700,17 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
   // ---- what RearrangeEnv._reset writes before anything is simulated: both worlds as freshly made, the arm's start pose, the objects placed
   if (F.ended) {
     const float* yw = a.yaw + (size_t)e * N;
+    const int n = F.n;
     for (int i = lane; i < nq; i += 64) {
       float v = m.qpos0[i];
       for (int j = 0; j < 6; j++) if (i == a.arm_qposadr[j]) v = a.arm_start[j];
-      for (int o = 0; o < N; o++) {
+      for (int o = 0; o < n; o++) {
         const int d = i - a.obj_qposadr[o];
         if (d >= 0 && d < 7) v = d < 3 ? F.pos[o][d] : (d == 3 ? cosf(0.5f * yw[o]) : (d == 6 ? sinf(0.5f * yw[o]) : 0.f));
+      }
+      for (int o = n; o < N; o++) {                   // objects beyond the env's count are parked (ra_recipe_args.park_pose), at rest: qvel is zeroed below
+        const int d = i - a.obj_qposadr[o];
+        if (d >= 0 && d < 7) v = a.park_pose[o][d];
       }
       bt.qpos[(size_t)e * nq + i] = v;
     }
@@ -669,7 +731,8 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
       if (lane == 0) { sb.time[e] = 0.f; sb.status[e] = 0; }
       if (ms.neq > 0 && lane < 7) sb.eq_data[(size_t)e * 7 * ms.neq + lane] = lane == 3 ? 1.f : 0.f;      // reset_mocap_welds
     }
-    if (lane < N) {      // the static observation: bounding box of the yawed object, a random colour
+    if (lane >= n && lane < N) { float* so = a.static_obs + ((size_t)e * N + lane) * 7; for (int q = 0; q < 7; q++) so[q] = 0.f; }
+    if (lane < n) {      // the static observation: bounding box of the yawed object, a random colour
       const float c = fabsf(cosf(yw[lane])), s_ = fabsf(sinf(yw[lane]));
       float* so = a.static_obs + ((size_t)e * N + lane) * 7;
       so[0] = c * a.obj_half[lane][0] + s_ * a.obj_half[lane][1]; so[1] = s_ * a.obj_half[lane][0] + c * a.obj_half[lane][1]; so[2] = a.obj_half[lane][2];

@@ -1551,6 +1551,8 @@ int ra_env_post_step(rb_batch* b, rb_batch* solver, const ra_post_args* args, vo
   if (a.obj_group && a.goal_kind >= 3) return fail("ra_env_post_step: obj_group with a reach goal (one object: nothing to match)");
   if (a.rot_dist_type < 0 || a.rot_dist_type > 2) return fail("ra_env_post_step: rot_dist_type out of range (0 full, 1 mod90, 2 mod180)");
   if ((a.rot_dist_type == 1 && !a.parallel_quats) || (a.rot_dist_type == 2 && !a.parallel_quats_180)) return fail("ra_env_post_step: rot_dist_type mod90 / mod180 needs its table of parallel quaternions");
+  if (a.num_active && a.goal_kind >= 3) return fail("ra_env_post_step: num_active with a reach goal (one object)");
+  if (a.num_active && a.max_timesteps_per_goal_per_obj < 0) return fail("ra_env_post_step: negative max_timesteps_per_goal_per_obj");
   if (solver) {
     if (solver->dev.B != b->dev.B || solver->device != b->device) return fail("ra_env_post_step: the two batches must have the same size and device");
     const RbModelDev& ds = solver->model->dev;
@@ -1599,6 +1601,14 @@ int ra_env_recipe_step(rb_batch* b, rb_batch* solver, const ra_recipe_args* args
   if (a.group_mode == 1 && !a.obj_group) return fail("ra_env_recipe_step: group_mode 1 needs obj_group");
   if (a.obj_group && (a.goal_kind == 3 || a.goal_kind == 4)) return fail("ra_env_recipe_step: obj_group with a reach goal (one object: nothing to group)");
   if (a.group_mode == 1 && !(a.sample_lam[0] >= 0.f && a.sample_lam[0] <= a.sample_lam[1])) return fail("ra_env_recipe_step: sample_lam is not a range of non-negative rates");
+  if (a.num_active) {      // per-env object counts
+    if (!a.num_objects_next) return fail("ra_env_recipe_step: num_active needs num_objects_next");
+    if (!(a.goal_kind <= 2 || a.goal_kind == 5)) return fail("ra_env_recipe_step: per-env object counts are built for goal kinds 0, 1, 2 and 5");
+    if (!(a.used_table_portion > 0.f) || !(a.used_table_portion <= 1.0e6f)) return fail("ra_env_recipe_step: num_active needs used_table_portion > 0");
+    for (int k = 0; k < a.num_objects; k++)
+      for (int c = 0; c < 7; c++)
+        if (!(fabsf(a.park_pose[k][c]) < 1.0e4f)) return fail("ra_env_recipe_step: park_pose is not finite (or beyond 1e4: RG_STATUS_BAD_STATE guards 1e10)");
+  }
   RbBatchDev sb; memset(&sb, 0, sizeof sb);
   const RbModelDev* ms = nullptr;
   if (solver) {

@@ -18,8 +18,21 @@ def split_task_args(parameters, constants, num_objects_default, sim_names=(), co
     return parameters, constants, task
 
 
-def check_block_count(num_objects):
+def check_block_count(num_objects, max_num_objects=None):
+    """`max_num_objects` (per-env object counts): the world is the one with that many blocks, and `num_objects`, the first count of every env, any of 1..max."""
     n = int(num_objects)
     counts = SHIPPED_BLOCK_COUNTS
+    if max_num_objects is not None:
+        if int(max_num_objects) not in counts:
+            raise NotImplementedError("max_num_objects=%d: the block tasks are built for worlds of %s objects" % (int(max_num_objects), ", ".join(map(str, counts))))
+        if not 1 <= n <= int(max_num_objects):
+            raise ValueError("num_objects=%d is outside 1..max_num_objects=%d" % (n, int(max_num_objects)))
+        return
     if n not in counts:
         raise NotImplementedError("num_objects=%d: the block tasks are built for %s objects" % (n, ", ".join(map(str, counts))))
+
+
+def refuse_max_num_objects(parameters, task):
+    """the tasks whose goal generator or world is not built for per-env object counts name the parameter they refuse"""
+    if "max_num_objects" in dict((parameters or {}).get("simulation_params", {})):
+        raise NotImplementedError("parameters.simulation_params.max_num_objects (per-env object counts) is not implemented for %s by the batched rearrange env" % task)

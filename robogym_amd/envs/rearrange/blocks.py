@@ -30,6 +30,10 @@ world; the hook runs on the env's own world (rb_tcp_args.self_world) -- ONE phys
 Duplicated-object groups (`object_groups`; the reference's `_randomize_object_groups` + the greedy matching of `ObjectStateGoal.relative_goal`) are opt-in here: the
 default "distinct" keeps every object its own group, where the reference samples groups at every reset.
 
+Per-env object counts (`max_num_objects`; the reference's `simulation_params.max_num_objects` with `num_objects` changing between episodes, simulation/base.py:68-74,
+common/base.py:850-856, 919-927): the batch's world is the M-block world, env e uses its first `num_active[e]` blocks, `num_objects_next` is the device row a curriculum
+writes, latched at every episode start; unused blocks are parked.
+
 Not built for this env: vision, `teleport_to_goal`, masks of the placement area, per-group materials / colours / scales.
 """
 import ctypes
@@ -284,6 +288,25 @@ def _parse_object_groups(object_groups, num_objects):
     return "fixed", counts
 
 
+#: parking of the objects an env does not use (max_num_objects): cells PARK_SPACING apart in a grid PARK_COLUMNS wide, PARK_HEIGHT above the table's centre -- the
+#: floor and table planes are that far below, the arm (reach about 1.3 m from its base), the camera rig and the backdrop (a 2 m half extent) stay more than 2 m away, so
+#: the broadphase drops every pair of a parked block by its bounding sphere or its oriented box; |x| stays far below the 1e10 of RG_STATUS_BAD_STATE
+PARK_SPACING, PARK_COLUMNS, PARK_HEIGHT = 0.5, 4, 6.0
+#: the dof damping of a parked object (N s / m, N m s / rad; the Euler step treats damping implicitly, inv(M + h B): any value is stable)
+PARK_DAMPING = 10.0
+
+
+def parking_poses(table_pos, num_objects):
+    """[N, 7] (position, quaternion w x y z): slot i's parking cell, identity orientation"""
+    i = np.arange(int(num_objects))
+    out = np.zeros((len(i), 7))
+    out[:, 0] = table_pos[0] + PARK_SPACING * (i % PARK_COLUMNS - 0.5 * (PARK_COLUMNS - 1))
+    out[:, 1] = table_pos[1] + PARK_SPACING * (i // PARK_COLUMNS - 0.5 * (PARK_COLUMNS - 1))
+    out[:, 2] = table_pos[2] + PARK_HEIGHT
+    out[:, 3] = 1.0
+    return out
+
+
 class BatchedBlockRearrangeEnv:
     def __init__(self, batch_size: int, device="cuda:0", num_objects: int = 5, starting_seed: int = 0, max_position_change: float = 0.1,
                  arm_reset_controller_error: bool = True, n_random_initial_steps: int = 10, stabilize_steps: int = 100, settle_steps: int = 100,
@@ -295,7 +318,7 @@ class BatchedBlockRearrangeEnv:
                  goal_kind: str = "object_state", height_range=(0.05, 0.25), object_size: float = 0.0254, fixed_order: bool = False, target_height: float = 0.1,
                  object_groups="distinct", sample_lam=SAMPLE_LAM, goal_distance_ratio=1.0, goal_distance_min: float = 0.06, pickup_proba: float = 0.0,
                  stacking_proba: float = 0.0, rot_dist_type: str = "full", randomize_goal_rot: bool = False, model=None, domino_distance_mul: float = 4.0,
-                 relative_placements=None, init_quats=None):
+                 relative_placements=None, init_quats=None, max_num_objects: Optional[int] = None):
         """`per_env_parameters`: every env carries its own copy of the randomisable model fields (`self.sim.params`, LargeModelSimulation(env_params=True)) -- what
         the reference's simulation randomizers and `stabilize_objects` write into `sim.model`.  On by default (measured cost: 0.7 % of the step,
         profiles/r05_ab_rb_env_params.txt); off: the model's own arrays, no randomizers, no damping change while the objects stabilise.
@@ -317,8 +340,35 @@ class BatchedBlockRearrangeEnv:
         goal_kind "fixed" (ObjectFixedStateGoal): `relative_placements` [N, 2] in [0, 1], each object's body origin relative to the placement area, and `init_quats` [N, 4],
         the goals' orientations (rotations about z; default identity) -- the same goal every time.  goal_kind "attached" (envs/rearrange/blocks_attached.py,
         AttachedBlockStateGoal): eight blocks, `object_size` apart from their neighbours' faces, in a 2-4-2 lattice with a random assignment and a random origin.  Both set the
-        goal's orientation themselves: `randomize_goal_rot` has no effect on them, as in the reference."""
+        goal's orientation themselves: `randomize_goal_rot` has no effect on them, as in the reference.
+        `max_num_objects` = M (`simulation_params.max_num_objects`, simulation/base.py:73-74): per-env object counts.  The batch's world is the M-block world, env e uses
+        its first `self.num_active[e]` <= M objects and `num_objects` is every env's first count.  `self.num_objects_next` (int32 [B], a device row a curriculum may write
+        per env; `set_num_objects_next` is the checked host setter) is latched into `num_active` when that env's episode begins -- reset(mask), the host recipe and the
+        device recipe alike; values outside 1..M are clamped.  Every per-object observation key keeps [B, M, ...] with zeros in the unused slots; distances, success, off-table
+        test, finger contacts, group matching, time-out (`max_timesteps_per_goal_per_obj * n`), placements and the placement area (`placement_area(n)`) follow the env's
+        count.  An unused object is parked at `self.park_pose[i]`, its weight cancelled through the env's `xfrc_applied` row and its dof damping raised
+        (`_apply_parking`); rb_step_kernel steps it like any other body.  Goal kinds object_state, pickandplace, stack and train; object_groups
+        "distinct" / "single" / "sample"."""
         self.B, self.N = int(batch_size), int(num_objects)
+        self.max_num_objects = None if max_num_objects is None else int(max_num_objects)
+        if self.max_num_objects is not None:
+            M = self.max_num_objects
+            refuse = lambda what: NotImplementedError("max_num_objects (per-env object counts) is not implemented for %s by the batched rearrange env" % what)
+            if goal_kind not in ("object_state", "pickandplace", "stack", "train"):
+                raise refuse("goal_kind %r (object_state, pickandplace, stack, train)" % (goal_kind,))
+            if not (object_groups is None or (isinstance(object_groups, str) and object_groups in ("distinct", "single", "sample"))):
+                raise refuse("explicit object_groups counts %r (\"distinct\", \"single\", \"sample\")" % (object_groups,))
+            if _solver_mode_name(tcp_solver_mode) == "mocap" and _control_mode_name(control_mode) != "joint":
+                raise refuse("tcp_solver_mode=\"mocap\"")
+            if model is not None or main_model is not None:
+                raise refuse("a world other than load_blocks_model (dominos, ycb)")
+            if not per_env_parameters:
+                raise refuse("per_env_parameters=False (an unused object is held by its env's xfrc_applied and dof_damping rows)")
+            if not 1 <= M <= _native.RA_MAXOBJ:
+                raise ValueError("max_num_objects=%d is outside 1..%d" % (M, _native.RA_MAXOBJ))
+            if not 1 <= self.N <= M:
+                raise ValueError("num_objects=%d is outside 1..max_num_objects=%d" % (self.N, M))
+            self.num_objects_initial, self.N = self.N, M            # (self.N: the world's count, the width of every per-object array)
         if goal_kind not in GOAL_KINDS:
             raise ValueError("goal_kind %r is not one of %s" % (goal_kind, ", ".join(GOAL_KINDS)))
         self.goal_kind_name, self.goal_kind = goal_kind, GOAL_KINDS[goal_kind]
@@ -504,6 +554,16 @@ class BatchedBlockRearrangeEnv:
             ids = group_ids(self.group_counts if self.group_mode == "fixed" else [1] * N)
             self.obj_group = torch.tensor(np.tile(ids, (B, 1)), dtype=torch.int32, device=dev).contiguous()
             a.obj_group = P(self.obj_group)
+        # ---- per-env object counts (max_num_objects): the latched counts, the row a curriculum writes, where an unused object is parked
+        self.num_active = self.num_objects_next = self.park_pose = None
+        if self.max_num_objects is not None:
+            self.num_active = torch.full((B,), self.num_objects_initial, dtype=torch.int32, device=dev)
+            self.num_objects_next = self.num_active.clone()
+            self.park_pose = parking_poses(self.table_pos, N)
+            self._park_pose_dev = torch.tensor(self.park_pose.astype(np.float32), device=dev)
+            self._obj_bodies = torch.tensor([int(a.obj_body[i]) for i in range(N)], device=dev, dtype=torch.long)
+            self._slot = torch.arange(N, device=dev, dtype=torch.int32)
+            a.num_active, a.max_timesteps_per_goal_per_obj = P(self.num_active), int(max_timesteps_per_goal_per_obj)
         self.action_shape = (self.B, self.action_dim)
         self._zero_action = z(B, AD)
         # ---- per-env model parameters: the reference's simulation randomizers (applied after _reset, robot_env.py:779-783) and stabilize_objects' damping change
@@ -585,6 +645,11 @@ class BatchedBlockRearrangeEnv:
             if self.goal_kind == 8:
                 for i in range(N):
                     r.fixed_xy[i][0], r.fixed_xy[i][1], r.fixed_yaw[i] = float(self.relative_placements[i, 0]), float(self.relative_placements[i, 1]), float(self.init_yaw[i])
+            if self.max_num_objects is not None:      # (area_offset / area_size above: the area of an env that uses all N objects)
+                r.num_active, r.num_objects_next, r.used_table_portion = P(self.num_active), P(self.num_objects_next), float(self.used_table_portion)
+                for i in range(N):
+                    for k in range(7):
+                        r.park_pose[i][k] = float(self.park_pose[i, k])
 
     # ------------------------------------------------------------------ launches
     def _stream(self):
@@ -719,14 +784,16 @@ class BatchedBlockRearrangeEnv:
         return out
 
     # ------------------------------------------------------------------ reset (host work + physics launches)
-    def _grid_placement(self, yaw, rows):
+    def _grid_placement(self, yaw, rows, n=None):
         """place_objects_in_grid (common/utils.py:719-829) for boxes: AABB of each yawed block, a grid of cells sized by the largest block over the
-        placement area (simulation/base.py:992-1010), distinct random cells."""
-        B, N = len(rows), self.N
-        half = self._aabb_half(yaw)                                      # rotate_bounding_box
+        placement area (simulation/base.py:992-1010), distinct random cells.  `n`: the first n objects only (`yaw` [len(rows), n]), in the placement area of that count."""
+        B, N = len(rows), self.N if n is None else int(n)
+        obj_center, obj_half = self.obj_center[:N], self.obj_half[:N]
+        # (without per-env counts the helpers are called as they always were: tests stand in for them with the one-argument forms)
+        half = self._aabb_half(yaw) if n is None else self._aabb_half(yaw, N)      # rotate_bounding_box
         c, s_ = np.cos(yaw), np.sin(yaw)
-        centre = np.stack([c * self.obj_center[:, 0] - s_ * self.obj_center[:, 1], s_ * self.obj_center[:, 0] + c * self.obj_center[:, 1], np.broadcast_to(self.obj_center[:, 2], yaw.shape)], -1)
-        (off_x, off_y, _), (width, height, _) = self.placement_area()
+        centre = np.stack([c * obj_center[:, 0] - s_ * obj_center[:, 1], s_ * obj_center[:, 0] + c * obj_center[:, 1], np.broadcast_to(obj_center[:, 2], yaw.shape)], -1)
+        (off_x, off_y, _), (width, height, _) = self.placement_area() if n is None else self.placement_area(n)
         out = np.zeros((B, N, 3))
         xy = np.zeros((B, N, 2))
         ncol, nrow = (width // (2 * half[:, :, 0].max(1))).astype(int), (height // (2 * half[:, :, 1].max(1))).astype(int)
@@ -744,13 +811,13 @@ class BatchedBlockRearrangeEnv:
             # full that mostly runs out of trials on the last large object and starts over).
             pending = np.nonzero(crowded)[0]
             area = np.array([width, height])
-            order = np.argsort(-(self.obj_half[:, 0] * self.obj_half[:, 1]), kind="stable")
+            order = np.argsort(-(obj_half[:, 0] * obj_half[:, 1]), kind="stable")
             rounds = 0
             while len(pending):
                 rounds += 1
                 if rounds > 200:      # (the reference gives up after max_placement_trial_count restarts as well, common/utils.py:623-716)
                     raise RuntimeError("no collision-free placement for %d envs: the objects' bounding boxes cover %.0f %% of the placement area" % (
-                        len(pending), 100 * float((4 * self.obj_half[:, 0] * self.obj_half[:, 1]).sum()) / (width * height)))
+                        len(pending), 100 * float((4 * obj_half[:, 0] * obj_half[:, 1]).sum()) / (width * height)))
                 h = half[pending]
                 cur, alive = np.zeros((len(pending), N, 2)), np.ones(len(pending), dtype=bool)
                 done_objs = []
@@ -775,11 +842,12 @@ class BatchedBlockRearrangeEnv:
         out = p + [off_x, off_y, 0.0] - self.table_size + self.table_pos - centre      # (the body origin, from the centre of its bounding box)
         return out
 
-    def placement_area(self):
+    def placement_area(self, n=None):
         """RearrangeSimulationInterface.get_placement_area / get_table_setting (simulation/base.py:980-1010): (offset, size) of the box objects and goals are placed
-        in, offset measured from the table's low corner; `used_table_portion` is clipped to at least a tenth per object."""
+        in, offset measured from the table's low corner; `used_table_portion` is clipped to at least a tenth per object.  `n`: the area of an env that uses n objects
+        (per-env object counts; default: all of them)."""
         tsx, tsy = 2 * self.table_size[0], 2 * self.table_size[1]
-        portion = float(np.clip(self.used_table_portion, self.N * 0.1, 1.0))
+        portion = float(np.clip(self.used_table_portion, (self.N if n is None else int(n)) * 0.1, 1.0))
         width, height = 0.5 * tsx * portion, 0.38 * tsy * portion
         return (0.5 * tsx - width / 2.0, 0.44 * tsy - height / 2.0, 2 * self.table_size[2]), (width, height, 0.26)
 
@@ -787,8 +855,16 @@ class BatchedBlockRearrangeEnv:
         """`_update_simulation_for_next_goal` (goals/object_state.py:333-358) for the envs `rows`, whose goals have the yaws `yaw` [len(rows), N]: with
         `randomize_goal_rot` new yaws first (per env, in the reference's draw order), then the positions for boxes turned by them; the domino goal sets yaws of its
         own.  -> (positions, yaws): `_write_goal`'s arguments."""
+        counts = self._counts(rows)
         if self.randomize_goal_rot and len(rows):
-            yaw = np.stack([randomize_yaw_along_z(self._rng, y) for y in yaw])
+            if counts is None:
+                yaw = np.stack([randomize_yaw_along_z(self._rng, y) for y in yaw])
+            else:      # (the env's active objects only; an unused slot keeps yaw 0)
+                yaw = np.array(yaw, dtype=np.float64)
+                for r, c in enumerate(counts):
+                    yaw[r, :c] = randomize_yaw_along_z(self._rng, yaw[r, :c])
+        if counts is not None:
+            return self._by_count(rows, yaw, counts, self._goal_positions), yaw
         if self.goal_kind == 6:
             return self._domino_goals(len(rows))
         if self.goal_kind in (7, 8):      # set_target_quat inside _sample_next_goal_positions, AFTER the randomisation: init_quats' yaws, always
@@ -805,10 +881,27 @@ class BatchedBlockRearrangeEnv:
                 self.host_placement_failed += 1
         return pos, yaws
 
-    def _goal_positions(self, rows, yaw):
+    def _counts(self, rows):
+        """per-env object counts: the latched counts of the envs `rows` as host integers (the host recipe reads flags back anyway); None without max_num_objects"""
+        if self.max_num_objects is None:
+            return None
+        return self.num_active[torch.as_tensor(rows, device=self.device, dtype=torch.long)].cpu().numpy().astype(np.int64)
+
+    def _by_count(self, rows, yaw, counts, fn):
+        """per-env object counts: `fn(rows_n, yaw_n, n)` -> [len(rows_n), n, 3] for the rows of each count n (ascending), put together as [len(rows), N, 3] with the
+        unused slots at their parking positions."""
+        rows = np.asarray(rows)
+        out = np.tile(self.park_pose[None, :, :3], (len(rows), 1, 1))
+        for n in np.unique(counts):
+            sel = np.nonzero(counts == n)[0]
+            out[sel, :n] = fn(rows[sel], yaw[sel, :n], int(n))
+        return out
+
+    def _goal_positions(self, rows, yaw, n=None):
         """`_sample_next_goal_positions` of the env's goal generator for the envs `rows` (host numpy; ra_recipe_kernel does the same on the device): [len(rows), N, 3].
-        Reach also moves the object itself (`set_object_pos`: position only) -- the caller's forward makes the observation see it."""
-        R, N, kind = len(rows), self.N, self.goal_kind
+        Reach also moves the object itself (`set_object_pos`: position only) -- the caller's forward makes the observation see it.  `n`: for the first n objects only
+        (`yaw` [len(rows), n]; per-env object counts: kinds 0, 1, 2 and 5)."""
+        R, N, kind = len(rows), self.N if n is None else int(n), self.goal_kind
         if kind == 6:          # (the arc's positions; its yaws go with them through _next_goal)
             return self._domino_goals(R)[0]
         if kind in (7, 8):     # the fixed placements: AttachedBlockStateGoal's lattice (a permutation and an origin per env) / ObjectFixedStateGoal's table
@@ -821,20 +914,21 @@ class BatchedBlockRearrangeEnv:
             idx = torch.as_tensor(rows, device=self.device, dtype=torch.long)
             qpos = self.sim.qpos[idx].cpu().numpy().astype(np.float64)
             ratios = self.goal_distance_ratio[idx].cpu().numpy().astype(np.float64)
-            half = self._aabb_half(yaw)
+            half = self._aabb_half(yaw) if n is None else self._aabb_half(yaw, N)
             c, s_ = np.cos(yaw), np.sin(yaw)
-            centre = np.stack([c * self.obj_center[:, 0] - s_ * self.obj_center[:, 1], s_ * self.obj_center[:, 0] + c * self.obj_center[:, 1], np.broadcast_to(self.obj_center[:, 2], yaw.shape)], -1)
-            offset, size = self.placement_area()
+            oc = self.obj_center[:N]
+            centre = np.stack([c * oc[:, 0] - s_ * oc[:, 1], s_ * oc[:, 0] + c * oc[:, 1], np.broadcast_to(oc[:, 2], yaw.shape)], -1)
+            offset, size = self.placement_area() if n is None else self.placement_area(n)
             pos = np.zeros((R, N, 3))
             for r in range(R):
-                op = np.array([qpos[r, qa:qa + 3] for qa in self.obj_q])
+                op = np.array([qpos[r, qa:qa + 3] for qa in self.obj_q[:N]])
                 pos[r], ok = place_targets_with_goal_distance_ratio(self._rng, centre[r], half[r], self.table_pos, self.table_size, offset, size, op, ratios[r], self.goal_distance_min)
                 if not ok:
                     self.host_placement_failed += 1
                 move_one_object_to_the_air_with_restrictions(self._rng, pos[r], self.height_range, self.object_size, self.pickup_proba, self.stacking_proba, ratios[r])
             return pos
         if kind <= 1:
-            pos = self._grid_placement(yaw, rows)
+            pos = self._grid_placement(yaw, rows) if n is None else self._grid_placement(yaw, rows, n)
             if kind == 1:      # move_one_object_to_the_air (goals/pickandplace.py:30-52): a height, then the object it raises
                 h = self._rng.uniform(self.height_range[0], self.height_range[1], R)
                 pos[np.arange(R), self._rng.randint(N, size=R), 2] += h
@@ -845,7 +939,7 @@ class BatchedBlockRearrangeEnv:
             self.goal_index[idx] = gi
             bottom = DET_REACH_POINTS[gi.cpu().numpy()]
         else:                  # place_objects_with_no_constraint on object 0's box alone
-            bottom = self._free_placement_of_object0(yaw[:, 0])
+            bottom = self._free_placement_of_object0(yaw[:, 0]) if n is None else self._free_placement_of_object0(yaw[:, 0], n)
         if kind == 2:          # ObjectStackGoal: the others on top of object 0's placement, in a shuffled block order unless fixed_order
             pos = np.repeat(bottom[:, None, :], N, 1)
             for r in range(R):
@@ -859,10 +953,10 @@ class BatchedBlockRearrangeEnv:
         pos[:, 0, 2] += self.target_height
         return pos
 
-    def _free_placement_of_object0(self, yaw0):
+    def _free_placement_of_object0(self, yaw0, n=None):
         """place_objects_with_no_constraint (common/utils.py:829-880) for object 0 alone: a uniform proposal inside the placement area (one object: always free);
-        the body origin in world coordinates, as _grid_placement gives it.  `yaw0` [R]."""
-        (off_x, off_y, _), (width, height, _) = self.placement_area()
+        the body origin in world coordinates, as _grid_placement gives it.  `yaw0` [R]; `n`: in the placement area of that object count."""
+        (off_x, off_y, _), (width, height, _) = self.placement_area() if n is None else self.placement_area(n)
         sx, sy = self.obj_half[0, 0], self.obj_half[0, 1]
         c, s_ = np.cos(yaw0), np.sin(yaw0)
         hx, hy = np.abs(c) * sx + np.abs(s_) * sy, np.abs(s_) * sx + np.abs(c) * sy
@@ -885,12 +979,19 @@ class BatchedBlockRearrangeEnv:
         eul = np.zeros(goal_pos.shape); eul[..., 2] = np.mod(yaw + np.pi, 2 * np.pi) - np.pi        # mat2euler of a z-rotation, normalised as get_target_rot + normalize_angles give it
         quat = euler2quat(eul)
         g = np.concatenate([goal_pos, quat], -1).astype(np.float32)
-        self.goal[idx] = torch.tensor(g, device=dev)
+        counts = self._counts(rows)
+        if counts is not None:      # an unused slot: its parked pose in qpos_goal, a zero goal row (identity orientation)
+            unused = np.arange(self.N)[None, :] >= counts[:, None]
+            g[unused] = np.broadcast_to(self.park_pose.astype(np.float32)[None], g.shape)[unused]
+            eul[unused] = 0.0
         self.goal_rot[idx] = torch.tensor(eul.astype(np.float32), device=dev)
         qg = self.sim.qpos[idx].clone()                                   # qpos_goal: the current qpos with the objects at their goals (object_state.py:381-389)
         for i, qa in enumerate(self.obj_q):
             qg[:, qa:qa + 7] = torch.tensor(g[:, i], device=dev)
         self.qpos_goal[idx] = qg
+        if counts is not None:
+            g[unused] = np.array([0, 0, 0, 1, 0, 0, 0], dtype=np.float32)
+        self.goal[idx] = torch.tensor(g, device=dev)
         self.prev_valid[idx] = 0
 
     def _begin_episode_state(self, rows, idx):
@@ -898,8 +999,15 @@ class BatchedBlockRearrangeEnv:
         rotations about z and their placement, bounding boxes / colours of the static observation.  Returns the drawn yaw angles [len(rows), N]."""
         dev, N = self.device, self.N
         A = self.model.arrays
+        counts = None
+        if self.max_num_objects is not None:      # the count of the episode that begins: _recreate_sim builds the simulation with the current num_objects (common/base.py:850-856, 904)
+            self.num_active[idx] = self.num_objects_next[idx].clamp(1, N)
+            counts = self._counts(rows)
         if self.group_mode == "sample":      # _randomize_object_groups: the first act of RearrangeEnv._reset (common/base.py:903)
-            rows_ids = np.stack([group_ids(sample_group_counts(self._rng, N, *self.sample_lam)) for _ in rows])
+            if counts is None:
+                rows_ids = np.stack([group_ids(sample_group_counts(self._rng, N, *self.sample_lam)) for _ in rows])
+            else:      # (over the env's own count; an unused slot belongs to no group: -1)
+                rows_ids = np.stack([np.concatenate([group_ids(sample_group_counts(self._rng, int(c), *self.sample_lam)), np.full(N - int(c), -1, dtype=np.int32)]) for c in counts])
             self.obj_group[idx] = torch.tensor(rows_ids, dtype=torch.int32, device=dev)
         worlds = [(self.sim, A)] + ([] if self.solver_sim is None else [(self.solver_sim, self.solver_model.arrays)])
         if self.per_env_parameters:      # _recreate_sim (common/base.py:850-856): a fresh model -- the previous episode's randomised values are gone
@@ -925,12 +1033,20 @@ class BatchedBlockRearrangeEnv:
             self.solver_sim.eq_data[idx, :7] = torch.tensor([0, 0, 0, 1, 0, 0, 0], dtype=torch.float32, device=dev)     # reset_mocap_welds
         # object rotations about z and grid placement (common/base.py:613-640, 797-822)
         yaw = self._rng.uniform(0.0, 2 * np.pi, (len(rows), N))
-        pos = self._grid_placement(yaw, rows)
+        if counts is None:
+            pos = self._grid_placement(yaw, rows)
+        else:                            # the env's first n objects in the placement area of n objects, the others parked (identity orientation: yaw 0)
+            unused = np.arange(N)[None, :] >= counts[:, None]
+            yaw[unused] = 0.0
+            pos = self._by_count(rows, yaw, counts, lambda rows_n, yaw_n, n: self._grid_placement(yaw_n, rows_n, n))
         quat = np.stack([np.cos(yaw / 2), 0 * yaw, 0 * yaw, np.sin(yaw / 2)], -1)
         for i, qa in enumerate(self.obj_q):
             self.sim.qpos[idx, qa:qa + 7] = torch.tensor(np.concatenate([pos[:, i], quat[:, i]], -1).astype(np.float32), device=dev)
         colors = self._rng.random_sample((len(rows), N, 4)); colors[..., 3] = 1.0
         so = np.concatenate([np.broadcast_to(self._aabb_half(yaw), (len(rows), N, 3)), colors], -1)
+        if counts is not None:
+            so[unused] = 0.0
+            self._apply_parking(self._mask_of(idx))      # (after the block's restore above: a fresh model has no wrench and the model's damping)
         self.static_obs[idx] = torch.tensor(so.astype(np.float32), device=dev)
         return yaw
 
@@ -1095,6 +1211,8 @@ class BatchedBlockRearrangeEnv:
                                      torch.where(self.stabilised[:, None], self._param_defaults["dof_damping"][cols][None, :].expand_as(cur), cur))
             for rz in self.randomizers:
                 rz.randomize(self.sim, self._rand_gen, self.episode_started)
+            if self.max_num_objects is not None:      # parking after the restore, the damping changes and the randomizers, on the recipe's masks
+                self._apply_parking(self.ended | self.stabilised | self.episode_started)
         if self.reach:      # the object the goal moved: _observe_sync's forward for the envs with a new goal (no readback: every env, masked by the reobserve codes)
             self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=(self.reobserve != 2).to(torch.int32))
         had = self.post.frozen
@@ -1110,6 +1228,42 @@ class BatchedBlockRearrangeEnv:
         d = self.sim.params["dof_damping"]
         cols = self.obj_dofs
         d[idx[:, None], cols[None, :]] = self._param_defaults["dof_damping"][cols] if value is None else float(value)
+        if self.max_num_objects is not None:      # (a parked object keeps its own damping)
+            self._apply_parking(self._mask_of(idx))
+
+    def _mask_of(self, idx):
+        mask = torch.zeros(self.B, dtype=torch.bool, device=self.device); mask[idx] = True
+        return mask
+
+    def _apply_parking(self, mask):
+        """Per-env object counts: what holds the unused objects of the envs `mask` ([B] bool, a device mask: tensor ops, no readback) at their parking poses -- their
+        weight cancelled by a force at the body's centre of mass, `xfrc_applied` = - body_mass x gravity from THAT env's rows (so it has to follow the block's restore
+        and the randomizers, which may change both), and the dof damping PARK_DAMPING on their six dofs (so it has to follow stabilize_objects' damping changes).  The
+        poses themselves and zero velocities are written where the episode begins (`_begin_episode_state`, ra_recipe_kernel)."""
+        P, N = self.sim.params, self.N
+        unused = (self._slot[None, :] >= self.num_active[:, None]) & mask[:, None]                       # [B, N]
+        x = P["xfrc_applied"]
+        force = -P["body_mass"][:, self._obj_bodies, None] * P["gravity"][:, None, :]                     # [B, N, 3]
+        cur = x[:, self._obj_bodies]
+        cur[..., :3] = torch.where(unused[..., None], force, cur[..., :3])
+        x[:, self._obj_bodies] = cur
+        d = P["dof_damping"]
+        dc = d[:, self.obj_dofs]
+        d[:, self.obj_dofs] = torch.where(unused.repeat_interleave(6, dim=1), torch.full_like(dc, PARK_DAMPING), dc)
+
+    def set_num_objects_next(self, counts, rows=None):
+        """The object count of the NEXT episode of the envs `rows` (default: every env), checked: an int or one per env, each in 1..max_num_objects.  (Writing
+        `self.num_objects_next` directly, as a curriculum on the device does, is clamped to that range where it is latched.)"""
+        if self.max_num_objects is None:
+            raise ValueError("set_num_objects_next: the env was built without max_num_objects")
+        c = np.asarray(counts)
+        if c.size == 0 or not np.all(c == np.round(c)) or c.min() < 1 or c.max() > self.N:
+            raise ValueError("num_objects_next %r is outside 1..max_num_objects=%d" % (np.asarray(counts).tolist(), self.N))
+        t = torch.as_tensor(c.astype(np.int32), device=self.device)
+        if rows is None:
+            self.num_objects_next.copy_(t.expand(self.B) if t.dim() == 0 else t)
+        else:
+            self.num_objects_next[torch.as_tensor(rows, device=self.device, dtype=torch.long)] = t
 
     def _randomize_simulation(self, idx):
         """`randomization.simulation_randomizer.randomize(mj_sim, random_state)` for the envs `idx` (robot_env.py:779-783): every randomizer draws new values of its
@@ -1119,10 +1273,12 @@ class BatchedBlockRearrangeEnv:
         mask = torch.zeros(self.B, dtype=torch.bool, device=self.device); mask[idx] = True
         for r in self.randomizers:
             r.randomize(self.sim, self._rand_gen, mask)
+        if self.max_num_objects is not None:      # (gravity and body masses may have changed: the cancelling force follows them)
+            self._apply_parking(mask)
 
-    def _aabb_half(self, yaw):
-        """half extents [.., N, 3] of the objects' bounding boxes after a rotation by `yaw` [.., N] about z"""
-        sx, sy, sz = self.obj_half[:, 0], self.obj_half[:, 1], self.obj_half[:, 2]
+    def _aabb_half(self, yaw, n=None):
+        """half extents [.., N, 3] of the objects' bounding boxes after a rotation by `yaw` [.., N] about z (`n`: of the first n objects, `yaw` [.., n])"""
+        sx, sy, sz = self.obj_half[:n, 0], self.obj_half[:n, 1], self.obj_half[:n, 2]
         return np.stack([np.abs(np.cos(yaw)) * sx + np.abs(np.sin(yaw)) * sy, np.abs(np.sin(yaw)) * sx + np.abs(np.cos(yaw)) * sy, np.broadcast_to(sz, yaw.shape)], -1)
 
     def _observe_only(self, rows=None):
@@ -1200,7 +1356,7 @@ def action_bin_array(lower_bound, upper_bound, n_bins, spacing="linear"):
 
 
 SUPPORTED_PARAMETERS = {"simulation_params", "robot_control_params", "n_random_initial_steps"}
-SUPPORTED_SIMULATION_PARAMS = {"num_objects", "penalty", "used_table_portion", "object_groups", "goal_distance_ratio", "goal_distance_min"}
+SUPPORTED_SIMULATION_PARAMS = {"num_objects", "max_num_objects", "penalty", "used_table_portion", "object_groups", "goal_distance_ratio", "goal_distance_min"}
 SUPPORTED_ROBOT_CONTROL_PARAMS = {"max_position_change", "arm_reset_controller_error", "control_mode", "tcp_solver_mode"}
 SUPPORTED_CONSTANTS = {"success_threshold", "successes_needed", "success_reward", "max_timesteps_per_goal_per_obj", "n_action_bins", "action_spacing", "use_goal_distance_reward",
                        "goal_reward_per_object", "normalize_mesh", "randomize", "sample_lam_low", "sample_lam_high"}
@@ -1290,7 +1446,7 @@ def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants
             args[k] = sp[k]
     args.update(group_args(sp, constants))
     args.update(rot_args)
-    for k in ("goal_distance_ratio", "goal_distance_min"):
+    for k in ("goal_distance_ratio", "goal_distance_min", "max_num_objects"):      # (max_num_objects: per-env object counts, num_objects the first count of every env)
         if k in sp:
             args[k] = sp[k]
     if constants.get("randomize", True) is False:    # RobotEnvConstants.randomize (robot_env.py:155): no simulation randomizers at all

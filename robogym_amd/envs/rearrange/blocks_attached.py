@@ -13,7 +13,7 @@ The world is the shipped 5-block model grown to eight blocks (envs/rearrange/xml
 rearrange/ycb).
 Everything else -- physics, observation, reward, tracker, wrappers, pipelined / device resets, control modes, object groups -- is envs/rearrange/blocks.py's."""
 from robogym_amd.envs.rearrange import blocks
-from robogym_amd.envs.rearrange._tasks import split_task_args
+from robogym_amd.envs.rearrange._tasks import refuse_max_num_objects, split_task_args
 from robogym_amd.envs.rearrange.blocks_train import OBJECT_SIZE
 
 #: AttachedBlockRearrangeEnvParameters.simulation_params (blocks_attached.py:18-22); the goal generator hard-codes eight target quaternions (attached_block_state.py:21)
@@ -23,6 +23,7 @@ NUM_OBJECTS = 8
 def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants=None, starting_seed: int = 0, apply_wrappers: bool = True, **kw):
     """`AttachedBlockRearrangeEnv.build`: blocks.make_env with eight blocks and the attached goal.  simulation_params.num_objects (8, nothing else), constants.goal_args:
     rot_dist_type full / mod90 / mod180, randomize_goal_rot (accepted, without effect on this goal), rot_randomize_type "z_axis"."""
+    refuse_max_num_objects(parameters, "rearrange/blocks_attached (AttachedBlockStateGoal places eight blocks)")
     parameters, constants, task = split_task_args(parameters, constants, num_objects_default=NUM_OBJECTS, constant_names=("goal_args",))
     n = int(parameters["simulation_params"]["num_objects"])
     if n != NUM_OBJECTS:

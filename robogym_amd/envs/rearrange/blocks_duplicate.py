@@ -9,7 +9,7 @@ from robogym_amd.envs.rearrange._tasks import check_block_count, split_task_args
 def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants=None, starting_seed: int = 0, apply_wrappers: bool = True, **kw):
     """`DuplicateBlockRearrangeEnv.build`: blocks.make_env with object_groups "single" and two blocks by default."""
     parameters, constants, task = split_task_args(parameters, constants, num_objects_default=2, sim_names=("object_groups",))
-    check_block_count(parameters["simulation_params"]["num_objects"])
+    check_block_count(parameters["simulation_params"]["num_objects"], parameters["simulation_params"].get("max_num_objects"))
     if task.get("object_groups", "single") != "single":
         raise ValueError("blocks_duplicate puts every block in one group; object_groups=%r belongs to envs/rearrange/blocks.py" % (task["object_groups"],))
     return blocks.make_env(batch_size, device=device, parameters=parameters, constants=constants, starting_seed=starting_seed, apply_wrappers=apply_wrappers,

@@ -12,7 +12,7 @@ OBJECT_SIZE = 0.0254
 def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants=None, starting_seed: int = 0, apply_wrappers: bool = True, **kw):
     """`BlockStackEnv.build`: blocks.make_env with goal_kind "stack", two blocks by default; constants.fixed_order."""
     parameters, constants, task = split_task_args(parameters, constants, num_objects_default=2, constant_names=("fixed_order",))
-    check_block_count(parameters["simulation_params"]["num_objects"])
+    check_block_count(parameters["simulation_params"]["num_objects"], parameters["simulation_params"].get("max_num_objects"))
     return blocks.make_env(batch_size, device=device, parameters=parameters, constants=constants, starting_seed=starting_seed, apply_wrappers=apply_wrappers,
                            goal_kind="stack", object_size=OBJECT_SIZE, fixed_order=bool(task.get("fixed_order", False)), **kw)
 

@@ -20,7 +20,7 @@ def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants
     """`BlockTrainRearrangeEnv.build`: blocks.make_env with goal_kind "train", five blocks, sampled groups; simulation_params.goal_distance_ratio / goal_distance_min,
     constants.goal_args {pickup_proba, stacking_proba, height_range, rot_dist_type (full / mod90 / mod180), randomize_goal_rot}, constants.use_cuboid, constants.goal_generation ("train" only)."""
     parameters, constants, task = split_task_args(parameters, constants, num_objects_default=5, constant_names=("goal_args", "use_cuboid", "goal_generation"))
-    check_block_count(parameters["simulation_params"]["num_objects"])
+    check_block_count(parameters["simulation_params"]["num_objects"], parameters["simulation_params"].get("max_num_objects"))
     if task.get("goal_generation", "train") != "train":
         raise NotImplementedError("constants.goal_generation %r: blocks_train is built with \"train\"" % (task["goal_generation"],))
     scales = {k: parameters.pop(k) for k in ("object_scale_low", "object_scale_high") if k in parameters}

@@ -280,6 +280,9 @@ def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants
     sp, rc = dict(parameters.get("simulation_params", {})), dict(parameters.get("robot_control_params", {}))
     if parameters.get("mesh_names") is not None or constants.get("normalize_mesh"):
         raise NotImplementedError("mesh_names / normalize_mesh: the shipped models hold fixed object sets")
+    if "max_num_objects" in sp:
+        raise NotImplementedError("parameters.simulation_params.max_num_objects (per-env object counts) is not implemented for the ycb worlds (their objects differ: "
+                                  "a prefix of a set is no set of its own); rearrange/blocks and its tasks take it")
     _check_supported({k: v for k, v in parameters.items() if k != "mesh_names"}, sp, rc, constants)
     args = dict(num_objects=sp.get("num_objects", 8), max_position_change=rc.get("max_position_change", 0.1), arm_reset_controller_error=rc.get("arm_reset_controller_error", True),
                 n_random_initial_steps=parameters.get("n_random_initial_steps", 10), starting_seed=starting_seed, wrappers=bool(apply_wrappers),
