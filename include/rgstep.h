@@ -486,7 +486,7 @@ int rb_tcp_args_size(void);   /* sizeof(rb_tcp_args): a binding checks its own l
  * at most 8), or one launch each, in order, when they do not match.  Results are those of the separate launches, bit for bit.
  * While recording: the `stream` argument of the recorded calls is IGNORED (rb_multi_launch's stream is the one); a batch may be recorded once only
  * (rb_multi_launch refuses a duplicate: two workgroups would step the same rows); the entry points that are not recordable -- rb_env_post_step, ra_env_post_step,
- * ra_env_recipe_step, rb_cube_ops, rb_batch_set_constants -- fail instead of running ahead of the recorded physics. */
+ * ra_env_recipe_step, rb_cube_ops, rb_batch_set_constants, and the ICP launch of rgstep_icp.h -- fail instead of running ahead of the recorded physics. */
 int rb_multi_begin(void);
 int rb_multi_launch(void* stream);
 /* mj_setConst on the large-model stepper: rb_batch_set_constants, the counterpart of rg_batch_set_constants: the three _invweight0 rows of the masked envs'
@@ -535,7 +535,7 @@ typedef struct ra_post_args {
    * ObjectStateGoal.relative_goal (goals/object_state.py:520-554) matches objects to goals inside each group greedily by position distance, and the relative goal,
    * both distances and the success count go through that match.  goal_obj_pos / goal_obj_rot / qpos_goal stay indexed by goal.  Kinds 0-2 only. */
   const int* obj_group;
-  /* rotation distance modes (appended; zero-filled = "full", the path above).  rot_dist_type 0: full -- quat2euler(q_goal conj(q_obj)); 1: mod90, 2: mod180 --
+  /* rotation distance modes (appended; zero-filled = "full", the path above; 3: icp, below).  rot_dist_type 0: full -- quat2euler(q_goal conj(q_obj)); 1: mod90, 2: mod180 --
    * euler_angle_difference_single_pair (goals/object_state.py:25-64): of diff_p = quat_difference(q_goal p, q_obj) over the 24 (mod90) or 4 (mod180) parallel quaternions
    * p, in the table's order, the first with the smallest quat_magnitude; the relative rotation is its Euler angles, the distance its angle.  Without the reference's
    * np.allclose(q_goal, q_obj) -> zeros shortcut (p = identity gives the same zeros).  The tables are the caller's: device pointers to EXACTLY 24 x 4 and 4 x 4 floats (the kernel reads those lengths, nothing carries them)
@@ -551,9 +551,15 @@ typedef struct ra_post_args {
    * max_timesteps_per_goal_per_obj * n (common/base.py:919-927); max_timesteps_per_goal is not read then.  qpos / qpos_goal keep the world's full nq. */
   const int* num_active;
   int max_timesteps_per_goal_per_obj;
+  /* rot_dist_type 3: icp (appended; NULL = none, every path above as it is).  icp_rel [B][N][3]: what the ICP launch (rgstep_icp.h) wrote for this state -- per object the Euler angles of
+   * the ICP fit against the goal it is measured against (the group matching is already applied), before normalize_angles, or (pi/2, pi/2, pi/2) where the fit was refused
+   * (goals/object_state.py:258-290).  With rot_dist_type 3 the relative rotation is normalize_angles(icp_rel) and the rotation distance the angle of euler2quat of it
+   * (goal_distance, :586-599); rot_dist_type 3 without icp_rel is an error.  Kinds 0-2. */
+  const float* icp_rel;
 } ra_post_args;
 int ra_env_post_step(rb_batch* main, rb_batch* solver, const ra_post_args* args, void* stream);
 int ra_post_args_size(void);
+/* rot_dist_type icp -- ra_env_icp, ra_icp_args: declared and described in rgstep_icp.h, which the end of this header includes. */
 /* ---- the reset recipe and the goal sampling of the rearrange envs on the device (pipelined resets: an ended episode restarts INSIDE the following step calls),
  * one launch after ra_env_post_step; no host readback.  Per env: the recipe's stage machine — stabilise (stabilize_steps, the stored controls held) -> one random
  * action for n_random_initial_steps (RearrangeEnv._randomize_robot_initial_position, /root/reference/robogym/envs/rearrange/common/base.py:498-510) -> settle_steps
@@ -710,4 +716,5 @@ const char* rg_last_error(void);
 }
 #endif
 #include "rgstep_setconst.h"
+#include "rgstep_icp.h"
 #endif

@@ -96,13 +96,23 @@ def _ra_post_fields():
             + [("goal_kind", _i), ("grip_site", _i), ("goal_dist_extra", _p)]
             + [("obj_group", _p)]
             + [("parallel_quats", _p), ("parallel_quats_180", _p), ("rot_dist_type", _i)]
-            + [("num_active", _p), ("max_timesteps_per_goal_per_obj", _i)])
+            + [("num_active", _p), ("max_timesteps_per_goal_per_obj", _i)]
+            + [("icp_rel", _p)])
 
 
 class RaPostArgs(ctypes.Structure):
     """`ra_post_args` of include/rgstep.h (field order and types must match; bind() checks the size)."""
 
     _fields_ = _ra_post_fields()
+
+
+class RaIcpArgs(ctypes.Structure):
+    """`ra_icp_args` of include/rgstep.h (field order and types must match; bind() checks the size)."""
+
+    _fields_ = [("icp_rel", ctypes.c_void_p), ("goal", ctypes.c_void_p), ("num_objects", ctypes.c_int), ("obj_body", ctypes.c_int * RA_MAXOBJ),
+                ("src", ctypes.c_void_p), ("src_stride", ctypes.c_int), ("src_num", ctypes.c_void_p), ("tgt", ctypes.c_void_p), ("tgt_total", ctypes.c_int),
+                ("tgt_adr", ctypes.c_void_p), ("tgt_num", ctypes.c_void_p), ("error_threshold", ctypes.c_float), ("obj_group", ctypes.c_void_p),
+                ("num_active", ctypes.c_void_p), ("frozen", ctypes.c_void_p)]
 
 
 def _ra_recipe_fields():
@@ -182,6 +192,7 @@ EXPORTS = [
     "rg_wrap_layout", "rg_wrap_pre_step", "rg_wrap_post_step", "rg_wrap_args_size", "rg_items_per_cu", "rg_kernel_resources",
 ]
 EXPORTS_SETCONST = ["rb_batch_set_constants"]      # include/rgstep_setconst.h (EXPORTS is what include/rgstep.h itself declares)
+EXPORTS_ICP = ["ra_env_icp", "ra_icp_args_size"]      # include/rgstep_icp.h
 
 
 
@@ -275,6 +286,10 @@ def bind(path):
     L.ra_post_args_size.restype = ci
     if L.ra_post_args_size() != ctypes.sizeof(RaPostArgs):
         raise NativeError("ra_post_args layout mismatch between include/rgstep.h and robogym_amd/_native.py")
+    L.ra_env_icp.argtypes = [vp, ctypes.POINTER(RaIcpArgs), vp]
+    L.ra_icp_args_size.restype = ci
+    if L.ra_icp_args_size() != ctypes.sizeof(RaIcpArgs):
+        raise NativeError("ra_icp_args layout mismatch between include/rgstep.h and robogym_amd/_native.py")
     L.ra_env_recipe_step.argtypes = [vp, vp, ctypes.POINTER(RaRecipeArgs), vp]
     L.ra_recipe_args_size.restype = ci
     if L.ra_recipe_args_size() != ctypes.sizeof(RaRecipeArgs):

@@ -8,7 +8,7 @@
 //                                                                 robot/ur16e/mujoco/simulation/base.py:142-167 (gripper - table plane)
 //   check_objects_off_table                                       envs/rearrange/simulation/base.py:805-832
 //   reward / done                                                 envs/rearrange/common/base.py:768-795, 824-848
-//   ObjectStateGoal.relative_goal / goal_distance                 envs/rearrange/goals/object_state.py:492-599 (rot_dist_type full / mod90 / mod180; duplicated-object groups: ra_group_match)
+//   ObjectStateGoal.relative_goal / goal_distance                 envs/rearrange/goals/object_state.py:492-599 (rot_dist_type full / mod90 / mod180, and icp through ra_icp_kernel.h; duplicated-object groups: ra_group_match)
 //   _get_goal_info, MultiGoalTracker.process                      robot_env.py:577-625, utils/multi_goal_tracker.py:157-241
 //   JointControlledTcpArm.on_observations_updated                 robot/ur16e/mujoco/joint_controlled_tcp_arm.py:114-129 (gripper state -> solver world)
 //   per-env object counts (num_active: zero padding to max_num_objects) envs/rearrange/simulation/base.py:73-74, 222-224, 1015-1024; common/base.py:751-757, 919-927
@@ -111,7 +111,14 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
     const float* gm = a.goal + ((size_t)e * N + mgoal) * 7;
     float qc[4] = {xquat[4 * b], -xquat[4 * b + 1], -xquat[4 * b + 2], -xquat[4 * b + 3]}, qd[4], Md[9], rel[3];
     if (reach) { qc[0] = 1.f; qc[1] = qc[2] = qc[3] = 0.f; }      // ObjectReachGoal.current_state: the achieved rotation is zero
-    if (a.rot_dist_type == 0) {
+    if (a.rot_dist_type == 3) {
+      // icp: _icp_euler_angle_difference's angles for this object against its matched goal, as ra_icp_kernel left them (ra_icp_kernel.h); relative_goal normalises them
+      // and goal_distance takes the angle of euler2quat of the result (goals/object_state.py:579-599): q = qx(e0) qy(e1) qz(e2), robogym/utils/rotation.py euler2quat
+      const float* ir = a.icp_rel + ((size_t)e * N + lane) * 3;
+      for (int k = 0; k < 3; k++) rel[k] = rbc_wrap(ir[k]);
+      const float cx = cosf(0.5f * rel[0]), sx = sinf(0.5f * rel[0]), cy = cosf(0.5f * rel[1]), sy = sinf(0.5f * rel[1]), cz = cosf(0.5f * rel[2]), sz = sinf(0.5f * rel[2]);
+      qd[0] = cx * cy * cz - sx * sy * sz; qd[1] = sx * cy * cz + cx * sy * sz; qd[2] = cx * sy * cz - sx * cy * sz; qd[3] = cx * cy * sz + sx * sy * cz;
+    } else if (a.rot_dist_type == 0) {
       rbc_qmul(gm + 3, qc, qd);               // subtract_euler(goal, current) = quat2euler(q_goal conj(q_obj))
     } else {
       // mod90 / mod180, euler_angle_difference_single_pair (goals/object_state.py:25-64): diff_p = quat_difference(q_goal p, q_obj) over the table's parallel
@@ -129,8 +136,10 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
         if (w > best) { best = w; qd[0] = d[0]; qd[1] = d[1]; qd[2] = d[2]; qd[3] = d[3]; }
       }
     }
-    rbc_quat2mat(qd, Md); rbc_mat2euler(Md, rel);
-    for (int k = 0; k < 3; k++) rel[k] = rbc_wrap(rel[k]);
+    if (a.rot_dist_type != 3) {
+      rbc_quat2mat(qd, Md); rbc_mat2euler(Md, rel);
+      for (int k = 0; k < 3; k++) rel[k] = rbc_wrap(rel[k]);
+    }
     const float* ach = reach ? grip : xpos + 3 * b;                // ... and the achieved position the grip site's
     const float rx = gm[0] - ach[0], ry = gm[1] - ach[1], rz = gm[2] - ach[2];
     dpos = fmaxf(sqrtf(rx * rx + ry * ry + rz * rz) + a.goal_pos_offset, 0.f);
@@ -743,3 +752,5 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
 }
 
 }  // namespace rgb
+
+#include "ra_icp_kernel.h"      // rot_dist_type icp: its own launch in front of ra_post_step_kernel (calls ra_group_match)

@@ -9,6 +9,7 @@ typedef rg_post_args RgPostArgs;
 typedef rb_post_args RbPostArgs;
 typedef ra_post_args RaPostArgs;
 typedef ra_recipe_args RaRecipeArgs;
+typedef ra_icp_args RaIcpArgs;
 #define RG_NS rgs
 #define RG_MAXCON 24
 #define RG_CPOOL 768
@@ -1549,7 +1550,9 @@ int ra_env_post_step(rb_batch* b, rb_batch* solver, const ra_post_args* args, vo
   if (a.goal_kind == 2 && !a.goal_dist_extra) return fail("ra_env_post_step: the stack goal needs goal_dist_extra");
   if (a.goal_kind >= 3 && a.num_objects != 1) return fail("ra_env_post_step: the reach goals take exactly one object");
   if (a.obj_group && a.goal_kind >= 3) return fail("ra_env_post_step: obj_group with a reach goal (one object: nothing to match)");
-  if (a.rot_dist_type < 0 || a.rot_dist_type > 2) return fail("ra_env_post_step: rot_dist_type out of range (0 full, 1 mod90, 2 mod180)");
+  if (a.rot_dist_type < 0 || a.rot_dist_type > 3) return fail("ra_env_post_step: rot_dist_type out of range (0 full, 1 mod90, 2 mod180, 3 icp)");
+  if (a.rot_dist_type == 3 && !a.icp_rel) return fail("ra_env_post_step: rot_dist_type icp needs icp_rel (ra_env_icp writes it)");
+  if (a.rot_dist_type == 3 && a.goal_kind >= 3) return fail("ra_env_post_step: rot_dist_type icp with a reach goal (the achieved rotation is zero: no object cloud to fit)");
   if ((a.rot_dist_type == 1 && !a.parallel_quats) || (a.rot_dist_type == 2 && !a.parallel_quats_180)) return fail("ra_env_post_step: rot_dist_type mod90 / mod180 needs its table of parallel quaternions");
   if (a.num_active && a.goal_kind >= 3) return fail("ra_env_post_step: num_active with a reach goal (one object)");
   if (a.num_active && a.max_timesteps_per_goal_per_obj < 0) return fail("ra_env_post_step: negative max_timesteps_per_goal_per_obj");
@@ -1561,6 +1564,22 @@ int ra_env_post_step(rb_batch* b, rb_batch* solver, const ra_post_args* args, vo
   } else { a.solver_qpos = nullptr; a.solver_ctrl = nullptr; }
   DeviceGuard g(b->device);
   return launch(rgb::ra_post_step_kernel, b->dev.B, 64, 0, 0, stream, b->model->dev_copy, b->dev, a);   // (no LDS)
+}
+int ra_icp_args_size(void) { return (int)sizeof(ra_icp_args); }
+int ra_env_icp(rb_batch* b, const ra_icp_args* args, void* stream) {
+  if (g_multi) return not_recordable("ra_env_icp");
+  if (!b || !args) return fail("null argument");
+  const ra_icp_args& a = *args;
+  const RbModelDev& d = b->model->dev;
+  if (!a.icp_rel || !a.goal || !a.src || !a.src_num || !a.tgt || !a.tgt_adr || !a.tgt_num) return fail("ra_env_icp: a required array is NULL");
+  if (a.num_objects < 1 || a.num_objects > RA_MAXOBJ) return fail("ra_env_icp: num_objects out of range");
+  for (int k = 0; k < a.num_objects; k++) if (a.obj_body[k] <= 0 || a.obj_body[k] >= d.nbody) return fail("ra_env_icp: object body id out of range");
+  if (a.src_stride < 1 || a.src_stride > RA_ICP_MAXSRC) return fail("ra_env_icp: src_stride out of range (1..512 source points per object)");
+  if (a.tgt_total < 1) return fail("ra_env_icp: empty target cloud");
+  if (!(a.error_threshold > 0.f)) return fail("ra_env_icp: error_threshold must be positive");
+  if ((long long)b->dev.B * a.num_objects > 0x7fffffffLL) return fail("ra_env_icp: batch x objects exceeds the grid");
+  DeviceGuard g(b->device);
+  return launch(rgb::ra_icp_kernel, b->dev.B * a.num_objects, RA_ICP_THREADS, 0, sizeof(rgb::RaIcpLds), stream, b->model->dev_copy, b->dev, a);
 }
 int ra_recipe_args_size(void) { return (int)sizeof(ra_recipe_args); }
 int ra_env_recipe_step(rb_batch* b, rb_batch* solver, const ra_recipe_args* args, void* stream) {

@@ -57,8 +57,8 @@ FLAG_FULL_FORWARD = 32
 GOAL_KINDS = {"object_state": 0, "pickandplace": 1, "stack": 2, "reach": 3, "det-reach": 4, "train": 5, "dominos": 6, "attached": 7, "fixed": 8}
 #: AttachedBlockStateGoal's cells (goals/attached_block_state.py:34-49), in steps of one block: a row of 2, a row of 4, a row of 2
 ATTACHED_LATTICE = np.array([[1, 0], [2, 0], [0, 1], [1, 1], [2, 1], [3, 1], [1, 2], [2, 2]], dtype=np.float64)
-#: GoalArgs.rot_dist_type (goals/object_state.py:127-131) -> ra_post_args.rot_dist_type; "icp" is not built
-ROT_DIST_TYPES = {"full": 0, "mod90": 1, "mod180": 2}
+#: GoalArgs.rot_dist_type (goals/object_state.py:127-131) -> ra_post_args.rot_dist_type; "icp": one more launch in front of the env kernel (ra_env_icp, csrc/ra_icp_kernel.h)
+ROT_DIST_TYPES = {"full": 0, "mod90": 1, "mod180": 2, "icp": 3}
 #: DominoStateGoal's attempts per goal (goals/dominos.py:10)
 DOMINO_MAX_RETRY = 1000
 #: DeterministicReachGoal's two object positions (goals/object_reach_goal.py:65-66)
@@ -308,6 +308,10 @@ def parking_poses(table_pos, num_objects):
 
 
 class BatchedBlockRearrangeEnv:
+    #: whether the class takes rot_dist_type "icp".  The block envs keep refusing it (boxes: mod90 / mod180 are their exact distances); the mesh envs of
+    #: envs/rearrange/ycb.py, the same class on another model, switch it on
+    ICP_ROT_DIST = False
+
     def __init__(self, batch_size: int, device="cuda:0", num_objects: int = 5, starting_seed: int = 0, max_position_change: float = 0.1,
                  arm_reset_controller_error: bool = True, n_random_initial_steps: int = 10, stabilize_steps: int = 100, settle_steps: int = 100,
                  success_threshold=None, penalty=None, max_timesteps_per_goal_per_obj: int = 200, successes_needed: int = 5, success_reward: float = 5.0,
@@ -318,7 +322,8 @@ class BatchedBlockRearrangeEnv:
                  goal_kind: str = "object_state", height_range=(0.05, 0.25), object_size: float = 0.0254, fixed_order: bool = False, target_height: float = 0.1,
                  object_groups="distinct", sample_lam=SAMPLE_LAM, goal_distance_ratio=1.0, goal_distance_min: float = 0.06, pickup_proba: float = 0.0,
                  stacking_proba: float = 0.0, rot_dist_type: str = "full", randomize_goal_rot: bool = False, model=None, domino_distance_mul: float = 4.0,
-                 relative_placements=None, init_quats=None, max_num_objects: Optional[int] = None):
+                 relative_placements=None, init_quats=None, max_num_objects: Optional[int] = None, icp_max_num_vertices: int = 500, icp_error_threshold: float = 0.15,
+                 icp_use_bbox_precheck: bool = False):
         """`per_env_parameters`: every env carries its own copy of the randomisable model fields (`self.sim.params`, LargeModelSimulation(env_params=True)) -- what
         the reference's simulation randomizers and `stabilize_objects` write into `sim.model`.  On by default (measured cost: 0.7 % of the step,
         profiles/r05_ab_rb_env_params.txt); off: the model's own arrays, no randomizers, no damping change while the objects stabilise.
@@ -333,7 +338,13 @@ class BatchedBlockRearrangeEnv:
         goal_kind "train" (envs/rearrange/blocks_train.py): `goal_distance_ratio` (a scalar or [B]: `self.goal_distance_ratio`, a device row a curriculum may write per
         env), `goal_distance_min`, `pickup_proba`, `stacking_proba`, with `height_range` and `object_size`.
         `rot_dist_type` (GoalArgs, goals/object_state.py:127-131): "full" (default), "mod90" or "mod180" -- the rotation distance of the env kernel
-        (ra_post_args.rot_dist_type; the tables of parallel quaternions are device tensors built from utils/rotation.py).  `randomize_goal_rot`: every goal's yaw is the
+        (ra_post_args.rot_dist_type; the tables of parallel quaternions are device tensors built from utils/rotation.py) -- or, in a subclass that sets `ICP_ROT_DIST`
+        (BatchedYcbRearrangeEnv; this class itself refuses it), "icp": the objects' point clouds are made
+        from the model once (envs/rearrange/icp.py object_point_clouds with `icp_max_num_vertices`, `icp_error_threshold`; `self.icp_clouds`, device tensors) and
+        `ra_env_icp` runs in front of EVERY launch of the env kernel, one ICP per (env, object), writing `self.icp_rel` [B, N, 3], which the env kernel reads
+        (ra_post_args.icp_rel).  `icp_use_bbox_precheck` is accepted and has NO effect: in the reference both "bounding_box" entries the precheck compares are the TARGET's
+        box (goals/object_state.py:420-425 and 483-488), so its IoU is 1 and the ICP always runs.  Not with the reach goals (their achieved rotation is zero).  With any
+        other `rot_dist_type` there is no launch and no allocation for it.  `randomize_goal_rot`: every goal's yaw is the
         previous one plus U(0, 2 pi) per object (`rot_randomize_type` "z_axis"), its placement made with the boxes turned by the new yaws.
         `model`: a compiled main world in place of `load_blocks_model(num_objects)` (envs/rearrange/dominos.py: the domino world); goal_kind "dominos" places the goals on a
         circle arc, `object_size * domino_distance_mul` apart, with per-object goal yaws (DominoStateGoal).
@@ -373,8 +384,6 @@ class BatchedBlockRearrangeEnv:
             raise ValueError("goal_kind %r is not one of %s" % (goal_kind, ", ".join(GOAL_KINDS)))
         self.goal_kind_name, self.goal_kind = goal_kind, GOAL_KINDS[goal_kind]
         if rot_dist_type not in ROT_DIST_TYPES:
-            if rot_dist_type == "icp":
-                raise NotImplementedError("rot_dist_type \"icp\" is not implemented by the batched rearrange env (full, mod90, mod180)")
             raise ValueError("rot_dist_type %r is not one of %s" % (rot_dist_type, ", ".join(ROT_DIST_TYPES)))
         self.rot_dist_type, self.randomize_goal_rot, self.domino_distance_mul = rot_dist_type, bool(randomize_goal_rot), float(domino_distance_mul)
         if self.goal_kind == 6 and not (float(object_size) > 0 and self.domino_distance_mul > 0):
@@ -392,6 +401,12 @@ class BatchedBlockRearrangeEnv:
                 raise ValueError("relative_placements must be [%d, 2] with every entry in [0, 1], got %r" % (self.N, np.asarray(relative_placements).tolist()))
             self.init_yaw = z_rotation_yaws(init_quats, self.N)
         self.reach = self.goal_kind in (3, 4)
+        if rot_dist_type == "icp" and not self.ICP_ROT_DIST:
+            raise NotImplementedError("rot_dist_type \"icp\" is built for the mesh worlds (envs/rearrange/ycb.py BatchedYcbRearrangeEnv), not for the block envs "
+                                      "(full, mod90, mod180: a box's symmetries are what mod90 / mod180 state exactly)")
+        if rot_dist_type == "icp" and self.reach:
+            raise NotImplementedError("rot_dist_type \"icp\" with goal_kind %r: the reach goals' achieved rotation is zero, there is no object cloud to fit (full, mod90, mod180)" % (goal_kind,))
+        self.icp_max_num_vertices, self.icp_error_threshold, self.icp_use_bbox_precheck = int(icp_max_num_vertices), float(icp_error_threshold), bool(icp_use_bbox_precheck)
         self.goal_distance_min, self.pickup_proba, self.stacking_proba = float(goal_distance_min), float(pickup_proba), float(stacking_proba)
         if not (self.goal_distance_min >= 0 and self.pickup_proba >= 0 and self.stacking_proba >= 0 and self.pickup_proba + self.stacking_proba <= 1.0):
             raise ValueError("goal_distance_min >= 0 and 0 <= pickup_proba + stacking_proba <= 1 (got %r, %r, %r)" % (goal_distance_min, pickup_proba, stacking_proba))
@@ -564,6 +579,22 @@ class BatchedBlockRearrangeEnv:
             self._obj_bodies = torch.tensor([int(a.obj_body[i]) for i in range(N)], device=dev, dtype=torch.long)
             self._slot = torch.arange(N, device=dev, dtype=torch.int32)
             a.num_active, a.max_timesteps_per_goal_per_obj = P(self.num_active), int(max_timesteps_per_goal_per_obj)
+        # ---- rot_dist_type icp: the clouds (constant, per object), the angles ra_env_icp leaves for the env kernel, its arguments
+        self.icp = self.icp_rel = self.icp_clouds = None
+        if rot_dist_type == "icp":
+            from robogym_amd.envs.rearrange.icp import object_point_clouds
+            src, src_num, tgt, tgt_adr, tgt_num = object_point_clouds(main, N, self.icp_error_threshold, self.icp_max_num_vertices)
+            self.icp_clouds = tuple(torch.as_tensor(x, device=dev).contiguous() for x in (src, src_num, tgt, tgt_adr, tgt_num))
+            self.icp_rel = z(B, N, 3)
+            c = self.icp = _native.RaIcpArgs()
+            c.icp_rel, c.goal, c.num_objects = P(self.icp_rel), P(self.goal), N
+            for i in range(N):
+                c.obj_body[i] = a.obj_body[i]
+            c.src, c.src_stride, c.src_num = P(self.icp_clouds[0]), int(src.shape[1]), P(self.icp_clouds[1])
+            c.tgt, c.tgt_total, c.tgt_adr, c.tgt_num = P(self.icp_clouds[2]), int(tgt.shape[0]), P(self.icp_clouds[3]), P(self.icp_clouds[4])
+            c.error_threshold = self.icp_error_threshold
+            c.obj_group, c.num_active = a.obj_group, a.num_active
+            a.icp_rel = P(self.icp_rel)
         self.action_shape = (self.B, self.action_dim)
         self._zero_action = z(B, AD)
         # ---- per-env model parameters: the reference's simulation randomizers (applied after _reset, robot_env.py:779-783) and stabilize_objects' damping change
@@ -656,6 +687,9 @@ class BatchedBlockRearrangeEnv:
         return None if self.sim._emul else ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _post(self):
+        if self.icp is not None:      # rot_dist_type icp: the angles of this state, for the envs this launch of the env kernel scores (the same frozen codes)
+            self.icp.frozen = self.post.frozen
+            _native.check(self._L, self._L.ra_env_icp(self.sim._bh, ctypes.byref(self.icp), self._stream()), "ra_env_icp")
         _native.check(self._L, self._L.ra_env_post_step(self.sim._bh, None if self.solver_sim is None else self.solver_sim._bh, ctypes.byref(self.post), self._stream()), "ra_env_post_step")
 
     def _joint_action(self, actions, wrapped):
@@ -1394,20 +1428,28 @@ def _check_supported(parameters, sp, rc, constants):
     _solver_mode_name(rc.get("tcp_solver_mode", "mocap_ik"))
 
 
-def goal_rot_args(goal_args, where="constants.goal_args", other=()):
-    """The constructor's keywords from the `GoalArgs` keys that concern the goal's orientation (goals/object_state.py:122-139): `rot_dist_type` (full / mod90 / mod180),
-    `randomize_goal_rot`, `rot_randomize_type` ("z_axis" only: "block" and "full" need goal boxes for orientations that are no yaw).  A key outside these and `other`
-    raises, named."""
+def goal_rot_args(goal_args, where="constants.goal_args", other=(), icp=False):
+    """The constructor's keywords from the `GoalArgs` keys that concern the goal's orientation (goals/object_state.py:122-149): `rot_dist_type` (full / mod90 / mod180 /
+    icp), `randomize_goal_rot`, `rot_randomize_type` ("z_axis" only: "block" and "full" need goal boxes for orientations that are no yaw), and icp's
+    `icp_max_num_vertices`, `icp_error_threshold`, `icp_use_bbox_precheck`.  The last is accepted and has NO effect: the precheck compares current_state["bounding_box"]
+    with goal_state["bounding_box"], and the reference fills BOTH from get_target_bounding_boxes_in_table_coordinates (goals/object_state.py:420-425 and 483-488) -- the
+    IoU is 1 > 0.75, the ICP always runs.  `icp=True` (ycb.make_env) lets rot_dist_type "icp" and its three keys through; the block envs' surfaces keep refusing them by name.
+    A key outside these and `other` raises, named."""
     goal_args = dict(goal_args or {})
-    known = {"rot_dist_type", "randomize_goal_rot", "rot_randomize_type"} | set(other)
+    icp_keys = ("icp_max_num_vertices", "icp_error_threshold", "icp_use_bbox_precheck")
+    known = {"rot_dist_type", "randomize_goal_rot", "rot_randomize_type"} | set(other) | (set(icp_keys) if icp else set())
     unknown = sorted(set(goal_args) - known)
     if unknown:
         raise NotImplementedError("%s: %s not implemented by the batched rearrange env (supported: %s)" % (where, ", ".join(unknown), ", ".join(sorted(known))))
     out = {}
     if "rot_dist_type" in goal_args:
-        if goal_args["rot_dist_type"] not in ROT_DIST_TYPES:
-            raise NotImplementedError("%s.rot_dist_type %r is not implemented by the batched rearrange env (%s)" % (where, goal_args["rot_dist_type"], ", ".join(ROT_DIST_TYPES)))
+        allowed = [k for k in ROT_DIST_TYPES if icp or k != "icp"]
+        if goal_args["rot_dist_type"] not in allowed:
+            raise NotImplementedError("%s.rot_dist_type %r is not implemented by the batched rearrange env (%s)" % (where, goal_args["rot_dist_type"], ", ".join(allowed)))
         out["rot_dist_type"] = goal_args["rot_dist_type"]
+    for k in icp_keys:
+        if k in goal_args:
+            out[k] = goal_args[k]
     if goal_args.get("rot_randomize_type", "z_axis") != "z_axis":
         raise NotImplementedError("%s.rot_randomize_type %r is not implemented by the batched rearrange env (z_axis)" % (where, goal_args["rot_randomize_type"]))
     if "randomize_goal_rot" in goal_args:

@@ -16,6 +16,8 @@ from robogym_amd.envs.rearrange.xml import load_ycb_model
 
 
 class BatchedYcbRearrangeEnv(BatchedBlockRearrangeEnv):
+    ICP_ROT_DIST = True      # rot_dist_type "icp" (envs/rearrange/icp.py, csrc/ra_icp_kernel.h): the distance that sees a mesh object's own symmetries
+
     def __init__(self, batch_size: int, device="cuda:0", num_objects: int = 8, **kw):
         model = kw.pop("main_model", None) or load_ycb_model(num_objects)
         super().__init__(batch_size, device=device, num_objects=num_objects, main_model=model, **kw)
@@ -274,10 +276,11 @@ class GroupedYcbRearrangeEnv:
 
 def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants=None, starting_seed: int = 0, apply_wrappers: bool = True, **kw):
     """`YcbRearrangeEnv.build` surface (ycb.py:96) for the batched env; accepts what envs/rearrange/blocks.py `make_env` accepts."""
-    from robogym_amd.envs.rearrange.blocks import _check_supported, group_args
+    from robogym_amd.envs.rearrange.blocks import _check_supported, goal_rot_args, group_args
 
     parameters, constants = dict(parameters or {}), dict(constants or {})
     sp, rc = dict(parameters.get("simulation_params", {})), dict(parameters.get("robot_control_params", {}))
+    rot_args = goal_rot_args(constants.pop("goal_args", None), icp=True)      # constants.goal_args as blocks.make_env takes it, and rot_dist_type icp with its icp_* keys
     if parameters.get("mesh_names") is not None or constants.get("normalize_mesh"):
         raise NotImplementedError("mesh_names / normalize_mesh: the shipped models hold fixed object sets")
     if "max_num_objects" in sp:
@@ -296,6 +299,7 @@ def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants
         if k in sp:
             args[k] = sp[k]
     args.update(group_args(sp, constants))
+    args.update(rot_args)
     args.update(kw)
     object_sets = args.pop("object_sets", None)      # e.g. (0, 1, 2, 3): different object sets across the batch (GroupedYcbRearrangeEnv)
     if object_sets is not None and len(object_sets) > 1:
