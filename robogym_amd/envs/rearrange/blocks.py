@@ -55,6 +55,14 @@ FLAG_FULL_FORWARD = 32
 #: (train: TrainStateGoal, goals/train_state.py; dominos: DominoStateGoal, goals/dominos.py; attached: AttachedBlockStateGoal, goals/attached_block_state.py; fixed:
 #: ObjectFixedStateGoal, goals/object_state_fixed.py)
 GOAL_KINDS = {"object_state": 0, "pickandplace": 1, "stack": 2, "reach": 3, "det-reach": 4, "train": 5, "dominos": 6, "attached": 7, "fixed": 8}
+#: the reach goals: one object, which the goal itself moves; the target is a point above it
+REACH_KINDS = ("reach", "det-reach")
+#: the kinds whose generator sets the goals' yaws itself (set_target_quat inside _sample_next_goal_positions): the arc's / init_quats', whatever the goals had
+OWN_YAW_KINDS = ("dominos", "attached", "fixed")
+#: the kinds built for per-env object counts (max_num_objects)
+COUNTED_KINDS = ("object_state", "pickandplace", "stack", "train")
+#: the kinds the post kernel knows by number (ra_post_args.goal_kind); the others differ in how a goal is made only and are scored as object_state
+POST_KINDS = ("object_state", "pickandplace", "stack", "reach", "det-reach")
 #: AttachedBlockStateGoal's cells (goals/attached_block_state.py:34-49), in steps of one block: a row of 2, a row of 4, a row of 2
 ATTACHED_LATTICE = np.array([[1, 0], [2, 0], [0, 1], [1, 1], [2, 1], [3, 1], [1, 2], [2, 2]], dtype=np.float64)
 #: GoalArgs.rot_dist_type (goals/object_state.py:127-131) -> ra_post_args.rot_dist_type; "icp": one more launch in front of the env kernel (ra_env_icp, csrc/ra_icp_kernel.h)
@@ -117,6 +125,23 @@ def greedy_group_match(obj_pos, goal_pos, groups):
     return match
 
 
+def yawed_half(half, yaw):
+    """`rotate_bounding_box` for boxes turned about z: half extents `half` [N, 3], yaws [.., N] -> the half extents of the turned boxes' bounding boxes [.., N, 3]"""
+    c, s_ = np.abs(np.cos(yaw)), np.abs(np.sin(yaw))
+    return np.stack([c * half[:, 0] + s_ * half[:, 1], s_ * half[:, 0] + c * half[:, 1], np.broadcast_to(half[:, 2], np.shape(yaw))], -1)
+
+
+def yawed_centre(centre, yaw):
+    """bounding-box centres `centre` [N, 3] in the body frames, yaws [.., N] -> the centres from the body origins once the bodies are turned about z [.., N, 3]"""
+    c, s_ = np.cos(yaw), np.sin(yaw)
+    return np.stack([c * centre[:, 0] - s_ * centre[:, 1], s_ * centre[:, 0] + c * centre[:, 1], np.broadcast_to(centre[:, 2], np.shape(yaw))], -1)
+
+
+def area_to_world(p, area_offset, table_pos, table_size):
+    """points [.., 3] measured from the placement area's low corner on the table's bottom face -> world coordinates"""
+    return p + [area_offset[0], area_offset[1], 0.0] - table_size + table_pos
+
+
 def place_targets_with_goal_distance_ratio(random_state, centre, half, table_pos, table_size, area_offset, area_size, object_pos, goal_distance_ratio, goal_distance_min,
                                            max_trials=100, max_trials_per_object=20):
     """`place_targets_with_goal_distance_ratio` over `_place_objects` (common/utils.py:922-994, 623-716), draw for draw, for axis-aligned boxes (`centre`, `half` [N, 3]:
@@ -124,7 +149,7 @@ def place_targets_with_goal_distance_ratio(random_state, centre, half, table_pos
     overlaps no goal placed before it.  Returns ([N, 3] body origins in world coordinates, valid); on failure the last proposals (the reference returns zeros)."""
     N = len(centre)
     table_pos, table_size = np.asarray(table_pos, dtype=np.float64), np.asarray(table_size, dtype=np.float64)
-    shift = np.array([area_offset[0], area_offset[1], 0.0]) - table_size + table_pos
+    shift = area_to_world(np.zeros(3), area_offset, table_pos, table_size)
     width, height = area_size[0], area_size[1]
     last = np.zeros((N, 3))
     for _ in range(max_trials):
@@ -207,8 +232,7 @@ def domino_goal(random_state, obj_half, object_distance, table_pos, table_size, 
         pos = np.zeros((N, 3))
         pos[1:, 0] = (np.cumsum(np.cos(between)) * object_distance)[:N - 1]
         pos[1:, 1] = (np.cumsum(np.sin(between)) * object_distance)[:N - 1]
-        c, s_ = np.abs(np.cos(yaws)), np.abs(np.sin(yaws))
-        half = np.stack([c * obj_half[:, 0] + s_ * obj_half[:, 1], s_ * obj_half[:, 0] + c * obj_half[:, 1], obj_half[:, 2]], -1)      # rotate_bounding_box
+        half = yawed_half(obj_half, yaws)
         pos[:, 2] = half[:, 2]
         max_x, max_y, _ = np.max(pos + half, axis=0)
         min_x, min_y, _ = np.min(pos - half, axis=0)
@@ -231,7 +255,7 @@ def fixed_goal(relative_placements, obj_center, obj_half, table_pos, table_size,
     prop = rel * [area_size[0], area_size[1]]
     z = obj_half[:, 2] + 2 * table_size[2] - obj_center[:, 2]
     placement = np.concatenate([prop, z[:, None]], -1)
-    return placement + [area_offset[0], area_offset[1], 0.0] - table_size + table_pos, True
+    return area_to_world(placement, area_offset, table_pos, table_size), True
 
 
 def attached_goal(random_state, obj_center, obj_half, object_size, table_pos, table_size, area_offset, area_size):
@@ -294,6 +318,10 @@ def _parse_object_groups(object_groups, num_objects):
 PARK_SPACING, PARK_COLUMNS, PARK_HEIGHT = 0.5, 4, 6.0
 #: the dof damping of a parked object (N s / m, N m s / rad; the Euler step treats damping implicitly, inv(M + h B): any value is stable)
 PARK_DAMPING = 10.0
+
+
+def _ptr(tensor):
+    return ctypes.c_void_p(tensor.data_ptr())
 
 
 def parking_poses(table_pos, num_objects):
@@ -365,8 +393,8 @@ class BatchedBlockRearrangeEnv:
         if self.max_num_objects is not None:
             M = self.max_num_objects
             refuse = lambda what: NotImplementedError("max_num_objects (per-env object counts) is not implemented for %s by the batched rearrange env" % what)
-            if goal_kind not in ("object_state", "pickandplace", "stack", "train"):
-                raise refuse("goal_kind %r (object_state, pickandplace, stack, train)" % (goal_kind,))
+            if goal_kind not in COUNTED_KINDS:
+                raise refuse("goal_kind %r (%s)" % (goal_kind, ", ".join(COUNTED_KINDS)))
             if not (object_groups is None or (isinstance(object_groups, str) and object_groups in ("distinct", "single", "sample"))):
                 raise refuse("explicit object_groups counts %r (\"distinct\", \"single\", \"sample\")" % (object_groups,))
             if _solver_mode_name(tcp_solver_mode) == "mocap" and _control_mode_name(control_mode) != "joint":
@@ -386,21 +414,21 @@ class BatchedBlockRearrangeEnv:
         if rot_dist_type not in ROT_DIST_TYPES:
             raise ValueError("rot_dist_type %r is not one of %s" % (rot_dist_type, ", ".join(ROT_DIST_TYPES)))
         self.rot_dist_type, self.randomize_goal_rot, self.domino_distance_mul = rot_dist_type, bool(randomize_goal_rot), float(domino_distance_mul)
-        if self.goal_kind == 6 and not (float(object_size) > 0 and self.domino_distance_mul > 0):
+        if goal_kind == "dominos" and not (float(object_size) > 0 and self.domino_distance_mul > 0):
             raise ValueError("goal_kind dominos needs object_size > 0 and domino_distance_mul > 0 (got %r, %r)" % (object_size, domino_distance_mul))
-        if self.goal_kind == 7 and not (self.N == 8 and float(object_size) > 0):
+        if goal_kind == "attached" and not (self.N == 8 and float(object_size) > 0):
             raise ValueError("goal_kind attached needs num_objects == 8 and object_size > 0 (got %r, %r)" % (num_objects, object_size))
-        if (relative_placements is not None or init_quats is not None) and self.goal_kind != 8:
+        if (relative_placements is not None or init_quats is not None) and goal_kind != "fixed":
             raise ValueError("relative_placements / init_quats belong to goal_kind \"fixed\" (ObjectFixedStateGoal), not to %r" % (goal_kind,))
         self.relative_placements, self.init_yaw = None, np.zeros(self.N)
-        if self.goal_kind == 8:
+        if goal_kind == "fixed":
             if relative_placements is None:
                 raise ValueError("goal_kind fixed needs relative_placements [N, 2]")
             self.relative_placements = np.array(relative_placements, dtype=np.float64)
             if self.relative_placements.shape != (self.N, 2) or not np.all((self.relative_placements >= 0.0) & (self.relative_placements <= 1.0)):
                 raise ValueError("relative_placements must be [%d, 2] with every entry in [0, 1], got %r" % (self.N, np.asarray(relative_placements).tolist()))
             self.init_yaw = z_rotation_yaws(init_quats, self.N)
-        self.reach = self.goal_kind in (3, 4)
+        self.reach = goal_kind in REACH_KINDS
         if rot_dist_type == "icp" and not self.ICP_ROT_DIST:
             raise NotImplementedError("rot_dist_type \"icp\" is built for the mesh worlds (envs/rearrange/ycb.py BatchedYcbRearrangeEnv), not for the block envs "
                                       "(full, mod90, mod180: a box's symmetries are what mod90 / mod180 state exactly)")
@@ -431,7 +459,7 @@ class BatchedBlockRearrangeEnv:
         self.max_position_change = float(max_position_change)
         if model is not None and main_model is not None:
             raise ValueError("model and main_model name the same thing: pass one")
-        if self.goal_kind == 6 and model is None and main_model is None:
+        if goal_kind == "dominos" and model is None and main_model is None:
             raise ValueError("goal_kind \"dominos\" is DominoStateGoal, the goal generator of the domino world only (goals/dominos.py:13-17): pass model=load_dominos_model(...), "
                              "as envs/rearrange/dominos.py make_env does")
         main_model = model if model is not None else main_model
@@ -459,8 +487,7 @@ class BatchedBlockRearrangeEnv:
         self.used_table_portion = used_table_portion
         self._rng = np.random.RandomState(starting_seed)
         self.host_placement_failed = 0      # host recipe: goal placements that ran out of restarts (the device recipe counts per env in `placement_failed`)
-        A, As = main.arrays, (None if solver is None else solver.arrays)
-        jn, sj = main.names["joint"], (None if solver is None else solver.names["joint"])
+        A, jn = main.arrays, main.names["joint"]
         self.arm_q = [int(A["jnt_qposadr"][jn.index("robot0:J%d" % k)]) for k in range(1, 7)]
         self.obj_q = [int(A["jnt_qposadr"][jn.index("object%d:joint" % i)]) for i in range(self.N)]
         self.obj_v = [int(A["jnt_dofadr"][jn.index("object%d:joint" % i)]) for i in range(self.N)]
@@ -468,45 +495,12 @@ class BatchedBlockRearrangeEnv:
         self.grip_act = main.names["actuator"].index("robot0:r_gripper_finger_joint")
         self.nq, self.nu = self.sim.nq, self.sim.nu
         self.obs_dim = 36 * self.N + 23 + 2 * self.nq
-        gn = main.names["geom"]
-        tb, tg = main.name2id("body", "table"), gn.index("table")
+        tb, tg = main.name2id("body", "table"), main.names["geom"].index("table")
         self.table_pos, self.table_size = A["body_pos"][tb].copy(), A["geom_size"][tg].copy()
         self.table_height = float(self.table_pos[2] + self.table_size[2])
         bb = object_bounding_boxes(main, self.N)                        # per object: centre and half extents of its vertices in the body frame
         self.obj_center, self.obj_half = bb[:, :3].copy(), bb[:, 3:].copy()
-        # ---- TCP hook arguments
-        t = self.tcp = _native.RbTcpArgs()
-        if self.joint_control:
-            # JointControlledArm drives ctrl[:6] from the six arm joints (joint_controlled_arm.py:186-190), MujocoRobotiqGripper its own actuator; relative actions:
-            # arm joint k around its position, +- min(ctrl range / 2, max_position_change); the gripper around its control, +- ctrl range / 2
-            assert self.grip_act == 6 and self.nu == 7 and list(np.diff(self.arm_q)) == [1] * 5, "joint control: ctrl[:6] = the arm's joints, ctrl[6] = the gripper"
-            assert [int(np.ravel(A["actuator_trnid"][u])[0]) for u in range(6)] == [jn.index("robot0:J%d" % k) for k in range(1, 7)], main.names["actuator"]
-            P = np.zeros((7, 6), dtype=np.float32); P[:6] = np.eye(6)
-            self.sim.set_action_map(self.arm_q[0], P, relative_action=True, max_position_change=float(max_position_change), ctrl_centre_mask=1 << self.grip_act)
-            self.solver_arm_q, self.solver_grip_q, self.solver_grip_act = [], -1, -1
-        elif self.ideal_arm:
-            # the hook on the env's own world (rb_tcp_args.self_world): TCP pose + denormalised action -> mocap target, gripper target into this world's ctrl, then its mj_steps
-            assert self.nu == 1 and self.grip_act == 0 and int(A["body_mocapid"][main.name2id("body", "robot0:mocap")]) == 0
-            for k in range(6):
-                t.arm_qposadr[k] = t.main_arm_qposadr[k] = self.arm_q[k]
-            t.main_gripper_actuator = self.grip_act; t.tcp_body = main.name2id("body", "robot0:gripper_tcp"); t.wrist_joint = jn.index("robot0:J6")
-            t.reset_controller_error = 0; t.self_world = 1; t.wrist_only = 1 if self.wrist_only else 0
-            t.max_position_change = max_position_change; t.speed_roll = SPEED_ROLL; t.speed_pitch = SPEED_PITCH; t.joint_drift_threshold = JOINT_DRIFT_THRESHOLD
-            t.gripper_ctrl_lo, t.gripper_ctrl_hi = float(A["actuator_ctrlrange"][self.grip_act, 0]), float(A["actuator_ctrlrange"][self.grip_act, 1])
-            self.solver_arm_q, self.solver_grip_q, self.solver_grip_act = [], -1, -1
-            self._tcp_body, self._gripper_base_body = int(t.tcp_body), main.name2id("body", "robot0:gripper_base")
-        else:
-            for k in range(6):
-                t.arm_qposadr[k] = int(As["jnt_qposadr"][sj.index("robot0:J%d" % (k + 1))]); t.main_arm_qposadr[k] = self.arm_q[k]
-            t.main_gripper_actuator = self.grip_act; t.tcp_body = solver.name2id("body", "robot0:gripper_tcp"); t.wrist_joint = sj.index("robot0:J6")
-            t.reset_controller_error = 1 if arm_reset_controller_error else 0
-            t.wrist_only = 1 if self.wrist_only else 0
-            t.max_position_change = max_position_change; t.speed_roll = SPEED_ROLL; t.speed_pitch = SPEED_PITCH; t.joint_drift_threshold = JOINT_DRIFT_THRESHOLD
-            t.gripper_ctrl_lo, t.gripper_ctrl_hi = float(A["actuator_ctrlrange"][self.grip_act, 0]), float(A["actuator_ctrlrange"][self.grip_act, 1])
-            self.solver_arm_q = [int(t.arm_qposadr[k]) for k in range(6)]
-            self.solver_grip_q = int(As["jnt_qposadr"][sj.index("robot0:r_gripper_RJ0_outer")])
-            self.solver_grip_act = solver.names["actuator"].index("robot0:r_gripper_finger_joint")
-        # ---- env-level state (device) and the post kernel's arguments
+        # ---- env-level state (device)
         dev, B, N = self.device, self.B, self.N
         z = lambda *shape, dt=torch.float32: torch.zeros(*shape, dtype=dt, device=dev)
         self.packed = z(B, self.obs_dim + 4)
@@ -519,17 +513,115 @@ class BatchedBlockRearrangeEnv:
         self.done, self.goal_reset, self.trial_success, self.sub_goal_ok, self.env_crash, self.objects_off_table = (z(B, dt=torch.bool) for _ in range(6))
         self.info_ssl = z(B, dt=torch.int32)
         self.goal[:, :, 3] = 1.0
-        st = dict(success_threshold or {"obj_pos": 0.04, "obj_rot": 0.2})
-        pen = dict(penalty or dict(table_collision=0.0, objects_off_table=1.0, wrist_collision=0.0))
+        self.obj_group = None
+        if self.group_mode != "distinct":      # ("sample": all distinct until the first reset draws the rows)
+            ids = group_ids(self.group_counts if self.group_mode == "fixed" else [1] * N)
+            self.obj_group = torch.tensor(np.tile(ids, (B, 1)), dtype=torch.int32, device=dev).contiguous()
+        # per-env object counts (max_num_objects): the latched counts, the row a curriculum writes, where an unused object is parked
+        self.num_active = self.num_objects_next = self.park_pose = None
+        if self.max_num_objects is not None:
+            self.num_active = torch.full((B,), self.num_objects_initial, dtype=torch.int32, device=dev)
+            self.num_objects_next = self.num_active.clone()
+            self.park_pose = parking_poses(self.table_pos, N)
+            self._obj_bodies = torch.tensor([main.name2id("body", "object%d" % i) for i in range(N)], device=dev, dtype=torch.long)
+            self._slot = torch.arange(N, device=dev, dtype=torch.int32)
+        # pipelined resets: an env whose episode ended runs the reset recipe INSIDE the following step calls (the stepper's launches take everybody
+        # along; a synchronous reset of a few envs costs ~210 launch pairs at the latency of a full batch).  The recipe's bookkeeping is host numpy (one
+        # readback of the flags per step -- a step is 70 ms of GPU work), its physics goes through the same three launches as the live envs': `hold` /
+        # `scripted` feed the recipe's actions to the solver world's launch, `frozen` keeps the env kernel from scoring those envs.
+        self.pipelined = bool(pipelined_reset)
+        self._stage, self._left = np.zeros(B, dtype=np.int8), np.zeros(B, dtype=np.int32)      # 0 live, 1 stabilise, 2 random action, 3 settle
+        self._yaw = np.zeros((B, N))
+        self.ended_rows = np.zeros(0, dtype=np.int64)          # rows whose episode ended on the last step (pipelined resets)
+        self.hold, self.scripted, self.frozen, self.solver_active = z(B, dt=torch.int32), z(B, AD), z(B, dt=torch.uint8), torch.ones(B, dtype=torch.int32, device=dev)
+        self.hold_ctrl = z(B, dt=torch.int32)      # joint control, pipelined resets: envs whose objects stabilise keep their stored controls (no action reaches the robot)
+        self.resetting, self.episode_started = z(B, dt=torch.bool), z(B, dt=torch.bool)
+        self.nticks = torch.full((B,), 2, dtype=torch.int32, device=dev)       # state-less forwards (controller ticks) per env of the main world's launch
+        self.wrapped = bool(wrappers)
+        # ---- the arguments of the TCP hook, the env kernel and, for rot_dist_type icp, the launch in front of it
+        self._fill_tcp_args(max_position_change, arm_reset_controller_error)
+        self._fill_post_args(dict(success_threshold or {"obj_pos": 0.04, "obj_rot": 0.2}), dict(penalty or dict(table_collision=0.0, objects_off_table=1.0, wrist_collision=0.0)),
+                             goal_reward_per_object, success_reward, max_timesteps_per_goal_per_obj, successes_needed, use_goal_distance_reward, reward_clip)
+        self.icp = self.icp_rel = self.icp_clouds = None
+        if rot_dist_type == "icp":
+            self._fill_icp_args()
+        self.action_shape = (self.B, self.action_dim)
+        self._zero_action = z(B, AD)
+        # ---- per-env model parameters: the reference's simulation randomizers (applied after _reset, robot_env.py:779-783) and stabilize_objects' damping change
+        self.stabilize_object_damping = float(stabilize_object_damping)
+        self.obj_dofs = torch.tensor([d for v in self.obj_v for d in range(v, v + 6)], device=dev, dtype=torch.long)
+        self.randomizers = build_simulation_randomizers(main, self.randomizer_params) if self.per_env_parameters else []
+        self._rand_gen = torch.Generator(device=dev); self._rand_gen.manual_seed(int(starting_seed) + 90001)
+        if self.per_env_parameters:
+            self._param_defaults = {k: self.sim.params[k][0].clone() for k in self.sim.params.keys()}
+            self._param_block_default = self.sim.params.block[0].clone()
+        # ---- RearrangeEnv.apply_wrappers (common/base.py:986-996): SmoothActionWrapper(alpha = 0.3) -> ClipRewardWrapper -> DiscretizeActionWrapper, all inside
+        # the launches: the solver world's launch maps bin indices to actions and smooths them (rb_tcp_args), the post kernel clips the reward
+        self.n_action_bins = int(n_action_bins)
+        self.ema_value, self.ema_t, self.action_ema = z(B, AD), z(B, dt=torch.int32), z(B, AD)
+        self.bins = torch.tensor(np.tile(action_bin_array(-1.0, 1.0, self.n_action_bins, action_spacing), (AD, 1)).astype(np.float32), device=dev).contiguous()   # over Box(-1, 1)
+        tw = self.tcp_wrapped = _native.RbTcpArgs()
+        ctypes.memmove(ctypes.byref(tw), ctypes.byref(self.tcp), ctypes.sizeof(tw))
+        tw.bins, tw.nbins = self.bins.data_ptr(), self.n_action_bins
+        self.ema_alpha = tw.ema_alpha = float(np.power(smooth_alpha, float(np.asarray(A["opt_timestep"]).reshape(-1)[0]) * n_substeps / 0.08))       # SmoothActionWrapper.reset (wrappers/util.py:203-211)
+        tw.ema_value, tw.ema_t, tw.action_out = self.ema_value.data_ptr(), self.ema_t.data_ptr(), self.action_ema.data_ptr()
+        # ---- the device recipe: its state and the recipe kernel's arguments
+        self.device_reset = bool(device_reset)
+        if self.device_reset:
+            if not self.pipelined:
+                raise ValueError("device_reset needs pipelined_reset=True (the synchronous reset() keeps its host recipe)")
+            self.stage, self.left, self.yaw, self.placement_failed = z(B, dt=torch.int32), z(B, dt=torch.int32), z(B, N), z(B, dt=torch.int32)
+            self.reobserve, self.ended, self.stabilised = torch.full((B,), 2, dtype=torch.uint8, device=dev), z(B, dt=torch.bool), z(B, dt=torch.bool)
+            self._fill_recipe_args(starting_seed)
+
+    def _fill_tcp_args(self, max_position_change, arm_reset_controller_error):
+        """`self.tcp`, rb_tcp_args of the TCP hook: on the solver world, or (`ideal_arm`) on the env's own world (rb_tcp_args.self_world: TCP pose + denormalised action ->
+        mocap target, gripper target into this world's ctrl, then its mj_steps).  Joint control has no hook: the main world's launch maps the action itself."""
+        main, solver = self.model, self.solver_model
+        A, jn = main.arrays, main.names["joint"]
+        t = self.tcp = _native.RbTcpArgs()
+        if self.pipelined:
+            t.hold, t.scripted = self.hold.data_ptr(), self.scripted.data_ptr()
+        self.solver_arm_q, self.solver_grip_q, self.solver_grip_act = [], -1, -1
+        if self.joint_control:
+            # JointControlledArm drives ctrl[:6] from the six arm joints (joint_controlled_arm.py:186-190), MujocoRobotiqGripper its own actuator; relative actions:
+            # arm joint k around its position, +- min(ctrl range / 2, max_position_change); the gripper around its control, +- ctrl range / 2
+            assert self.grip_act == 6 and self.nu == 7 and list(np.diff(self.arm_q)) == [1] * 5, "joint control: ctrl[:6] = the arm's joints, ctrl[6] = the gripper"
+            assert [int(np.ravel(A["actuator_trnid"][u])[0]) for u in range(6)] == [jn.index("robot0:J%d" % k) for k in range(1, 7)], main.names["actuator"]
+            P = np.zeros((7, 6), dtype=np.float32); P[:6] = np.eye(6)
+            self.sim.set_action_map(self.arm_q[0], P, relative_action=True, max_position_change=float(max_position_change), ctrl_centre_mask=1 << self.grip_act)
+            return
+        world = main if self.ideal_arm else solver      # the world the hook runs on
+        wj = world.names["joint"]
+        for k in range(6):
+            t.arm_qposadr[k] = int(world.arrays["jnt_qposadr"][wj.index("robot0:J%d" % (k + 1))]); t.main_arm_qposadr[k] = self.arm_q[k]
+        t.main_gripper_actuator = self.grip_act; t.tcp_body = world.name2id("body", "robot0:gripper_tcp"); t.wrist_joint = wj.index("robot0:J6")
+        t.wrist_only = 1 if self.wrist_only else 0
+        t.max_position_change = max_position_change; t.speed_roll = SPEED_ROLL; t.speed_pitch = SPEED_PITCH; t.joint_drift_threshold = JOINT_DRIFT_THRESHOLD
+        t.gripper_ctrl_lo, t.gripper_ctrl_hi = float(A["actuator_ctrlrange"][self.grip_act, 0]), float(A["actuator_ctrlrange"][self.grip_act, 1])
+        if self.ideal_arm:
+            assert self.nu == 1 and self.grip_act == 0 and int(A["body_mocapid"][main.name2id("body", "robot0:mocap")]) == 0
+            t.reset_controller_error = 0; t.self_world = 1
+            self._tcp_body, self._gripper_base_body = int(t.tcp_body), main.name2id("body", "robot0:gripper_base")
+        else:
+            t.reset_controller_error = 1 if arm_reset_controller_error else 0
+            self.solver_arm_q = [int(t.arm_qposadr[k]) for k in range(6)]
+            self.solver_grip_q = int(solver.arrays["jnt_qposadr"][wj.index("robot0:r_gripper_RJ0_outer")])
+            self.solver_grip_act = solver.names["actuator"].index("robot0:r_gripper_finger_joint")
+
+    def _fill_post_args(self, st, pen, goal_reward_per_object, success_reward, max_timesteps_per_goal_per_obj, successes_needed, use_goal_distance_reward, reward_clip):
+        """`self.post`, ra_post_args of the env kernel (csrc/ra_env_kernel.h): the env-level rows, where the robot, the objects and the table are in the main world, the
+        thresholds `st`, the rewards and the penalties `pen`"""
+        main, N = self.model, self.N
+        A, jn, gn, sn = main.arrays, main.names["joint"], main.names["geom"], main.names["sensor"]
         a = self.post = _native.RaPostArgs()
-        P = lambda x: ctypes.c_void_p(x.data_ptr())
-        a.obs, a.obs_dim, a.num_objects = P(self.packed), self.obs_dim, N
+        a.obs, a.obs_dim, a.num_objects = _ptr(self.packed), self.obs_dim, N
         for name, ten in (("t", self.t), ("steps", self.steps), ("steps_since_last_goal", self.ssl), ("successes_so_far", self.successes), ("consecutive", self.consecutive),
                           ("prev_nsucc", self.prev_nsucc), ("prev_valid", self.prev_valid), ("goal", self.goal), ("goal_rot", self.goal_rot), ("qpos_goal", self.qpos_goal),
                           ("static_obs", self.static_obs), ("reward", self.reward), ("goal_dist", self.goal_dist), ("done", self.done), ("goal_reset", self.goal_reset),
                           ("trial_success", self.trial_success), ("sub_goal_ok", self.sub_goal_ok), ("env_crash", self.env_crash), ("objects_off_table", self.objects_off_table),
                           ("info_ssl", self.info_ssl)):
-            setattr(a, name, P(ten))
+            setattr(a, name, _ptr(ten))
         for i in range(N):
             a.obj_body[i] = main.name2id("body", "object%d" % i)
         a.tcp_body = main.name2id("body", "robot0:gripper_tcp")
@@ -538,7 +630,6 @@ class BatchedBlockRearrangeEnv:
         a.grip_qposadr, a.grip_dofadr, a.grip_act = self.grip_q, int(A["jnt_dofadr"][jn.index("robot0:r_gripper_RJ0_outer")]), self.grip_act
         a.finger_geom[0], a.finger_geom[1] = gn.index("robot0:left_contact_v"), gn.index("robot0:right_contact_v")
         a.table_plane_geom = gn.index("table_collision_plane")
-        sn = main.names["sensor"]
         a.force_adr, a.torque_adr = int(A["sensor_adr"][sn.index("toolhead_force")]), int(A["sensor_adr"][sn.index("toolhead_torque")])
         mask = 0
         for bname in ("robot0:gripper_base", "left_gripper", "left_inner_follower", "left_outer_driver", "right_gripper", "right_inner_follower", "right_outer_driver"):
@@ -557,140 +648,99 @@ class BatchedBlockRearrangeEnv:
         a.safety_stop_force = 150.0                                      # robot/ur16e/arm_interface.py:46
         a.max_timesteps_per_goal, a.successes_needed, a.use_goal_distance_reward = max_timesteps_per_goal_per_obj * N, successes_needed, int(use_goal_distance_reward)
         a.solver_grip_qposadr, a.solver_grip_act = self.solver_grip_q, self.solver_grip_act
-        a.goal_kind, a.grip_site, a.goal_dist_extra = (0 if self.goal_kind >= 5 else self.goal_kind), main.names["site"].index("robot0:grip"), P(self.goal_dist_extra)
-        a.rot_dist_type = ROT_DIST_TYPES[rot_dist_type]
+        a.goal_kind = self.goal_kind if self.goal_kind_name in POST_KINDS else GOAL_KINDS["object_state"]
+        a.grip_site, a.goal_dist_extra = main.names["site"].index("robot0:grip"), _ptr(self.goal_dist_extra)
+        self._grip_site = int(a.grip_site)
+        a.rot_dist_type = ROT_DIST_TYPES[self.rot_dist_type]
         if a.rot_dist_type:      # the tables euler_angle_difference_single_pair walks, in the reference's order (constant data: built once on the host)
             from robogym_amd.utils.rotation import parallel_quat_table
-            self.parallel_quats = {m: torch.tensor(parallel_quat_table(m), dtype=torch.float32, device=dev).contiguous() for m in ("mod90", "mod180")}
-            a.parallel_quats, a.parallel_quats_180 = P(self.parallel_quats["mod90"]), P(self.parallel_quats["mod180"])
-        self._grip_site = int(a.grip_site)
-        self.obj_group = None
-        if self.group_mode != "distinct":      # ("sample": all distinct until the first reset draws the rows)
-            ids = group_ids(self.group_counts if self.group_mode == "fixed" else [1] * N)
-            self.obj_group = torch.tensor(np.tile(ids, (B, 1)), dtype=torch.int32, device=dev).contiguous()
-            a.obj_group = P(self.obj_group)
-        # ---- per-env object counts (max_num_objects): the latched counts, the row a curriculum writes, where an unused object is parked
-        self.num_active = self.num_objects_next = self.park_pose = None
+            self.parallel_quats = {m: torch.tensor(parallel_quat_table(m), dtype=torch.float32, device=self.device).contiguous() for m in ("mod90", "mod180")}
+            a.parallel_quats, a.parallel_quats_180 = _ptr(self.parallel_quats["mod90"]), _ptr(self.parallel_quats["mod180"])
+        if self.obj_group is not None:
+            a.obj_group = _ptr(self.obj_group)
         if self.max_num_objects is not None:
-            self.num_active = torch.full((B,), self.num_objects_initial, dtype=torch.int32, device=dev)
-            self.num_objects_next = self.num_active.clone()
-            self.park_pose = parking_poses(self.table_pos, N)
-            self._park_pose_dev = torch.tensor(self.park_pose.astype(np.float32), device=dev)
-            self._obj_bodies = torch.tensor([int(a.obj_body[i]) for i in range(N)], device=dev, dtype=torch.long)
-            self._slot = torch.arange(N, device=dev, dtype=torch.int32)
-            a.num_active, a.max_timesteps_per_goal_per_obj = P(self.num_active), int(max_timesteps_per_goal_per_obj)
-        # ---- rot_dist_type icp: the clouds (constant, per object), the angles ra_env_icp leaves for the env kernel, its arguments
-        self.icp = self.icp_rel = self.icp_clouds = None
-        if rot_dist_type == "icp":
-            from robogym_amd.envs.rearrange.icp import object_point_clouds
-            src, src_num, tgt, tgt_adr, tgt_num = object_point_clouds(main, N, self.icp_error_threshold, self.icp_max_num_vertices)
-            self.icp_clouds = tuple(torch.as_tensor(x, device=dev).contiguous() for x in (src, src_num, tgt, tgt_adr, tgt_num))
-            self.icp_rel = z(B, N, 3)
-            c = self.icp = _native.RaIcpArgs()
-            c.icp_rel, c.goal, c.num_objects = P(self.icp_rel), P(self.goal), N
-            for i in range(N):
-                c.obj_body[i] = a.obj_body[i]
-            c.src, c.src_stride, c.src_num = P(self.icp_clouds[0]), int(src.shape[1]), P(self.icp_clouds[1])
-            c.tgt, c.tgt_total, c.tgt_adr, c.tgt_num = P(self.icp_clouds[2]), int(tgt.shape[0]), P(self.icp_clouds[3]), P(self.icp_clouds[4])
-            c.error_threshold = self.icp_error_threshold
-            c.obj_group, c.num_active = a.obj_group, a.num_active
-            a.icp_rel = P(self.icp_rel)
-        self.action_shape = (self.B, self.action_dim)
-        self._zero_action = z(B, AD)
-        # ---- per-env model parameters: the reference's simulation randomizers (applied after _reset, robot_env.py:779-783) and stabilize_objects' damping change
-        self.stabilize_object_damping = float(stabilize_object_damping)
-        self.obj_dofs = torch.tensor([d for v in self.obj_v for d in range(v, v + 6)], device=dev, dtype=torch.long)
-        self.randomizers = build_simulation_randomizers(main, self.randomizer_params) if self.per_env_parameters else []
-        self._rand_gen = torch.Generator(device=dev); self._rand_gen.manual_seed(int(starting_seed) + 90001)
-        if self.per_env_parameters:
-            self._param_defaults = {k: self.sim.params[k][0].clone() for k in self.sim.params.keys()}
-            self._param_block_default = self.sim.params.block[0].clone()
-        # ---- RearrangeEnv.apply_wrappers (common/base.py:986-996): SmoothActionWrapper(alpha = 0.3) -> ClipRewardWrapper -> DiscretizeActionWrapper, all inside
-        # the launches: the solver world's launch maps bin indices to actions and smooths them (rb_tcp_args), the post kernel clips the reward
-        self.wrapped = bool(wrappers)
-        self.n_action_bins = int(n_action_bins)
-        self.ema_value, self.ema_t, self.action_ema = z(B, AD), z(B, dt=torch.int32), z(B, AD)
-        self.bins = torch.tensor(np.tile(action_bin_array(-1.0, 1.0, self.n_action_bins, action_spacing), (AD, 1)).astype(np.float32), device=dev).contiguous()   # over Box(-1, 1)
-        tw = self.tcp_wrapped = _native.RbTcpArgs()
-        ctypes.memmove(ctypes.byref(tw), ctypes.byref(t), ctypes.sizeof(t))
-        tw.bins, tw.nbins = self.bins.data_ptr(), self.n_action_bins
-        self.ema_alpha = tw.ema_alpha = float(np.power(smooth_alpha, float(np.asarray(A["opt_timestep"]).reshape(-1)[0]) * n_substeps / 0.08))       # SmoothActionWrapper.reset (wrappers/util.py:203-211)
-        tw.ema_value, tw.ema_t, tw.action_out = self.ema_value.data_ptr(), self.ema_t.data_ptr(), self.action_ema.data_ptr()
+            a.num_active, a.max_timesteps_per_goal_per_obj = _ptr(self.num_active), int(max_timesteps_per_goal_per_obj)
         if self.wrapped:
             a.reward_clip = float(reward_clip)
-        # ---- pipelined resets: an env whose episode ended runs the reset recipe INSIDE the following step calls (the stepper's launches take everybody
-        # along; a synchronous reset of a few envs costs ~210 launch pairs at the latency of a full batch).  The recipe's bookkeeping is host numpy (one
-        # readback of the flags per step -- a step is 70 ms of GPU work), its physics goes through the same three launches as the live envs': `hold` /
-        # `scripted` feed the recipe's actions to the solver world's launch, `frozen` keeps the env kernel from scoring those envs.
-        self.pipelined = bool(pipelined_reset)
-        self._stage, self._left = np.zeros(B, dtype=np.int8), np.zeros(B, dtype=np.int32)      # 0 live, 1 stabilise, 2 random action, 3 settle
-        self._yaw = np.zeros((B, N))
-        self.ended_rows = np.zeros(0, dtype=np.int64)          # rows whose episode ended on the last step (pipelined resets)
-        self.hold, self.scripted, self.frozen, self.solver_active = z(B, dt=torch.int32), z(B, AD), z(B, dt=torch.uint8), torch.ones(B, dtype=torch.int32, device=dev)
-        self.hold_ctrl = z(B, dt=torch.int32)      # joint control, pipelined resets: envs whose objects stabilise keep their stored controls (no action reaches the robot)
-        self.resetting, self.episode_started = z(B, dt=torch.bool), z(B, dt=torch.bool)
-        self.nticks = torch.full((B,), 2, dtype=torch.int32, device=dev)       # state-less forwards (controller ticks) per env of the main world's launch
         if self.pipelined:
-            for args_ in (t, tw):
-                args_.hold, args_.scripted = self.hold.data_ptr(), self.scripted.data_ptr()
             a.frozen = self.frozen.data_ptr()
-        self.device_reset = bool(device_reset)
-        if self.device_reset:
-            if not self.pipelined:
-                raise ValueError("device_reset needs pipelined_reset=True (the synchronous reset() keeps its host recipe)")
-            self.stage, self.left, self.yaw, self.placement_failed = z(B, dt=torch.int32), z(B, dt=torch.int32), z(B, N), z(B, dt=torch.int32)
-            self.reobserve, self.ended, self.stabilised = torch.full((B,), 2, dtype=torch.uint8, device=dev), z(B, dt=torch.bool), z(B, dt=torch.bool)
-            r = self.recipe = _native.RaRecipeArgs()
-            r.num_objects, r.action_dim = N, AD
-            for name, ten in (("stage", self.stage), ("left", self.left), ("yaw", self.yaw), ("done", self.done), ("goal_reset", self.goal_reset), ("hold", self.hold),
-                              ("hold_ctrl", self.hold_ctrl), ("solver_active", self.solver_active), ("nticks", self.nticks), ("scripted", self.scripted), ("frozen", self.frozen),
-                              ("resetting", self.resetting), ("episode_started", self.episode_started), ("reobserve", self.reobserve), ("ended", self.ended),
-                              ("stabilised", self.stabilised), ("placement_failed", self.placement_failed), ("t", self.t), ("steps", self.steps), ("steps_since_last_goal", self.ssl),
-                              ("successes_so_far", self.successes), ("consecutive", self.consecutive), ("prev_valid", self.prev_valid), ("ema_t", self.ema_t),
-                              ("ema_value", self.ema_value), ("action_ema", self.action_ema), ("goal", self.goal), ("goal_rot", self.goal_rot), ("qpos_goal", self.qpos_goal),
-                              ("static_obs", self.static_obs)):
-                setattr(r, name, P(ten))
-            for i in range(N):
-                r.obj_qposadr[i] = self.obj_q[i]
-                for k in range(3):
-                    r.obj_center[i][k], r.obj_half[i][k] = float(self.obj_center[i, k]), float(self.obj_half[i, k])
-            for k in range(6):
-                r.arm_qposadr[k], r.arm_start[k] = self.arm_q[k], float(TABLETOP_EXPERIMENT_INITIAL_POS[k])
-                r.solver_arm_qposadr[k] = self.solver_arm_q[k] if self.solver_arm_q else 0
-            (off_x, off_y, _), (width, height, _) = self.placement_area()
-            r.area_offset[0], r.area_offset[1], r.area_size[0], r.area_size[1] = float(off_x), float(off_y), float(width), float(height)
+
+    def _fill_icp_args(self):
+        """rot_dist_type icp: the clouds (constant, per object), the angles ra_env_icp leaves for the env kernel, and `self.icp`, its arguments"""
+        from robogym_amd.envs.rearrange.icp import object_point_clouds
+        a, N = self.post, self.N
+        src, src_num, tgt, tgt_adr, tgt_num = object_point_clouds(self.model, N, self.icp_error_threshold, self.icp_max_num_vertices)
+        self.icp_clouds = tuple(torch.as_tensor(x, device=self.device).contiguous() for x in (src, src_num, tgt, tgt_adr, tgt_num))
+        self.icp_rel = torch.zeros(self.B, N, 3, device=self.device)
+        c = self.icp = _native.RaIcpArgs()
+        c.icp_rel, c.goal, c.num_objects = _ptr(self.icp_rel), _ptr(self.goal), N
+        for i in range(N):
+            c.obj_body[i] = a.obj_body[i]
+        c.src, c.src_stride, c.src_num = _ptr(self.icp_clouds[0]), int(src.shape[1]), _ptr(self.icp_clouds[1])
+        c.tgt, c.tgt_total, c.tgt_adr, c.tgt_num = _ptr(self.icp_clouds[2]), int(tgt.shape[0]), _ptr(self.icp_clouds[3]), _ptr(self.icp_clouds[4])
+        c.error_threshold = self.icp_error_threshold
+        c.obj_group, c.num_active = a.obj_group, a.num_active
+        a.icp_rel = _ptr(self.icp_rel)
+
+    def _fill_recipe_args(self, starting_seed):
+        """`self.recipe`, ra_recipe_args of the recipe kernel (ra_env_recipe_step, include/rgstep.h): the stage machine's rows, the placement geometry, the goal kind's numbers"""
+        N = self.N
+        r = self.recipe = _native.RaRecipeArgs()
+        r.num_objects, r.action_dim = N, self.launch_action_dim
+        for name, ten in (("stage", self.stage), ("left", self.left), ("yaw", self.yaw), ("done", self.done), ("goal_reset", self.goal_reset), ("hold", self.hold),
+                          ("hold_ctrl", self.hold_ctrl), ("solver_active", self.solver_active), ("nticks", self.nticks), ("scripted", self.scripted), ("frozen", self.frozen),
+                          ("resetting", self.resetting), ("episode_started", self.episode_started), ("reobserve", self.reobserve), ("ended", self.ended),
+                          ("stabilised", self.stabilised), ("placement_failed", self.placement_failed), ("t", self.t), ("steps", self.steps), ("steps_since_last_goal", self.ssl),
+                          ("successes_so_far", self.successes), ("consecutive", self.consecutive), ("prev_valid", self.prev_valid), ("ema_t", self.ema_t),
+                          ("ema_value", self.ema_value), ("action_ema", self.action_ema), ("goal", self.goal), ("goal_rot", self.goal_rot), ("qpos_goal", self.qpos_goal),
+                          ("static_obs", self.static_obs)):
+            setattr(r, name, _ptr(ten))
+        for i in range(N):
+            r.obj_qposadr[i] = self.obj_q[i]
             for k in range(3):
-                r.table_pos[k], r.table_size[k] = float(self.table_pos[k]), float(self.table_size[k])
-            r.stabilize_steps, r.n_random_initial_steps, r.settle_steps = int(stabilize_steps), int(n_random_initial_steps), int(settle_steps)
-            r.seed, r.step = (int(starting_seed) * 2654435761 + 40503) & 0xFFFFFFFF, 0
-            r.goal_kind, r.height_range[0], r.height_range[1], r.object_size = self.goal_kind, self.height_range[0], self.height_range[1], self.object_size
-            r.fixed_order, r.target_height, r.goal_index = int(self.fixed_order), self.target_height, P(self.goal_index)
-            for j in range(2):
-                for k in range(3):
-                    r.det_points[j][k] = float(DET_REACH_POINTS[j, k])
-            r.goal_distance_ratio, r.goal_distance_min, r.pickup_proba, r.stacking_proba = P(self.goal_distance_ratio), self.goal_distance_min, self.pickup_proba, self.stacking_proba
-            if self.obj_group is not None:
-                r.obj_group, r.group_mode = P(self.obj_group), int(self.group_mode == "sample")
-                r.sample_lam[0], r.sample_lam[1] = self.sample_lam
-            r.randomize_goal_rot, r.domino_distance_mul = int(self.randomize_goal_rot), self.domino_distance_mul
-            if self.goal_kind == 8:
-                for i in range(N):
-                    r.fixed_xy[i][0], r.fixed_xy[i][1], r.fixed_yaw[i] = float(self.relative_placements[i, 0]), float(self.relative_placements[i, 1]), float(self.init_yaw[i])
-            if self.max_num_objects is not None:      # (area_offset / area_size above: the area of an env that uses all N objects)
-                r.num_active, r.num_objects_next, r.used_table_portion = P(self.num_active), P(self.num_objects_next), float(self.used_table_portion)
-                for i in range(N):
-                    for k in range(7):
-                        r.park_pose[i][k] = float(self.park_pose[i, k])
+                r.obj_center[i][k], r.obj_half[i][k] = float(self.obj_center[i, k]), float(self.obj_half[i, k])
+        for k in range(6):
+            r.arm_qposadr[k], r.arm_start[k] = self.arm_q[k], float(TABLETOP_EXPERIMENT_INITIAL_POS[k])
+            r.solver_arm_qposadr[k] = self.solver_arm_q[k] if self.solver_arm_q else 0
+        (off_x, off_y, _), (width, height, _) = self.placement_area(N)
+        r.area_offset[0], r.area_offset[1], r.area_size[0], r.area_size[1] = float(off_x), float(off_y), float(width), float(height)
+        for k in range(3):
+            r.table_pos[k], r.table_size[k] = float(self.table_pos[k]), float(self.table_size[k])
+        r.stabilize_steps, r.n_random_initial_steps, r.settle_steps = int(self.stabilize_steps), int(self.n_random_initial_steps), int(self.settle_steps)
+        r.seed, r.step = (int(starting_seed) * 2654435761 + 40503) & 0xFFFFFFFF, 0
+        r.goal_kind, r.height_range[0], r.height_range[1], r.object_size = self.goal_kind, self.height_range[0], self.height_range[1], self.object_size
+        r.fixed_order, r.target_height, r.goal_index = int(self.fixed_order), self.target_height, _ptr(self.goal_index)
+        for j in range(2):
+            for k in range(3):
+                r.det_points[j][k] = float(DET_REACH_POINTS[j, k])
+        r.goal_distance_ratio, r.goal_distance_min, r.pickup_proba, r.stacking_proba = _ptr(self.goal_distance_ratio), self.goal_distance_min, self.pickup_proba, self.stacking_proba
+        if self.obj_group is not None:
+            r.obj_group, r.group_mode = _ptr(self.obj_group), int(self.group_mode == "sample")
+            r.sample_lam[0], r.sample_lam[1] = self.sample_lam
+        r.randomize_goal_rot, r.domino_distance_mul = int(self.randomize_goal_rot), self.domino_distance_mul
+        if self.goal_kind_name == "fixed":
+            for i in range(N):
+                r.fixed_xy[i][0], r.fixed_xy[i][1], r.fixed_yaw[i] = float(self.relative_placements[i, 0]), float(self.relative_placements[i, 1]), float(self.init_yaw[i])
+        if self.max_num_objects is not None:      # (area_offset / area_size above: the area of an env that uses all N objects)
+            r.num_active, r.num_objects_next, r.used_table_portion = _ptr(self.num_active), _ptr(self.num_objects_next), float(self.used_table_portion)
+            for i in range(N):
+                for k in range(7):
+                    r.park_pose[i][k] = float(self.park_pose[i, k])
 
     # ------------------------------------------------------------------ launches
     def _stream(self):
         return None if self.sim._emul else ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def _post(self):
-        if self.icp is not None:      # rot_dist_type icp: the angles of this state, for the envs this launch of the env kernel scores (the same frozen codes)
+    def _post(self, frozen=None):
+        """The env kernel.  `frozen`: the [B] uint8 codes THIS launch goes by, in place of the ones the arguments point to (which they point to again afterwards)."""
+        if frozen is not None:
+            had, self.post.frozen = self.post.frozen, frozen.data_ptr()
+        if self.icp is not None:     # rot_dist_type icp: the angles of this state, for the envs this launch of the env kernel scores (the same frozen codes)
             self.icp.frozen = self.post.frozen
             _native.check(self._L, self._L.ra_env_icp(self.sim._bh, ctypes.byref(self.icp), self._stream()), "ra_env_icp")
         _native.check(self._L, self._L.ra_env_post_step(self.sim._bh, None if self.solver_sim is None else self.solver_sim._bh, ctypes.byref(self.post), self._stream()), "ra_env_post_step")
+        if frozen is not None:
+            self.post.frozen = had
 
     def _joint_action(self, actions, wrapped):
         """Joint control: the [B, 7] action that reaches `RobotEnv._set_action`.  With the wrapper stack: bin index -> value (DiscretizeActionWrapper.action,
@@ -793,7 +843,7 @@ class BatchedBlockRearrangeEnv:
         out = {"goal_dist_obj_pos": self.goal_dist[:, 0], "goal_dist_obj_rot": self.goal_dist[:, 1], "goal_reset": self.goal_reset, "trial_success": self.trial_success,
                "sub_goal_is_successful": self.sub_goal_ok, "env_crash": self.env_crash, "objects_off_table": self.objects_off_table, "successes_so_far": self.successes,
                "steps_since_last_goal": self.info_ssl, "resetting": self.resetting, "episode_started": self.episode_started}
-        if self.goal_kind == 2:      # ObjectStackGoal.goal_distance's two more keys, summed as goal_info["goal_dist"] sums every key (robot_env.py:611)
+        if self.goal_kind_name == "stack":      # ObjectStackGoal.goal_distance's two more keys, summed as goal_info["goal_dist"] sums every key (robot_env.py:611)
             out["goal_dist_gripper_pos"], out["goal_dist_grasped"] = self.goal_dist_extra[:, 0], self.goal_dist_extra[:, 1]
         return out
 
@@ -821,14 +871,12 @@ class BatchedBlockRearrangeEnv:
     def _grid_placement(self, yaw, rows, n=None):
         """place_objects_in_grid (common/utils.py:719-829) for boxes: AABB of each yawed block, a grid of cells sized by the largest block over the
         placement area (simulation/base.py:992-1010), distinct random cells.  `n`: the first n objects only (`yaw` [len(rows), n]), in the placement area of that count."""
-        B, N = len(rows), self.N if n is None else int(n)
-        obj_center, obj_half = self.obj_center[:N], self.obj_half[:N]
-        # (without per-env counts the helpers are called as they always were: tests stand in for them with the one-argument forms)
-        half = self._aabb_half(yaw) if n is None else self._aabb_half(yaw, N)      # rotate_bounding_box
-        c, s_ = np.cos(yaw), np.sin(yaw)
-        centre = np.stack([c * obj_center[:, 0] - s_ * obj_center[:, 1], s_ * obj_center[:, 0] + c * obj_center[:, 1], np.broadcast_to(obj_center[:, 2], yaw.shape)], -1)
-        (off_x, off_y, _), (width, height, _) = self.placement_area() if n is None else self.placement_area(n)
-        out = np.zeros((B, N, 3))
+        if n is None:
+            n = self.N
+        B, N = len(rows), int(n)
+        obj_half = self.obj_half[:N]
+        half = self._aabb_half(yaw, N)
+        offset, (width, height, _) = self.placement_area(N)
         xy = np.zeros((B, N, 2))
         ncol, nrow = (width // (2 * half[:, :, 0].max(1))).astype(int), (height // (2 * half[:, :, 1].max(1))).astype(int)
         crowded = ncol * nrow < N
@@ -873,86 +921,84 @@ class BatchedBlockRearrangeEnv:
                 xy[pending[alive]] = cur[alive]
                 pending = pending[~alive]
         p = np.concatenate([xy, half[:, :, 2:3] + 2 * self.table_size[2]], -1)
-        out = p + [off_x, off_y, 0.0] - self.table_size + self.table_pos - centre      # (the body origin, from the centre of its bounding box)
-        return out
+        return area_to_world(p, offset, self.table_pos, self.table_size) - yawed_centre(self.obj_center[:N], yaw)      # (the body origin, from the centre of its bounding box)
 
     def placement_area(self, n=None):
         """RearrangeSimulationInterface.get_placement_area / get_table_setting (simulation/base.py:980-1010): (offset, size) of the box objects and goals are placed
         in, offset measured from the table's low corner; `used_table_portion` is clipped to at least a tenth per object.  `n`: the area of an env that uses n objects
         (per-env object counts; default: all of them)."""
+        if n is None:
+            n = self.N
         tsx, tsy = 2 * self.table_size[0], 2 * self.table_size[1]
-        portion = float(np.clip(self.used_table_portion, (self.N if n is None else int(n)) * 0.1, 1.0))
+        portion = float(np.clip(self.used_table_portion, int(n) * 0.1, 1.0))
         width, height = 0.5 * tsx * portion, 0.38 * tsy * portion
         return (0.5 * tsx - width / 2.0, 0.44 * tsy - height / 2.0, 2 * self.table_size[2]), (width, height, 0.26)
 
     def _next_goal(self, rows, yaw):
         """`_update_simulation_for_next_goal` (goals/object_state.py:333-358) for the envs `rows`, whose goals have the yaws `yaw` [len(rows), N]: with
-        `randomize_goal_rot` new yaws first (per env, in the reference's draw order), then the positions for boxes turned by them; the domino goal sets yaws of its
-        own.  -> (positions, yaws): `_write_goal`'s arguments."""
+        `randomize_goal_rot` new yaws first (per env, over its active objects, in the reference's draw order; an unused slot keeps yaw 0), then the positions for boxes
+        turned by them; the kinds of OWN_YAW_KINDS set yaws of their own.  -> (positions, yaws): `_write_goal`'s arguments."""
         counts = self._counts(rows)
         if self.randomize_goal_rot and len(rows):
-            if counts is None:
-                yaw = np.stack([randomize_yaw_along_z(self._rng, y) for y in yaw])
-            else:      # (the env's active objects only; an unused slot keeps yaw 0)
-                yaw = np.array(yaw, dtype=np.float64)
-                for r, c in enumerate(counts):
-                    yaw[r, :c] = randomize_yaw_along_z(self._rng, yaw[r, :c])
-        if counts is not None:
-            return self._by_count(rows, yaw, counts, self._goal_positions), yaw
-        if self.goal_kind == 6:
-            return self._domino_goals(len(rows))
-        if self.goal_kind in (7, 8):      # set_target_quat inside _sample_next_goal_positions, AFTER the randomisation: init_quats' yaws, always
-            yaw = np.tile(self.init_yaw, (len(rows), 1))
-        return self._goal_positions(rows, yaw), yaw
+            yaw = np.array(yaw, dtype=np.float64)
+            for r, c in enumerate(counts):
+                yaw[r, :c] = randomize_yaw_along_z(self._rng, yaw[r, :c])
+        if self.goal_kind_name in OWN_YAW_KINDS:
+            return self._own_yaw_goals(len(rows))
+        return self._by_count(rows, yaw, counts, self._goal_positions), yaw
 
-    def _domino_goals(self, R):
-        """DominoStateGoal for `R` envs (host numpy; ra_domino_arc does the same on the device): the dominos on a circle arc -> ([R, N, 3], yaws [R, N])"""
-        offset, size = self.placement_area()
-        pos, yaws = np.zeros((R, self.N, 3)), np.zeros((R, self.N))
+    def _own_yaw_goals(self, R):
+        """The goals of `R` envs for the kinds that turn the goals themselves, AFTER the randomisation (host numpy; ra_recipe_kernel does the same on the device):
+        DominoStateGoal's circle arc with its yaws, AttachedBlockStateGoal's lattice (a permutation and an origin per env) and ObjectFixedStateGoal's table with
+        init_quats' yaws, always -> ([R, N, 3], yaws [R, N])"""
+        table = (self.table_pos, self.table_size) + self.placement_area(self.N)
+        pos, yaws = np.zeros((R, self.N, 3)), np.tile(self.init_yaw, (R, 1))
         for r in range(R):
-            pos[r], yaws[r], ok = domino_goal(self._rng, self.obj_half, self.object_size * self.domino_distance_mul, self.table_pos, self.table_size, offset, size)
+            if self.goal_kind_name == "dominos":
+                pos[r], yaws[r], ok = domino_goal(self._rng, self.obj_half, self.object_size * self.domino_distance_mul, *table)
+            elif self.goal_kind_name == "attached":
+                pos[r], ok = attached_goal(self._rng, self.obj_center, self.obj_half, self.object_size, *table)
+            else:
+                pos[r], ok = fixed_goal(self.relative_placements, self.obj_center, self.obj_half, *table)
             if not ok:
                 self.host_placement_failed += 1
         return pos, yaws
 
     def _counts(self, rows):
-        """per-env object counts: the latched counts of the envs `rows` as host integers (the host recipe reads flags back anyway); None without max_num_objects"""
+        """The object counts of the envs `rows` as host integers: N without max_num_objects (no device access), else the latched counts (the host recipe reads flags
+        back anyway)"""
         if self.max_num_objects is None:
-            return None
+            return np.full(len(rows), self.N)
         return self.num_active[torch.as_tensor(rows, device=self.device, dtype=torch.long)].cpu().numpy().astype(np.int64)
 
+    def _parked(self):
+        """[N, 7] what fills an unused slot: its parking pose (zeros without max_num_objects, where no slot is unused and the fill is never read)"""
+        return np.zeros((self.N, 7)) if self.park_pose is None else self.park_pose
+
     def _by_count(self, rows, yaw, counts, fn):
-        """per-env object counts: `fn(rows_n, yaw_n, n)` -> [len(rows_n), n, 3] for the rows of each count n (ascending), put together as [len(rows), N, 3] with the
-        unused slots at their parking positions."""
+        """`fn(rows_n, yaw_n, n)` -> [len(rows_n), n, 3] for the rows of each count n (ascending), put together as [len(rows), N, 3] with the unused slots at their
+        parking positions."""
         rows = np.asarray(rows)
-        out = np.tile(self.park_pose[None, :, :3], (len(rows), 1, 1))
+        out = np.tile(self._parked()[None, :, :3], (len(rows), 1, 1))
         for n in np.unique(counts):
             sel = np.nonzero(counts == n)[0]
             out[sel, :n] = fn(rows[sel], yaw[sel, :n], int(n))
         return out
 
     def _goal_positions(self, rows, yaw, n=None):
-        """`_sample_next_goal_positions` of the env's goal generator for the envs `rows` (host numpy; ra_recipe_kernel does the same on the device): [len(rows), N, 3].
-        Reach also moves the object itself (`set_object_pos`: position only) -- the caller's forward makes the observation see it.  `n`: for the first n objects only
-        (`yaw` [len(rows), n]; per-env object counts: kinds 0, 1, 2 and 5)."""
-        R, N, kind = len(rows), self.N if n is None else int(n), self.goal_kind
-        if kind == 6:          # (the arc's positions; its yaws go with them through _next_goal)
-            return self._domino_goals(R)[0]
-        if kind in (7, 8):     # the fixed placements: AttachedBlockStateGoal's lattice (a permutation and an origin per env) / ObjectFixedStateGoal's table
-            offset, size = self.placement_area()
-            where = (self.obj_center, self.obj_half, self.table_pos, self.table_size, offset, size)
-            if kind == 8:
-                return np.tile(fixed_goal(self.relative_placements, *where)[0], (R, 1, 1))
-            return np.array([attached_goal(self._rng, self.obj_center, self.obj_half, self.object_size, *where[2:])[0] for _ in range(R)]).reshape(R, N, 3)
-        if kind == 5:          # TrainStateGoal: goals near the objects' current positions, then one in the air or a tower (goals/train_state.py:81-113)
+        """`_sample_next_goal_positions` of the env's goal generator for the envs `rows` (host numpy; ra_recipe_kernel does the same on the device), for the first `n`
+        objects (default: all of them) in the placement area of that count, `yaw` [len(rows), n] -> [len(rows), n, 3].  Every kind but those of OWN_YAW_KINDS
+        (`_own_yaw_goals`).  Reach also moves the object itself (`set_object_pos`: position only) -- the caller's forward makes the observation see it."""
+        if n is None:
+            n = self.N
+        R, N, kind = len(rows), int(n), self.goal_kind_name
+        if kind in ("train",) + REACH_KINDS:
             idx = torch.as_tensor(rows, device=self.device, dtype=torch.long)
+        if kind == "train":    # TrainStateGoal: goals near the objects' current positions, then one in the air or a tower (goals/train_state.py:81-113)
             qpos = self.sim.qpos[idx].cpu().numpy().astype(np.float64)
             ratios = self.goal_distance_ratio[idx].cpu().numpy().astype(np.float64)
-            half = self._aabb_half(yaw) if n is None else self._aabb_half(yaw, N)
-            c, s_ = np.cos(yaw), np.sin(yaw)
-            oc = self.obj_center[:N]
-            centre = np.stack([c * oc[:, 0] - s_ * oc[:, 1], s_ * oc[:, 0] + c * oc[:, 1], np.broadcast_to(oc[:, 2], yaw.shape)], -1)
-            offset, size = self.placement_area() if n is None else self.placement_area(n)
+            half, centre = self._aabb_half(yaw, N), yawed_centre(self.obj_center[:N], yaw)
+            offset, size = self.placement_area(N)
             pos = np.zeros((R, N, 3))
             for r in range(R):
                 op = np.array([qpos[r, qa:qa + 3] for qa in self.obj_q[:N]])
@@ -961,26 +1007,25 @@ class BatchedBlockRearrangeEnv:
                     self.host_placement_failed += 1
                 move_one_object_to_the_air_with_restrictions(self._rng, pos[r], self.height_range, self.object_size, self.pickup_proba, self.stacking_proba, ratios[r])
             return pos
-        if kind <= 1:
-            pos = self._grid_placement(yaw, rows) if n is None else self._grid_placement(yaw, rows, n)
-            if kind == 1:      # move_one_object_to_the_air (goals/pickandplace.py:30-52): a height, then the object it raises
+        if kind in ("object_state", "pickandplace"):
+            pos = self._grid_placement(yaw, rows, N)
+            if kind == "pickandplace":      # move_one_object_to_the_air (goals/pickandplace.py:30-52): a height, then the object it raises
                 h = self._rng.uniform(self.height_range[0], self.height_range[1], R)
                 pos[np.arange(R), self._rng.randint(N, size=R), 2] += h
             return pos
-        if kind == 4:          # DeterministicReachGoal: the next of its two points, per env
-            idx = torch.as_tensor(rows, device=self.device, dtype=torch.long)
+        if kind == "det-reach":      # DeterministicReachGoal: the next of its two points, per env
             gi = (self.goal_index[idx] + 1) % 2
             self.goal_index[idx] = gi
             bottom = DET_REACH_POINTS[gi.cpu().numpy()]
-        else:                  # place_objects_with_no_constraint on object 0's box alone
-            bottom = self._free_placement_of_object0(yaw[:, 0]) if n is None else self._free_placement_of_object0(yaw[:, 0], n)
-        if kind == 2:          # ObjectStackGoal: the others on top of object 0's placement, in a shuffled block order unless fixed_order
+        else:                        # place_objects_with_no_constraint on object 0's box alone
+            bottom = self._free_placement_of_object0(yaw[:, 0], N)
+        if kind == "stack":          # ObjectStackGoal: the others on top of object 0's placement, in a shuffled block order unless fixed_order
             pos = np.repeat(bottom[:, None, :], N, 1)
             for r in range(R):
                 order = np.arange(N) if self.fixed_order else self._rng.permutation(N)
                 pos[r, order, 2] += np.arange(N) * 2 * self.object_size
             return pos
-        idx = torch.as_tensor(rows, device=self.device, dtype=torch.long)      # reach
+        assert kind in REACH_KINDS, kind
         qa = self.obj_q[0]
         self.sim.qpos[idx, qa:qa + 3] = torch.tensor(bottom.astype(np.float32), device=self.device)
         pos = bottom[:, None, :].copy()
@@ -990,22 +1035,17 @@ class BatchedBlockRearrangeEnv:
     def _free_placement_of_object0(self, yaw0, n=None):
         """place_objects_with_no_constraint (common/utils.py:829-880) for object 0 alone: a uniform proposal inside the placement area (one object: always free);
         the body origin in world coordinates, as _grid_placement gives it.  `yaw0` [R]; `n`: in the placement area of that object count."""
-        (off_x, off_y, _), (width, height, _) = self.placement_area() if n is None else self.placement_area(n)
-        sx, sy = self.obj_half[0, 0], self.obj_half[0, 1]
-        c, s_ = np.cos(yaw0), np.sin(yaw0)
-        hx, hy = np.abs(c) * sx + np.abs(s_) * sy, np.abs(s_) * sx + np.abs(c) * sy
-        x, y = self._rng.uniform(hx, width - hx), self._rng.uniform(hy, height - hy)
-        centre = np.stack([c * self.obj_center[0, 0] - s_ * self.obj_center[0, 1], s_ * self.obj_center[0, 0] + c * self.obj_center[0, 1], np.full_like(yaw0, self.obj_center[0, 2])], -1)
-        p = np.stack([x, y, np.full_like(yaw0, self.obj_half[0, 2] + 2 * self.table_size[2])], -1)
-        return p + [off_x, off_y, 0.0] - self.table_size + self.table_pos - centre
+        offset, (width, height, _) = self.placement_area(n)
+        h = yawed_half(self.obj_half[:1], yaw0[:, None])[:, 0]
+        x, y = self._rng.uniform(h[:, 0], width - h[:, 0]), self._rng.uniform(h[:, 1], height - h[:, 1])
+        p = np.stack([x, y, h[:, 2] + 2 * self.table_size[2]], -1)
+        return area_to_world(p, offset, self.table_pos, self.table_size) - yawed_centre(self.obj_center[:1], yaw0[:, None])[:, 0]
 
     def _forward_rows(self, rows):
         """_observe_sync's forward (one controller tick, the full stage arrays) for the envs `rows` only."""
         if len(rows) == 0:
             return
-        active = torch.zeros(self.B, dtype=torch.int32, device=self.device)
-        active[torch.as_tensor(rows, device=self.device, dtype=torch.long)] = 1
-        self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=active)
+        self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=self._mask_of(rows, torch.int32))
 
     def _write_goal(self, rows, goal_pos, yaw):
         dev = self.device
@@ -1013,18 +1053,15 @@ class BatchedBlockRearrangeEnv:
         eul = np.zeros(goal_pos.shape); eul[..., 2] = np.mod(yaw + np.pi, 2 * np.pi) - np.pi        # mat2euler of a z-rotation, normalised as get_target_rot + normalize_angles give it
         quat = euler2quat(eul)
         g = np.concatenate([goal_pos, quat], -1).astype(np.float32)
-        counts = self._counts(rows)
-        if counts is not None:      # an unused slot: its parked pose in qpos_goal, a zero goal row (identity orientation)
-            unused = np.arange(self.N)[None, :] >= counts[:, None]
-            g[unused] = np.broadcast_to(self.park_pose.astype(np.float32)[None], g.shape)[unused]
-            eul[unused] = 0.0
+        unused = np.arange(self.N)[None, :] >= self._counts(rows)[:, None]      # an unused slot: its parked pose in qpos_goal, a zero goal row (identity orientation)
+        g[unused] = np.broadcast_to(self._parked().astype(np.float32)[None], g.shape)[unused]
+        eul[unused] = 0.0
         self.goal_rot[idx] = torch.tensor(eul.astype(np.float32), device=dev)
         qg = self.sim.qpos[idx].clone()                                   # qpos_goal: the current qpos with the objects at their goals (object_state.py:381-389)
         for i, qa in enumerate(self.obj_q):
             qg[:, qa:qa + 7] = torch.tensor(g[:, i], device=dev)
         self.qpos_goal[idx] = qg
-        if counts is not None:
-            g[unused] = np.array([0, 0, 0, 1, 0, 0, 0], dtype=np.float32)
+        g[unused] = np.array([0, 0, 0, 1, 0, 0, 0], dtype=np.float32)
         self.goal[idx] = torch.tensor(g, device=dev)
         self.prev_valid[idx] = 0
 
@@ -1033,15 +1070,12 @@ class BatchedBlockRearrangeEnv:
         rotations about z and their placement, bounding boxes / colours of the static observation.  Returns the drawn yaw angles [len(rows), N]."""
         dev, N = self.device, self.N
         A = self.model.arrays
-        counts = None
         if self.max_num_objects is not None:      # the count of the episode that begins: _recreate_sim builds the simulation with the current num_objects (common/base.py:850-856, 904)
             self.num_active[idx] = self.num_objects_next[idx].clamp(1, N)
-            counts = self._counts(rows)
-        if self.group_mode == "sample":      # _randomize_object_groups: the first act of RearrangeEnv._reset (common/base.py:903)
-            if counts is None:
-                rows_ids = np.stack([group_ids(sample_group_counts(self._rng, N, *self.sample_lam)) for _ in rows])
-            else:      # (over the env's own count; an unused slot belongs to no group: -1)
-                rows_ids = np.stack([np.concatenate([group_ids(sample_group_counts(self._rng, int(c), *self.sample_lam)), np.full(N - int(c), -1, dtype=np.int32)]) for c in counts])
+        counts = self._counts(rows)
+        unused = np.arange(N)[None, :] >= counts[:, None]
+        if self.group_mode == "sample":      # _randomize_object_groups: the first act of RearrangeEnv._reset (common/base.py:903), over the env's own count; an unused slot belongs to no group: -1
+            rows_ids = np.stack([np.concatenate([group_ids(sample_group_counts(self._rng, int(c), *self.sample_lam)), np.full(N - int(c), -1, dtype=np.int32)]) for c in counts])
             self.obj_group[idx] = torch.tensor(rows_ids, dtype=torch.int32, device=dev)
         worlds = [(self.sim, A)] + ([] if self.solver_sim is None else [(self.solver_sim, self.solver_model.arrays)])
         if self.per_env_parameters:      # _recreate_sim (common/base.py:850-856): a fresh model -- the previous episode's randomised values are gone
@@ -1065,21 +1099,18 @@ class BatchedBlockRearrangeEnv:
         if self.solver_sim is not None:
             self.solver_sim.qpos[idx[:, None], torch.tensor(self.solver_arm_q, device=dev)] = arm0
             self.solver_sim.eq_data[idx, :7] = torch.tensor([0, 0, 0, 1, 0, 0, 0], dtype=torch.float32, device=dev)     # reset_mocap_welds
-        # object rotations about z and grid placement (common/base.py:613-640, 797-822)
+        # object rotations about z and grid placement (common/base.py:613-640, 797-822): the env's first n objects in the placement area of n objects, the others
+        # parked (identity orientation: yaw 0)
         yaw = self._rng.uniform(0.0, 2 * np.pi, (len(rows), N))
-        if counts is None:
-            pos = self._grid_placement(yaw, rows)
-        else:                            # the env's first n objects in the placement area of n objects, the others parked (identity orientation: yaw 0)
-            unused = np.arange(N)[None, :] >= counts[:, None]
-            yaw[unused] = 0.0
-            pos = self._by_count(rows, yaw, counts, lambda rows_n, yaw_n, n: self._grid_placement(yaw_n, rows_n, n))
+        yaw[unused] = 0.0
+        pos = self._by_count(rows, yaw, counts, lambda rows_n, yaw_n, n: self._grid_placement(yaw_n, rows_n, n))
         quat = np.stack([np.cos(yaw / 2), 0 * yaw, 0 * yaw, np.sin(yaw / 2)], -1)
         for i, qa in enumerate(self.obj_q):
             self.sim.qpos[idx, qa:qa + 7] = torch.tensor(np.concatenate([pos[:, i], quat[:, i]], -1).astype(np.float32), device=dev)
         colors = self._rng.random_sample((len(rows), N, 4)); colors[..., 3] = 1.0
         so = np.concatenate([np.broadcast_to(self._aabb_half(yaw), (len(rows), N, 3)), colors], -1)
-        if counts is not None:
-            so[unused] = 0.0
+        so[unused] = 0.0
+        if self.max_num_objects is not None:
             self._apply_parking(self._mask_of(idx))      # (after the block's restore above: a fresh model has no wrench and the model's damping)
         self.static_obs[idx] = torch.tensor(so.astype(np.float32), device=dev)
         return yaw
@@ -1087,16 +1118,15 @@ class BatchedBlockRearrangeEnv:
     def _mocap_to_body(self, idx, body):
         """reset_mocap_welds + "mocap pose <- that body's pose" for the envs `idx`: the weld's relative pose back to identity, one forward (kinematics + the controller
         tick of mj_forward), the mocap row from the body's frame (gym.envs.robotics.utils.reset_mocap_welds / reset_mocap2body_xpos)."""
-        active = torch.zeros(self.B, dtype=torch.int32, device=self.device); active[idx] = 1
         self.sim.eq_data[idx, :7] = torch.tensor([0, 0, 0, 1, 0, 0, 0], dtype=torch.float32, device=self.device)
-        self.sim.env_step(nsubsteps=0, nforward_ticks=1, active=active)
+        self.sim.env_step(nsubsteps=0, nforward_ticks=1, active=self._mask_of(idx, torch.int32))
         xp, xq = self.sim.scratch("xpos"), self.sim.scratch("xquat")
         self.sim.mocap[idx] = torch.cat([xp[idx, 3 * body:3 * body + 3], xq[idx, 4 * body:4 * body + 4]], 1)
 
     def _initialize_mocap_world(self, idx):
         """RearrangeEnv._initialize_sim_state for a mocap-actuated arm (common/base.py:448-465): welds reset, forward, the mocap body put at the pose of
         robot0:gripper_base, ten simulation steps (the weld pulls the TCP there)."""
-        active = torch.zeros(self.B, dtype=torch.int32, device=self.device); active[idx] = 1
+        active = self._mask_of(idx, torch.int32)
         self._mocap_to_body(idx, self._gripper_base_body)
         for _ in range(10):
             self.sim.env_step(nforward_ticks=1, active=active)
@@ -1107,9 +1137,9 @@ class BatchedBlockRearrangeEnv:
         rows = np.arange(self.B) if mask is None else np.nonzero(mask.cpu().numpy())[0]
         if len(rows) == 0:
             return self.observe()
-        dev, N = self.device, self.N
+        dev = self.device
         idx = torch.as_tensor(rows, device=dev, dtype=torch.long)
-        active = torch.zeros(self.B, dtype=torch.int32, device=dev); active[idx] = 1
+        active = self._mask_of(idx, torch.int32)
         if self.pipelined:       # a synchronous reset ends whatever recipe those envs were in
             self._stage[rows] = 0; self._left[rows] = 0
             if self.device_reset:
@@ -1131,17 +1161,26 @@ class BatchedBlockRearrangeEnv:
                 self._recipe_physics(act, active)
             for _ in range(self.settle_steps):
                 self._recipe_physics(self._zero_action, active)
-        # tracker reset and the first goal (robot_env.py:780-792; ObjectStateGoal.next_goal; randomize_goal_rot: _next_goal)
+        self._start_episode(rows, idx, yaw)
+        self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=active)       # the forward of _observe_sync, after the goal is written
+        # the first observation of the new episodes: the env kernel for exactly those rows (observation + gripper hand-over, zeroed reward / done, the success count
+        # the first step's goal reward is measured from); the rows of everybody else -- and the reward / done / info tensors their last step() returned -- stay
+        self._reobserve(rows, np.zeros(0, dtype=np.int64))
+        return self.observe()
+
+    def _start_episode(self, rows, idx, yaw):
+        """The end of the reset recipe for the envs `rows` (`idx`: the same as a device index), whose objects were placed with the yaws `yaw`: tracker reset and the
+        first goal (robot_env.py:780-792; ObjectStateGoal.next_goal; randomize_goal_rot: _next_goal)."""
         for f in (self.t, self.steps, self.ssl, self.successes, self.consecutive, self.ema_t):
             f[idx] = 0
         self.ema_value[idx] = 0; self.action_ema[idx] = 0          # SmoothActionWrapper.reset: a fresh filter, action_ema = 0
         self._randomize_simulation(idx)                               # simulation_randomizer.randomize AFTER _reset (robot_env.py:779-783)
         self._write_goal(rows, *self._next_goal(rows, yaw))
-        self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=active)       # the forward of _observe_sync
-        # the first observation of the new episodes: the env kernel for exactly those rows (observation + gripper hand-over, zeroed reward / done, the success count
-        # the first step's goal reward is measured from); the rows of everybody else -- and the reward / done / info tensors their last step() returned -- stay
-        self._reobserve(rows, np.zeros(0, dtype=np.int64))
-        return self.observe()
+
+    def _regoal(self, rows):
+        """ObjectStateGoal.next_goal for the live envs `rows`: the next goal, from the yaws of the one they have"""
+        yaw = self.goal_rot[torch.as_tensor(rows, device=self.device, dtype=torch.long), :, 2].cpu().numpy().astype(np.float64)
+        self._write_goal(rows, *self._next_goal(rows, yaw))
 
     # ------------------------------------------------------------------ pipelined resets
     def _reobserve(self, started, regoaled):
@@ -1153,10 +1192,7 @@ class BatchedBlockRearrangeEnv:
         self.frozen.fill_(2)
         self.frozen[torch.as_tensor(started, device=self.device, dtype=torch.long)] = 1
         self.frozen[torch.as_tensor(regoaled, device=self.device, dtype=torch.long)] = 3
-        had = self.post.frozen
-        self.post.frozen = self.frozen.data_ptr()
-        self._post()
-        self.post.frozen = had
+        self._post(frozen=self.frozen)
         self.frozen.copy_(saved)
 
     def _advance_recipes(self):
@@ -1193,19 +1229,14 @@ class BatchedBlockRearrangeEnv:
             rows = np.concatenate(started)
             idx = torch.as_tensor(rows, device=dev, dtype=torch.long)
             st[rows], left[rows] = 0, 0
-            for f in (self.t, self.steps, self.ssl, self.successes, self.consecutive, self.ema_t, self.hold):
-                f[idx] = 0
-            self.ema_value[idx] = 0; self.action_ema[idx] = 0; self.scripted[idx] = 0
-            self.frozen[idx] = 0; self.solver_active[idx] = 1; self.hold_ctrl[idx] = 0
+            self.hold[idx] = 0; self.scripted[idx] = 0; self.frozen[idx] = 0; self.solver_active[idx] = 1; self.hold_ctrl[idx] = 0
             self.resetting[idx] = False; self.episode_started[idx] = True
-            self._randomize_simulation(idx)
-            self._write_goal(rows, *self._next_goal(rows, self._yaw[rows]))
+            self._start_episode(rows, idx, self._yaw[rows])
         # ---- live envs with a reached goal: ObjectStateGoal.next_goal (what reset_goals() does on request)
         grows = np.nonzero(newgoal.astype(bool) & (st == 0) & ~done.astype(bool))[0]     # (an episode that ends on the same step keeps the reached goal's entries in its terminal observation: ra_recipe_kernel)
         if len(grows):
-            yaw = self.goal_rot[torch.as_tensor(grows, device=dev, dtype=torch.long), :, 2].cpu().numpy().astype(np.float64)
-            self._write_goal(grows, *self._next_goal(grows, yaw))
-        if self.reach:
+            self._regoal(grows)
+        if self.reach:      # (one forward and one re-observation for the rows that start and the rows with a new goal)
             self._forward_rows(np.concatenate(started + [grows]))
         self._reobserve(np.concatenate(started) if started else np.zeros(0, dtype=np.int64), grows)
         # ---- episodes that ended on this step: their recipe begins (the returned observation / reward / done are the terminal ones)
@@ -1249,10 +1280,7 @@ class BatchedBlockRearrangeEnv:
                 self._apply_parking(self.ended | self.stabilised | self.episode_started)
         if self.reach:      # the object the goal moved: _observe_sync's forward for the envs with a new goal (no readback: every env, masked by the reobserve codes)
             self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=(self.reobserve != 2).to(torch.int32))
-        had = self.post.frozen
-        self.post.frozen = self.reobserve.data_ptr()
-        self._post()
-        self.post.frozen = had
+        self._post(frozen=self.reobserve)
         self.ended_rows = np.zeros(0, dtype=np.int64)
 
     def _set_object_damping(self, idx, value):
@@ -1265,8 +1293,10 @@ class BatchedBlockRearrangeEnv:
         if self.max_num_objects is not None:      # (a parked object keeps its own damping)
             self._apply_parking(self._mask_of(idx))
 
-    def _mask_of(self, idx):
-        mask = torch.zeros(self.B, dtype=torch.bool, device=self.device); mask[idx] = True
+    def _mask_of(self, idx, dtype=torch.bool):
+        """[B] mask of the envs `idx` (rows or a device index): bool, or int32 as the launches' `active` argument"""
+        mask = torch.zeros(self.B, dtype=dtype, device=self.device)
+        mask[torch.as_tensor(idx, device=self.device, dtype=torch.long)] = 1
         return mask
 
     def _apply_parking(self, mask):
@@ -1304,7 +1334,7 @@ class BatchedBlockRearrangeEnv:
         model field from the model's own (the block was restored at the start of the reset), on the device."""
         if not self.randomizers:
             return
-        mask = torch.zeros(self.B, dtype=torch.bool, device=self.device); mask[idx] = True
+        mask = self._mask_of(idx)
         for r in self.randomizers:
             r.randomize(self.sim, self._rand_gen, mask)
         if self.max_num_objects is not None:      # (gravity and body masses may have changed: the cancelling force follows them)
@@ -1312,8 +1342,7 @@ class BatchedBlockRearrangeEnv:
 
     def _aabb_half(self, yaw, n=None):
         """half extents [.., N, 3] of the objects' bounding boxes after a rotation by `yaw` [.., N] about z (`n`: of the first n objects, `yaw` [.., n])"""
-        sx, sy, sz = self.obj_half[:n, 0], self.obj_half[:n, 1], self.obj_half[:n, 2]
-        return np.stack([np.abs(np.cos(yaw)) * sx + np.abs(np.sin(yaw)) * sy, np.abs(np.sin(yaw)) * sx + np.abs(np.cos(yaw)) * sy, np.broadcast_to(sz, yaw.shape)], -1)
+        return yawed_half(self.obj_half[:n], yaw)
 
     def _observe_only(self, rows=None):
         """The observation rows of `rows` (default: everybody) from the state as it is, without a step: observation entries, gripper hand-over, zeroed
@@ -1325,8 +1354,7 @@ class BatchedBlockRearrangeEnv:
         rows = np.nonzero(self.goal_reset.cpu().numpy())[0]
         if len(rows) == 0:
             return
-        yaw = self.goal_rot[torch.as_tensor(rows, device=self.device, dtype=torch.long), :, 2].cpu().numpy().astype(np.float64)
-        self._write_goal(rows, *self._next_goal(rows, yaw))
+        self._regoal(rows)
         if self.reach:
             self._forward_rows(rows)
         self._reobserve(np.zeros(0, dtype=np.int64), rows)      # robot_env.py:893-909: the observation returned after a goal reset carries the new goal

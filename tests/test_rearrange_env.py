@@ -718,3 +718,28 @@ def test_env_kernel_goal_layer_matches_reference_code_emul(emul_lib):
 @pytest.mark.gpu
 def test_env_kernel_goal_layer_matches_reference_code_gpu():
     _env_kernel_goal_layer(None, "cuda:0", B=16)
+
+
+# ------------------------------------------------------------------------------------------------ the order of the host recipe's draws
+def test_host_recipe_draws_are_pinned_emul(emul_lib):
+    """The host reset / goal recipe, env by env: what `_begin_episode_state`, `_next_goal` and `_write_goal` write for seed 7, two goals in a row, and the generator's
+    next draw, against tests/golden/rearrange_host_draws.npz (tools/gen_golden_rearrange_host_draws.py, whose driver this runs).  The samplers' own goldens pin each
+    of them; this pins the order in which the env calls them.  float64 host values to 1e-12 (libm's last bit), float32 device rows to 1e-6, integer rows exactly."""
+    import importlib.util
+    import os
+
+    root = os.path.join(os.path.dirname(__file__), "..")
+    spec = importlib.util.spec_from_file_location("gen_golden_rearrange_host_draws", os.path.join(root, "tools", "gen_golden_rearrange_host_draws.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    want = np.load(os.path.join(os.path.dirname(__file__), "golden", "rearrange_host_draws.npz"))
+    got = tool.record_host_draws(emul_lib)
+    assert sorted(got) == sorted(want.files) and len({k.split("/")[0] for k in got}) == 13
+    for k in sorted(got):
+        g, w = got[k], want[k]
+        assert g.dtype == w.dtype and g.shape == w.shape, k
+        if g.dtype.kind == "f":
+            err = float(np.abs(g.astype(np.float64) - w.astype(np.float64)).max())
+            assert err <= (1e-12 if g.dtype == np.float64 else 1e-6), (k, err)
+        else:
+            assert np.array_equal(g, w), k

@@ -583,8 +583,8 @@ def test_crowded_table_placement_keeps_objects_apart():
         A, gn = model.arrays, model.names["geom"]
         tb, tg = model.name2id("body", "table"), gn.index("table")
         e.table_pos, e.table_size, e.used_table_portion, e._rng = A["body_pos"][tb].copy(), A["geom_size"][tg].copy(), 1.0, np.random.RandomState(3)
-        e._aabb_half = lambda yaw, e=e: Bk.BatchedBlockRearrangeEnv._aabb_half(e, yaw)
-        e.placement_area = lambda e=e: Bk.BatchedBlockRearrangeEnv.placement_area(e)
+        e._aabb_half = lambda yaw, n=None, e=e: Bk.BatchedBlockRearrangeEnv._aabb_half(e, yaw, n)
+        e.placement_area = lambda n=None, e=e: Bk.BatchedBlockRearrangeEnv.placement_area(e, n)
         B = 256
         yaw = e._rng.uniform(0, 2 * np.pi, (B, N))
         half = e._aabb_half(yaw)

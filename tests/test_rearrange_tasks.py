@@ -93,20 +93,20 @@ def test_host_goal_kinds_replay_the_reference_goal_code_emul(emul_lib):
     for N in (1, 5):
         env = _env(emul_lib, "cpu", 1, num_objects=N, goal_kind="pickandplace")
         for t in range(len(g["pnp%d_goal" % N])):
-            env._grid_placement = lambda yaw, rows, t=t: g["pnp%d_placement" % N][t][None].copy()
+            env._grid_placement = lambda yaw, rows, n=None, t=t: g["pnp%d_placement" % N][t][None].copy()
             env._rng = ReplayRng(uniform=[g["pnp%d_height" % N][t]], randint=[g["pnp%d_index" % N][t]])
             assert np.abs(env._goal_positions(np.arange(1), np.zeros((1, N)))[0] - g["pnp%d_goal" % N][t]).max() < 1e-12
     for N, fixed in ((2, False), (5, False), (5, True)):
         tag = "stack%d%s" % (N, "_fixed" if fixed else "")
         env = _env(emul_lib, "cpu", 1, num_objects=N, goal_kind="stack", fixed_order=fixed)
         for t in range(len(g[tag + "_goal"])):
-            env._free_placement_of_object0 = lambda yaw0, t=t: g[tag + "_bottom"][t].copy()
+            env._free_placement_of_object0 = lambda yaw0, n=None, t=t: g[tag + "_bottom"][t].copy()
             env._rng = ReplayRng(permutation=[] if fixed else [g[tag + "_order"][t]])
             assert np.abs(env._goal_positions(np.arange(1), np.zeros((1, N)))[0] - g[tag + "_goal"][t]).max() < 1e-12
     env = _env(emul_lib, "cpu", 1, num_objects=1, goal_kind="reach")
     qa = env.obj_q[0]
     for t in range(8):
-        env._free_placement_of_object0 = lambda yaw0, t=t: g["reach_placement"][t].copy()
+        env._free_placement_of_object0 = lambda yaw0, n=None, t=t: g["reach_placement"][t].copy()
         before = env.sim.qpos[0].clone()
         got = env._goal_positions(np.arange(1), np.zeros((1, 1)))[0]
         assert np.abs(got - g["reach_goal"][t]).max() < 1e-12
