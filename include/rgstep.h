@@ -571,6 +571,8 @@ int ra_post_args_size(void);
  * frozen / solver_active / nticks; `reobserve` is the `frozen` array of a second ra_env_post_step launch (1 = first observation of a new episode, 3 = a live env with
  * a new goal, 2 = skip); `ended` / `stabilised` / `episode_started` are masks for the host's tensor ops on the per-env parameter rows (stabilize_objects' damping,
  * the simulation randomizers).  solver may be NULL (control_mode joint). */
+#define RA_SYNC_FORCED_END 1
+#define RA_SYNC_REGOAL_ONLY 2
 typedef struct ra_recipe_args {
   int num_objects, action_dim;
   int *stage, *left;                             /* [B]: 0 live, 1 stabilise, 2 random action, 3 settle; steps left in the stage */
@@ -641,7 +643,17 @@ typedef struct ra_recipe_args {
   const int* num_objects_next;
   float used_table_portion;
   float park_pose[RA_MAXOBJ][7];
+  /* the synchronous episode API, reset(mask) and reset_goals() (appended; zero-filled = every env, the pipelined stage machine: every path above as it is).
+   * active [B] bytes, NULL = all envs: an env whose byte is 0 is skipped entirely -- the launch writes no row of it (episode_started, reobserve, nticks, stage and left
+   * included).  sync_mode RA_SYNC_FORCED_END: every active env is treated as "its episode ended on this step", whatever its done flag and whatever stage it was in (a
+   * synchronous reset ends a recipe in progress); from there the stage machine runs as above.  RA_SYNC_REGOAL_ONLY: a live env with goal_reset && !done gets its next
+   * goal (the branch above, the reach goals' object move included) and `reobserve` says so; no stage is counted, no episode ends, and stage / left / nticks / ended /
+   * stabilised / episode_started keep what they hold.  In both modes the draws are the ones the pipelined launch makes: the same streams keyed by (seed, step, env, k);
+   * no draw depends on which other envs are active. */
+  const unsigned char* active;
+  int sync_mode;
 } ra_recipe_args;
+/* The launch that follows it on the per-env parameter rows (ra_param_rows_args): declared and described in rgstep_sync_reset.h, which the end of this header includes. */
 int ra_env_recipe_step(rb_batch* main, rb_batch* solver, const ra_recipe_args* args, void* stream);
 int ra_recipe_args_size(void);
 /* ---- the env-level half of RobotEnv.step for the full cube (dactyl/full_perpendicular), one launch after rb_batch_step:
@@ -717,4 +729,5 @@ const char* rg_last_error(void);
 #endif
 #include "rgstep_setconst.h"
 #include "rgstep_icp.h"
+#include "rgstep_sync_reset.h"
 #endif

@@ -129,13 +129,26 @@ def _ra_recipe_fields():
             + [("goal_distance_ratio", _p), ("goal_distance_min", _f), ("pickup_proba", _f), ("stacking_proba", _f)]
             + [("randomize_goal_rot", _i), ("domino_distance_mul", _f)]
             + [("fixed_xy", (_f * 2) * RA_MAXOBJ), ("fixed_yaw", _f * RA_MAXOBJ)]
-            + [("num_active", _p), ("num_objects_next", _p), ("used_table_portion", _f), ("park_pose", (_f * 7) * RA_MAXOBJ)])
+            + [("num_active", _p), ("num_objects_next", _p), ("used_table_portion", _f), ("park_pose", (_f * 7) * RA_MAXOBJ)]
+            + [("active", _p), ("sync_mode", _i)])
 
 
 class RaRecipeArgs(ctypes.Structure):
     """`ra_recipe_args` of include/rgstep.h (field order and types must match; bind() checks the size)."""
 
     _fields_ = _ra_recipe_fields()
+
+
+RA_SYNC_FORCED_END, RA_SYNC_REGOAL_ONLY = 1, 2      # ra_recipe_args.sync_mode
+RA_ROWS_RESTORE, RA_ROWS_PARK = 1, 2                # ra_param_rows_args.stages
+
+
+class RaParamRowsArgs(ctypes.Structure):
+    """`ra_param_rows_args` of include/rgstep_sync_reset.h (field order and types must match; bind() checks the size)."""
+
+    _fields_ = [("ended", ctypes.c_void_p), ("stabilised", ctypes.c_void_p), ("episode_started", ctypes.c_void_p), ("active", ctypes.c_void_p),
+                ("block_default", ctypes.c_void_p), ("num_objects", ctypes.c_int), ("obj_dofadr", ctypes.c_int * RA_MAXOBJ), ("obj_body", ctypes.c_int * RA_MAXOBJ),
+                ("stabilize_damping", ctypes.c_float), ("num_active", ctypes.c_void_p), ("park_damping", ctypes.c_float), ("stages", ctypes.c_int)]
 
 
 # the wrapper stack's two launches (include/rgstep.h rg_wrap_*): the packed row's keys in RG_WK_* order ("_delta": the block of the RandomizedBodyWrapper family's entries)
@@ -193,6 +206,7 @@ EXPORTS = [
 ]
 EXPORTS_SETCONST = ["rb_batch_set_constants"]      # include/rgstep_setconst.h (EXPORTS is what include/rgstep.h itself declares)
 EXPORTS_ICP = ["ra_env_icp", "ra_icp_args_size"]      # include/rgstep_icp.h
+EXPORTS_SYNC_RESET = ["ra_env_param_rows", "ra_param_rows_args_size"]      # include/rgstep_sync_reset.h
 
 
 
@@ -294,6 +308,10 @@ def bind(path):
     L.ra_recipe_args_size.restype = ci
     if L.ra_recipe_args_size() != ctypes.sizeof(RaRecipeArgs):
         raise NativeError("ra_recipe_args layout mismatch between include/rgstep.h and robogym_amd/_native.py")
+    L.ra_env_param_rows.argtypes = [vp, ctypes.POINTER(RaParamRowsArgs), vp]
+    L.ra_param_rows_args_size.restype = ci
+    if L.ra_param_rows_args_size() != ctypes.sizeof(RaParamRowsArgs):
+        raise NativeError("ra_param_rows_args layout mismatch between include/rgstep_sync_reset.h and robogym_amd/_native.py")
     L.rb_env_post_step.argtypes = [vp, ctypes.POINTER(RbPostArgs), vp]
     L.rb_post_args_size.restype = ci
     if L.rb_post_args_size() != ctypes.sizeof(RbPostArgs):

@@ -516,17 +516,21 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
   const int e = blockIdx.x, lane = threadIdx.x;
   if (e >= bt.B) return;
   const int N = a.num_objects, AD = a.action_dim, nq = m.nq;
+  if (a.active && !a.active[e]) return;                                // (uniform over the workgroup: an env outside the launch keeps every row)
+  // the synchronous episode API (ra_recipe_args.sync_mode): a forced end takes the env out of whatever stage it was in and ends its episode whatever `done` says; a
+  // regoal-only launch runs the live env's next-goal branch and neither counts a stage nor ends an episode.  Both draw what the pipelined launch of this `step` draws
+  const bool forced = a.sync_mode == RA_SYNC_FORCED_END, regoal_only = a.sync_mode == RA_SYNC_REGOAL_ONLY;
   if (lane == 0) {
-    int st = a.stage[e], lf = a.left[e];
+    int st = forced ? 0 : a.stage[e], lf = forced ? 0 : a.left[e];
     int started = 0, ended = 0, regoal = 0, stabilised = 0;
     unsigned k = 0;
     auto U = [&]() -> float { return env_u01(a.seed, a.step, (unsigned)e, k++); };
     // per-env object counts: the env's first n objects are in use (latched below when an episode ends); without them n = N and every line is the one it was
     int n = N;
     if (a.num_active) { n = a.num_active[e]; n = n < 1 ? 1 : (n > N ? N : n); }
-    a.episode_started[e] = 0;
+    if (!regoal_only) a.episode_started[e] = 0;
     // ---- an env inside the recipe: this step counted
-    if (st > 0) {
+    if (st > 0 && !regoal_only) {
       lf -= 1;
       if (lf <= 0) {
         if (st == 1) {
@@ -549,7 +553,7 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
       a.hold[e] = 0; a.hold_ctrl[e] = 0; a.frozen[e] = 0; a.solver_active[e] = 1; a.resetting[e] = 0; a.episode_started[e] = 1;
       for (int d = 0; d < AD; d++) { a.scripted[(size_t)e * AD + d] = 0.f; a.ema_value[(size_t)e * AD + d] = 0.f; a.action_ema[(size_t)e * AD + d] = 0.f; }
       gy = a.yaw + (size_t)e * N; gstride = 1;
-    } else if (st == 0 && a.goal_reset[e] && !a.done[e]) {             // a live env that reached its goal: ObjectStateGoal.next_goal keeps the goal's yaw
+    } else if (!forced && st == 0 && a.goal_reset[e] && !a.done[e]) {  // a live env that reached its goal: ObjectStateGoal.next_goal keeps the goal's yaw
       // (not when the episode ends on the same step -- objects off the table while every object sits within its thresholds --: the begin-of-episode state written
       //  below would be what the goal's re-observation reads; the terminal observation keeps the reached goal's entries, on this path and on the host path alike)
       regoal = 1;
@@ -628,7 +632,7 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
       }
     }
     // ---- an episode that ended on this step: its recipe begins (the returned observation / reward / done are the terminal ones)
-    if (!started && st == 0 && a.done[e]) {
+    if (!started && st == 0 && (forced || a.done[e]) && !regoal_only) {
       ended = 1;
       // the count of the episode that begins: RearrangeEnv._reset re-creates the simulation with the current num_objects (common/base.py:850-856, 904)
       if (a.num_active) { n = a.num_objects_next[e]; n = n < 1 ? 1 : (n > N ? N : n); a.num_active[e] = n; }
@@ -666,10 +670,12 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
     // controller ticks of the NEXT step's main-world launch: two for live envs, one inside the recipe, two on the recipe's last step
     // (reach: one on the recipe's last step -- the goal moves the object, the forward of _observe_sync follows it: the host's launch over the reobserve codes)
     const int last_stage = a.n_random_initial_steps >= 1 ? 3 : 1;
-    a.nticks[e] = st > 0 ? ((st == last_stage && lf <= 1 && !(a.goal_kind == 3 || a.goal_kind == 4)) ? 2 : 1) : 2;
-    a.stage[e] = st; a.left[e] = lf;
+    if (!regoal_only) {                                                // (a regoal-only launch leaves stage, left and the next step's launch rows as they are)
+      a.nticks[e] = st > 0 ? ((st == last_stage && lf <= 1 && !(a.goal_kind == 3 || a.goal_kind == 4)) ? 2 : 1) : 2;
+      a.stage[e] = st; a.left[e] = lf;
+      a.ended[e] = (unsigned char)ended; a.stabilised[e] = (unsigned char)stabilised;
+    }
     a.reobserve[e] = started ? 1 : (regoal ? 3 : 2);
-    a.ended[e] = (unsigned char)ended; a.stabilised[e] = (unsigned char)stabilised;
     F.started = started; F.ended = ended; F.regoal = regoal; F.n = n;
   }
   __syncthreads();
@@ -748,6 +754,42 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
       for (int q = 0; q < 3; q++) so[3 + q] = env_u01(a.seed, a.step, (unsigned)e, 500u + 3u * lane + q);
       so[6] = 1.f;
     }
+  }
+}
+
+// The per-env parameter rows after a recipe launch, on the rows of its masks only (ra_param_rows_args, include/rgstep_sync_reset.h): what
+// BatchedBlockRearrangeEnv._advance_recipes_device does with whole-batch tensor ops.  One wave per env; an env outside `active`, or with none of its three mask
+// bytes set, is left after three byte loads.  `blk`: word offset of the parameter block in the scratch row, `words` its length; `damp` / `xfrc` / `mass` / `grav`: the
+// fields' word offsets in the row (RbModelDev.prm_off).  Plain vector stores; every store of a phase goes to a word no other lane writes in that phase.
+__global__ void __launch_bounds__(64) ra_param_rows_kernel(RbBatchDev bt, int scratch_words, int blk, int words, int damp, int xfrc, int mass, int grav, RaParamRowsArgs a) {
+  const int e = blockIdx.x, lane = threadIdx.x;
+  if (e >= bt.B) return;
+  if (a.active && !a.active[e]) return;
+  const int ended = a.ended[e], stabilised = a.stabilised[e], started = a.episode_started[e];
+  if (!(ended | stabilised | started)) return;                         // (all three uniform over the workgroup)
+  float* row = bt.scratch + (size_t)e * scratch_words;
+  const int N = a.num_objects;
+  if (a.stages & RA_ROWS_RESTORE) {
+    // _recreate_sim's fresh model for an episode that ended: the whole block (xfrc_applied among it: zero) back at the model's values
+    if (ended) for (int i = lane; i < words; i += 64) row[blk + i] = a.block_default[i];
+    __syncthreads();
+    // stabilize_objects (common/utils.py:76-92): the objects' dof damping lowered while they settle, the model's own again afterwards
+    if (ended || stabilised)
+      for (int i = lane; i < 6 * N; i += 64) {
+        const int dof = a.obj_dofadr[i / 6] + i % 6;
+        row[damp + dof] = ended ? a.stabilize_damping : a.block_default[damp - blk + dof];
+      }
+    __syncthreads();
+  }
+  if ((a.stages & RA_ROWS_PARK) && a.num_active) {
+    // per-env object counts: an unused object's weight cancelled by a force at its centre of mass, from THIS env's mass and gravity rows, and its dofs damped
+    const int n = a.num_active[e];
+    for (int i = lane; i < 3 * N; i += 64) {
+      const int o = i / 3, c = i % 3, b = a.obj_body[o];
+      if (o >= n) row[xfrc + 6 * b + c] = -row[mass + b] * row[grav + c];
+    }
+    for (int i = lane; i < 6 * N; i += 64)
+      if (i / 6 >= n) row[damp + a.obj_dofadr[i / 6] + i % 6] = a.park_damping;
   }
 }
 

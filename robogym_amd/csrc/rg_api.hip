@@ -10,6 +10,7 @@ typedef rb_post_args RbPostArgs;
 typedef ra_post_args RaPostArgs;
 typedef ra_recipe_args RaRecipeArgs;
 typedef ra_icp_args RaIcpArgs;
+typedef ra_param_rows_args RaParamRowsArgs;
 #define RG_NS rgs
 #define RG_MAXCON 24
 #define RG_CPOOL 768
@@ -1620,6 +1621,7 @@ int ra_env_recipe_step(rb_batch* b, rb_batch* solver, const ra_recipe_args* args
   if (a.group_mode == 1 && !a.obj_group) return fail("ra_env_recipe_step: group_mode 1 needs obj_group");
   if (a.obj_group && (a.goal_kind == 3 || a.goal_kind == 4)) return fail("ra_env_recipe_step: obj_group with a reach goal (one object: nothing to group)");
   if (a.group_mode == 1 && !(a.sample_lam[0] >= 0.f && a.sample_lam[0] <= a.sample_lam[1])) return fail("ra_env_recipe_step: sample_lam is not a range of non-negative rates");
+  if (a.sync_mode < 0 || a.sync_mode > RA_SYNC_REGOAL_ONLY) return fail("ra_env_recipe_step: sync_mode out of range (0 the pipelined stage machine, 1 forced end, 2 regoal only)");
   if (a.num_active) {      // per-env object counts
     if (!a.num_objects_next) return fail("ra_env_recipe_step: num_active needs num_objects_next");
     if (!(a.goal_kind <= 2 || a.goal_kind == 5)) return fail("ra_env_recipe_step: per-env object counts are built for goal kinds 0, 1, 2 and 5");
@@ -1637,6 +1639,30 @@ int ra_env_recipe_step(rb_batch* b, rb_batch* solver, const ra_recipe_args* args
   }
   DeviceGuard g(b->device);
   return launch(rgb::ra_recipe_kernel, b->dev.B, 64, 0, sizeof(rgb::RaRecipeLds), stream, b->model->dev_copy, b->dev, ms, sb, a);
+}
+int ra_param_rows_args_size(void) { return (int)sizeof(ra_param_rows_args); }
+int ra_env_param_rows(rb_batch* b, const ra_param_rows_args* args, void* stream) {
+  if (g_multi) return not_recordable("ra_env_param_rows");
+  if (!b || !args) return fail("null argument");
+  const ra_param_rows_args& a = *args;
+  const RbModelDev& d = b->model->dev;
+  if (!d.prm_on) return fail("ra_env_param_rows: the batch has no per-env parameter rows (rb_model_enable_env_params)");
+  if (!a.ended || !a.stabilised || !a.episode_started || !a.block_default) return fail("ra_env_param_rows: a required array is NULL");
+  if (a.num_objects < 1 || a.num_objects > RA_MAXOBJ) return fail("ra_env_param_rows: num_objects out of range");
+  if (a.stages < 1 || a.stages > (RA_ROWS_RESTORE | RA_ROWS_PARK)) return fail("ra_env_param_rows: stages is RA_ROWS_RESTORE, RA_ROWS_PARK or both");
+  for (int k = 0; k < a.num_objects; k++) {
+    if (a.obj_dofadr[k] < 0 || a.obj_dofadr[k] + 6 > d.nv) return fail("ra_env_param_rows: object dof address out of range");
+    if (a.obj_body[k] <= 0 || a.obj_body[k] >= d.nbody) return fail("ra_env_param_rows: object body id out of range");
+  }
+  if (!(fabsf(a.stabilize_damping) <= 3.0e38f) || !(fabsf(a.park_damping) <= 3.0e38f)) return fail("ra_env_param_rows: damping is not finite");
+  // the block and its fields inside the scratch row: every store of the kernel lands inside [blk, blk + words) of the env's own row
+  const int blk = d.off[RB_O_PRM], words = d.prm_words;
+  const int damp = d.prm_off[RB_P_DOF_DAMPING], xfrc = d.prm_off[RB_P_XFRC], mass = d.prm_off[RB_P_BODY_MASS], grav = d.prm_off[RB_P_GRAVITY];
+  if (blk < 0 || words < 1 || blk + words > d.scratch_words) return fail("ra_env_param_rows: parameter block outside the scratch row");
+  if (damp < blk || damp + d.nv > blk + words || xfrc < blk || xfrc + 6 * d.nbody > blk + words || mass < blk || mass + d.nbody > blk + words || grav < blk || grav + 3 > blk + words)
+    return fail("ra_env_param_rows: a parameter field lies outside the block");
+  DeviceGuard g(b->device);
+  return launch(rgb::ra_param_rows_kernel, b->dev.B, 64, 0, 0, stream, b->dev, d.scratch_words, blk, words, damp, xfrc, mass, grav, a);
 }
 int rb_cube_ops(rb_batch* b, int block_col, const int* cube_tab_dev, const float* ops_dev, int nops, const int* active_dev, void* stream) {
   if (g_multi) return not_recordable("rb_cube_ops");

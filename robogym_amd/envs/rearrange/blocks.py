@@ -355,8 +355,9 @@ class BatchedBlockRearrangeEnv:
         """`per_env_parameters`: every env carries its own copy of the randomisable model fields (`self.sim.params`, LargeModelSimulation(env_params=True)) -- what
         the reference's simulation randomizers and `stabilize_objects` write into `sim.model`.  On by default (measured cost: 0.7 % of the step,
         profiles/r05_ab_rb_env_params.txt); off: the model's own arrays, no randomizers, no damping change while the objects stabilise.
-        `device_reset` (with `pipelined_reset`): the recipe's stage machine, the begin-of-episode state and the placement / goal sampling run in ONE more launch after the
-        env kernel (ra_env_recipe_step, include/rgstep.h) instead of host numpy behind a readback of the done / goal flags: a step call never waits for the GPU.
+        `device_reset`: with `pipelined_reset`, the recipe's stage machine, the begin-of-episode state and the placement / goal sampling run in ONE more launch after the
+        env kernel (ra_env_recipe_step, include/rgstep.h) instead of host numpy behind a readback of the done / goal flags: a step call never waits for the GPU.  Without `pipelined_reset`, `step` is the plain step (finished envs stay done) and the synchronous
+        `reset(mask)` / `reset_goals()` run that recipe on the device (`on_device`; `_reset_device`): the same kernel, the same draw streams, no readback of the mask.
         `randomizer_params`: name -> parameter of `build_simulation_randomizers` (the reference's ADR-controlled values; all zero by default = identity).
         `goal_kind` (GOAL_KINDS): the task's goal generator -- "object_state" (this env's own), "pickandplace" (`height_range`), "stack" (`object_size`, `fixed_order`),
         "reach" / "det-reach" (one object, `target_height`); envs/rearrange/blocks_pickandplace.py, blocks_stack.py, blocks_reach.py and ycb_pickandplace.py set it.
@@ -568,11 +569,10 @@ class BatchedBlockRearrangeEnv:
         # ---- the device recipe: its state and the recipe kernel's arguments
         self.device_reset = bool(device_reset)
         if self.device_reset:
-            if not self.pipelined:
-                raise ValueError("device_reset needs pipelined_reset=True (the synchronous reset() keeps its host recipe)")
             self.stage, self.left, self.yaw, self.placement_failed = z(B, dt=torch.int32), z(B, dt=torch.int32), z(B, N), z(B, dt=torch.int32)
             self.reobserve, self.ended, self.stabilised = torch.full((B,), 2, dtype=torch.uint8, device=dev), z(B, dt=torch.bool), z(B, dt=torch.bool)
             self._fill_recipe_args(starting_seed)
+            self._fill_sync_reset_args()
 
     def _fill_tcp_args(self, max_position_change, arm_reset_controller_error):
         """`self.tcp`, rb_tcp_args of the TCP hook: on the solver world, or (`ideal_arm`) on the env's own world (rb_tcp_args.self_world: TCP pose + denormalised action ->
@@ -726,6 +726,34 @@ class BatchedBlockRearrangeEnv:
             for i in range(N):
                 for k in range(7):
                     r.park_pose[i][k] = float(self.park_pose[i, k])
+
+    def _fill_sync_reset_args(self):
+        """What the synchronous episode API on the device adds to the recipe's arguments (`reset(mask, on_device=True)`, `reset_goals(on_device=True)`): the `active` row
+        of its launches, `self.param_rows` (ra_param_rows_args, include/rgstep_sync_reset.h: the per-env parameter rows on the recipe's masks) and `self.tcp_sync`, the
+        TCP hook's arguments with the recipe's `hold` / `scripted` rows, which a pipelined env's hook has anyway."""
+        dev, B = self.device, self.B
+        self.active_row = torch.zeros(B, dtype=torch.uint8, device=dev)
+        self.param_rows = None
+        if self.per_env_parameters:
+            a = self.param_rows = _native.RaParamRowsArgs()
+            a.ended, a.stabilised, a.episode_started, a.active = _ptr(self.ended), _ptr(self.stabilised), _ptr(self.episode_started), _ptr(self.active_row)
+            self._param_block_default = self._param_block_default.contiguous()
+            a.block_default, a.num_objects = _ptr(self._param_block_default), self.N
+            for i in range(self.N):
+                a.obj_dofadr[i], a.obj_body[i] = self.obj_v[i], self.model.name2id("body", "object%d" % i)
+            a.stabilize_damping, a.park_damping = self.stabilize_object_damping, PARK_DAMPING
+            if self.max_num_objects is not None:
+                a.num_active = _ptr(self.num_active)
+        for rz in self.randomizers:      # (their index tables: uploaded here, not inside a reset that must not wait for the device)
+            rz.prepare(self.sim)
+        self.tcp_sync = None
+        if not self.joint_control:      # (tcp_solver_mode mocap refuses device_reset above: a solver world exists)
+            t = self.tcp_sync = _native.RbTcpArgs()
+            ctypes.memmove(ctypes.byref(t), ctypes.byref(self.tcp_wrapped if self.wrapped else self.tcp), ctypes.sizeof(t))
+            t.hold, t.scripted = self.hold.data_ptr(), self.scripted.data_ptr()
+            self._zero_index = torch.zeros(B, 6, dtype=torch.int32, device=dev)      # (wrapped: the hook wants bin indices; every env of these launches takes its scripted action)
+            if self.wrapped:
+                t.action_index = self._zero_index.data_ptr()
 
     # ------------------------------------------------------------------ launches
     def _stream(self):
@@ -1131,9 +1159,92 @@ class BatchedBlockRearrangeEnv:
         for _ in range(10):
             self.sim.env_step(nforward_ticks=1, active=active)
 
-    def reset(self, mask: Optional[torch.Tensor] = None):
+    def _on_device(self, on_device):
+        """Which recipe `reset` / `reset_goals` run: None = the device recipe exactly when the env was built with `device_reset` and without `pipelined_reset` (every
+        other env keeps the path it had), True needs `device_reset`, False = the host recipe."""
+        if on_device is None:
+            return self.device_reset and not self.pipelined
+        if on_device and not self.device_reset:
+            raise ValueError("on_device=True needs an env built with device_reset=True (the recipe kernel's rows and arguments are made by the constructor)")
+        return bool(on_device)
+
+    def sync_reset_iterations(self):
+        """Launch chains between the forced end and the episode start of a synchronous device reset: the stage machine's own count (ra_recipe_kernel: a stage of zero
+        steps still takes one launch; without a random action there is no settling stage, as in `reset`'s host recipe)"""
+        n = max(int(self.stabilize_steps), 1)
+        if self.n_random_initial_steps >= 1:
+            n += int(self.n_random_initial_steps) + max(int(self.settle_steps), 1)
+        return n
+
+    def _recipe_launch(self):
+        r = self.recipe
+        r.step = (int(r.step) + 1) & 0xFFFFFFFF
+        _native.check(self._L, self._L.ra_env_recipe_step(self.sim._bh, None if self.solver_sim is None else self.solver_sim._bh, ctypes.byref(r), self._stream()), "ra_env_recipe_step")
+
+    def _param_rows_launch(self, stages):
+        self.param_rows.stages = stages
+        _native.check(self._L, self._L.ra_env_param_rows(self.sim._bh, ctypes.byref(self.param_rows), self._stream()), "ra_env_param_rows")
+
+    def _reset_device(self, mask):
+        """`reset(mask)` without the host: one forced-end launch of the recipe kernel for the envs of the mask (ra_recipe_args.sync_mode; whatever recipe they were in
+        ends), then `sync_reset_iterations()` times the pipelined step's launch chain restricted to those envs -- solver world and main world under the rows the recipe
+        kernel maintains (hold / hold_ctrl / scripted / nticks / solver_active), the recipe launch (its `step` counter + 1 per launch: the draw streams of the pipelined
+        recipe), ra_env_param_rows -- and, once the last launch has started the episodes, the randomizers, the reach goals' forward and the env kernel over the
+        `reobserve` codes of those rows.  No readback: the number of iterations is known here, every mask stays on the device."""
+        dev = self.device
+        if mask is None:
+            act = torch.ones(self.B, dtype=torch.bool, device=dev)
+        else:
+            assert mask.shape == (self.B,)
+            if mask.device.type == "cpu" and not bool(mask.any()):      # (a mask that lives on the host: nothing to launch; a device mask is not read back -- its launches skip every env)
+                return self.observe()
+            act = mask.to(device=dev) != 0
+        act32 = act.to(torch.int32)
+        self.active_row.copy_(act)
+        r = self.recipe
+        r.active, r.sync_mode = _ptr(self.active_row), _native.RA_SYNC_FORCED_END
+        both = _native.RA_ROWS_RESTORE | _native.RA_ROWS_PARK
+        try:
+            self._recipe_launch()
+            r.sync_mode = 0
+            if self.param_rows is not None:
+                self._param_rows_launch(both)
+            iterations, stabilising = self.sync_reset_iterations(), max(int(self.stabilize_steps), 1)
+            for it in range(iterations):
+                # the envs of the mask run the stages in lockstep, so the host knows what the recipe's rows hold: `solver_active` is 0 for all of them while the
+                # objects stabilise (no solver world launch: it would skip every env) and 1 afterwards
+                if self.joint_control:      # every env of these launches is inside its recipe: the stored controls while the objects stabilise, then the scripted action
+                    self.sim.env_step(action=self.scripted, nforward_ticks=2, flags=FLAG_FULL_FORWARD, active=act32, nticks=self.nticks, hold=self.hold_ctrl)
+                else:
+                    if it >= stabilising:
+                        self.solver_sim.step_tcp(self.sim, None if self.wrapped else self._zero_action, self.tcp_sync, active=act32)
+                    self.sim.env_step(nforward_ticks=2, flags=FLAG_FULL_FORWARD, active=act32, nticks=self.nticks)
+                self._recipe_launch()
+                if self.param_rows is not None:
+                    self._param_rows_launch(both)
+        finally:
+            r.active, r.sync_mode = None, 0
+        # the last launch started the episodes (the envs of the mask run the stages in lockstep)
+        if self.randomizers:
+            started = self.episode_started & act
+            for rz in self.randomizers:
+                rz.randomize(self.sim, self._rand_gen, started)
+            if self.max_num_objects is not None:      # (gravity and body masses may have changed: the cancelling force follows them)
+                self._param_rows_launch(_native.RA_ROWS_PARK)
+        if self.reach:
+            self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=act32)
+        self._post(frozen=torch.where(act, self.reobserve, torch.full_like(self.reobserve, 2)))
+        self.episode_started.masked_fill_(act, False)      # (as after the host recipe: the flag belongs to the step calls of a pipelined env)
+        self.ended_rows = np.zeros(0, dtype=np.int64)
+        return self.observe()
+
+    def reset(self, mask: Optional[torch.Tensor] = None, on_device: Optional[bool] = None):
         """RobotEnv.reset -> RearrangeEnv._reset (common/base.py:897-932): robot start pose, object rotations + grid placement, stabilisation
-        (100 simulation steps), n_random_initial_steps of one random action then 100 zero-action steps, tracker reset, first goal."""
+        (100 simulation steps), n_random_initial_steps of one random action then 100 zero-action steps, tracker reset, first goal.
+        `on_device` (`_on_device`): the same recipe in ra_recipe_kernel with its draws (`_reset_device`: no readback of the mask, no host sampling) instead of the
+        host recipe below."""
+        if self._on_device(on_device):
+            return self._reset_device(mask)
         rows = np.arange(self.B) if mask is None else np.nonzero(mask.cpu().numpy())[0]
         if len(rows) == 0:
             return self.observe()
@@ -1263,9 +1374,7 @@ class BatchedBlockRearrangeEnv:
         """`_advance_recipes` without the host: the recipe kernel (stage machine, begin-of-episode state, placement and goal sampling), tensor ops on its masks for the
         per-env parameter rows (the block restored for an episode that ended = `_recreate_sim`'s fresh model; stabilize_objects' damping change; the simulation randomizers
         for the envs whose episode starts), and the env kernel once more over the `reobserve` codes (first observation of a new episode / the new goal's entries)."""
-        r = self.recipe
-        r.step = (int(r.step) + 1) & 0xFFFFFFFF
-        _native.check(self._L, self._L.ra_env_recipe_step(self.sim._bh, None if self.solver_sim is None else self.solver_sim._bh, ctypes.byref(r), self._stream()), "ra_env_recipe_step")
+        self._recipe_launch()
         if self.per_env_parameters:
             P = self.sim.params
             # (the block also holds mjData.xfrc_applied, whose default is zero: a re-created simulation starts without applied wrenches, as after mj_resetData)
@@ -1349,8 +1458,20 @@ class BatchedBlockRearrangeEnv:
         reward / done, and -- as `_observe_sync` does through `update_goal_info` -- the success count the next step's goal reward is measured from."""
         self._reobserve(np.arange(self.B) if rows is None else np.asarray(rows), np.zeros(0, dtype=np.int64))
 
-    def reset_goals(self):
-        """`reset_goal` for the envs the tracker flagged (robot_env.py:893-909): a new ObjectStateGoal placement; host sampling."""
+    def reset_goals(self, on_device: Optional[bool] = None):
+        """`reset_goal` for the envs the tracker flagged (robot_env.py:893-909): a new ObjectStateGoal placement; host sampling, or (`on_device`, `_on_device`) one
+        regoal-only launch of the recipe kernel over the live envs with `goal_reset` and not `done`, the reach goals' forward, the env kernel over the `reobserve` codes."""
+        if self._on_device(on_device):
+            r = self.recipe
+            r.active, r.sync_mode = None, _native.RA_SYNC_REGOAL_ONLY
+            try:
+                self._recipe_launch()
+            finally:
+                r.sync_mode = 0
+            if self.reach:
+                self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=(self.reobserve != 2).to(torch.int32))
+            self._post(frozen=self.reobserve)
+            return
         rows = np.nonzero(self.goal_reset.cpu().numpy())[0]
         if len(rows) == 0:
             return

@@ -169,13 +169,18 @@ class GroupedYcbRearrangeEnv:
     def _names(self):
         return [self.object_names[s // self.b] for s in self._slot]
 
-    def reset(self, mask=None):
+    def reset(self, mask=None, on_device=None):
+        """The groups' host recipe (`on_device` None / False).  The synchronous device recipe of the groups (BatchedBlockRearrangeEnv.reset(on_device=True)) is not
+        built for this env: handing the slots out again reads the mask back."""
         import numpy as np
 
+        if on_device:
+            raise NotImplementedError("GroupedYcbRearrangeEnv.reset(on_device=True): the grouped env keeps its host reset (the slot deal of a reset reads the mask back); "
+                                      "on_device=None or False, or BatchedYcbRearrangeEnv for one object set")
         envs = np.arange(self.B) if mask is None else np.nonzero(mask.cpu().numpy())[0]
         self._reassign(envs)                                          # a reset is a new episode: a new object set with it
         smask = None if mask is None else self._to_slots(mask)
-        self._each(lambda i, g: g.reset(None if smask is None else smask[i * self.b:(i + 1) * self.b]))
+        self._each(lambda i, g: g.reset(None if smask is None else smask[i * self.b:(i + 1) * self.b], on_device=False))
         return self._observation()
 
     def step(self, actions):

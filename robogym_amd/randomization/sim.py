@@ -26,6 +26,9 @@ class SimulationRandomizer:
         self.name = name
         self._initial = None
 
+    def prepare(self, sim):
+        """Whatever `randomize` would have to upload from the host, made now: afterwards a call of `randomize` waits for nothing."""
+
     def _field(self, sim) -> torch.Tensor:
         raise NotImplementedError
 
@@ -84,6 +87,19 @@ class GenericSimRandomizer(SimulationRandomizer):
         super().__init__(name)
         self.field_name, self.mode, self.coef, self.ids, self.positive_only = field_name, apply_mode, coef, ids, positive_only
         self.param = np.atleast_1d(np.asarray(param, dtype=np.float64)) * coef
+        self._sel = None
+
+    def _row_mask(self, f):
+        """[rows] bool: the rows `ids` names, on f's device; made once (the upload of a host list waits for the device)"""
+        if self._sel is None or self._sel.device != f.device or self._sel.shape[0] != f.shape[1]:
+            sel = torch.zeros(f.shape[1], dtype=torch.bool, device=f.device)
+            sel[torch.as_tensor(list(self.ids), device=f.device)] = True
+            self._sel = sel
+        return self._sel
+
+    def prepare(self, sim):
+        if self.ids is not None:
+            self._row_mask(sim.params[self.field_name])
 
     def _field(self, sim):
         f = sim.params[self.field_name]
@@ -98,9 +114,7 @@ class GenericSimRandomizer(SimulationRandomizer):
         if self.positive_only:
             new = new.clamp(min=0.0)
         if self.ids is not None:
-            sel = torch.zeros(f.shape[1], dtype=torch.bool, device=f.device)
-            sel[torch.as_tensor(list(self.ids), device=f.device)] = True
-            new = torch.where(sel.reshape((1, -1) + (1,) * (f.dim() - 2)), new, f)
+            new = torch.where(self._row_mask(f).reshape((1, -1) + (1,) * (f.dim() - 2)), new, f)
         if mask is not None:
             new = torch.where(mask.reshape((-1,) + (1,) * (f.dim() - 1)), new, f)
         f.copy_(new)
