@@ -556,6 +556,23 @@ typedef struct ra_post_args {
    * (goals/object_state.py:258-290).  With rot_dist_type 3 the relative rotation is normalize_angles(icp_rel) and the rotation distance the angle of euler2quat of it
    * (goal_distance, :586-599); rot_dist_type 3 without icp_rel is an error.  Kinds 0-2. */
   const float* icp_rel;
+  /* masks of the placement area (appended; mask_obs 0 = none, every path above as it is, obs_dim = 36 N + 23 + 2 nq).  constants.mask_obs_outside_placement_area
+   * (common/base.py:311-374, 415-419): with mask_obs 1 every launch that writes observation entries (frozen 1 and 3 included) evaluates
+   * check_objects_in_placement_area (simulation/base.py:847-902) on the obj_pos it just wrote, against the boundary of extract_placement_area_boundary (:834-845; the
+   * reference caches it per episode, common/base.py:929-932) -- lo.xy = area offset + table_pos - table_size, lo.z = table_pos.z + table_size.z, hi = lo + (area_size,
+   * area_height); with num_active the area of the env's own count (get_placement_area, :980-1010, from used_table_portion; area_offset / area_size are then the area of
+   * num_objects objects) -- max_dist = the largest of max(p - hi, lo - p, 0) over x, y, z; mask = max_dist < mask_margin, or with soft_mask u > clip(max_dist /
+   * mask_margin, 0, 1) with ONE u per env and launch shared by its objects, draw (seed ^ 0xA54FF53Au, step, env, 0): re-observations that carry the same step see the
+   * same mask.  The row grows by 38 N columns behind tcp_torque (obs_dim = 74 N + 23 + 2 nq; reward[3] and done stay at row + obs_dim): placement_mask N |
+   * goal_placement_mask N (goal_in_area [B][N], written with the goal by ra_env_recipe_step or the host, goals/object_state.py:373-378, 403-404) | masked_goal_obj_pos 3N |
+   * masked_goal_obj_rot 3N | masked_rel_goal_obj_pos 3N | masked_rel_goal_obj_rot 3N | masked_obj_pos 3N | masked_obj_rot 3N | masked_obj_rel_pos 3N | masked_obj_vel_pos
+   * 3N | masked_obj_vel_rot 3N | masked_obj_gripper_contact 2N | masked_obj_bbox_size 3N | masked_obj_colors 4N: the goal keys where goal_placement_mask is 1, the object
+   * keys where placement_mask is 1, zero elsewhere.  A padded slot (num_active) has both masks 1 and zero values. */
+  int mask_obs, soft_mask;
+  float mask_margin, area_height;                /* GoalArgs.mask_margin / soft_mask; the third size of get_placement_area (0.26) */
+  float area_offset[2], area_size[2], table_pos[3], table_size[3], used_table_portion;   /* as ra_recipe_args */
+  unsigned seed, step;
+  const float* goal_in_area;                     /* [B][N] 1.0 / 0.0 */
 } ra_post_args;
 int ra_env_post_step(rb_batch* main, rb_batch* solver, const ra_post_args* args, void* stream);
 int ra_post_args_size(void);
@@ -652,6 +669,13 @@ typedef struct ra_recipe_args {
    * no draw depends on which other envs are active. */
   const unsigned char* active;
   int sync_mode;
+  /* the goal's mask of the placement area (appended; goal_in_area NULL = none, every path above as it is).  ObjectStateGoal.next_goal (goals/object_state.py:373-378,
+   * 403-404): wherever the kernel writes goal rows -- a started episode, a regoal, both sync modes -- it writes goal_in_area[e][i] = check_objects_in_placement_area
+   * (simulation/base.py:847-902; the rule of ra_post_args.mask_obs, in the area of the env's count) of the goal position it just wrote, 1.0 for a padded slot.  With
+   * soft_mask one u per env and goal, draw (seed ^ 0x3C6EF372u, step, env, 0): a stream of its own.  The row changes only where the goal does. */
+  float* goal_in_area;                           /* [B][N] */
+  int soft_mask;
+  float mask_margin, area_height;
 } ra_recipe_args;
 /* The launch that follows it on the per-env parameter rows (ra_param_rows_args): declared and described in rgstep_sync_reset.h, which the end of this header includes. */
 int ra_env_recipe_step(rb_batch* main, rb_batch* solver, const ra_recipe_args* args, void* stream);

@@ -97,7 +97,9 @@ def _ra_post_fields():
             + [("obj_group", _p)]
             + [("parallel_quats", _p), ("parallel_quats_180", _p), ("rot_dist_type", _i)]
             + [("num_active", _p), ("max_timesteps_per_goal_per_obj", _i)]
-            + [("icp_rel", _p)])
+            + [("icp_rel", _p)]
+            + [("mask_obs", _i), ("soft_mask", _i), ("mask_margin", _f), ("area_height", _f), ("area_offset", _f * 2), ("area_size", _f * 2), ("table_pos", _f * 3),
+               ("table_size", _f * 3), ("used_table_portion", _f), ("seed", ctypes.c_uint), ("step", ctypes.c_uint), ("goal_in_area", _p)])
 
 
 class RaPostArgs(ctypes.Structure):
@@ -130,7 +132,8 @@ def _ra_recipe_fields():
             + [("randomize_goal_rot", _i), ("domino_distance_mul", _f)]
             + [("fixed_xy", (_f * 2) * RA_MAXOBJ), ("fixed_yaw", _f * RA_MAXOBJ)]
             + [("num_active", _p), ("num_objects_next", _p), ("used_table_portion", _f), ("park_pose", (_f * 7) * RA_MAXOBJ)]
-            + [("active", _p), ("sync_mode", _i)])
+            + [("active", _p), ("sync_mode", _i)]
+            + [("goal_in_area", _p), ("soft_mask", _i), ("mask_margin", _f), ("area_height", _f)])
 
 
 class RaRecipeArgs(ctypes.Structure):

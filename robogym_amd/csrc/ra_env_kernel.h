@@ -12,6 +12,8 @@
 //   _get_goal_info, MultiGoalTracker.process                      robot_env.py:577-625, utils/multi_goal_tracker.py:157-241
 //   JointControlledTcpArm.on_observations_updated                 robot/ur16e/mujoco/joint_controlled_tcp_arm.py:114-129 (gripper state -> solver world)
 //   per-env object counts (num_active: zero padding to max_num_objects) envs/rearrange/simulation/base.py:73-74, 222-224, 1015-1024; common/base.py:751-757, 919-927
+//   masks of the placement area, masked observations (mask_obs)   envs/rearrange/common/base.py:311-374, 415-419, 929-932; simulation/base.py:834-902;
+//                                                                 goals/object_state.py:373-378, 403-404 (the goal's mask: ra_recipe_kernel)
 // Rotation helpers follow robogym/utils/rotation.py (mat2euler, quat2mat, normalize_angles) as rb_env_kernel.h's rbc_* do.
 #pragma once
 #include "rb_env_kernel.h"
@@ -64,6 +66,41 @@ __device__ inline int ra_group_match(const int* grp, const float* xpos, const in
     if (lane == i) mine = j;
   }
   return mine;
+}
+
+// get_placement_area (simulation/base.py:980-1010) of one env: offset from the table's low corner and size.  Without per-env object counts the launch constants.
+// With them the area follows the env's own count n: used_table_portion clipped to [0.1 n, 1], width = 0.5 x table width x portion, height = 0.38 x table depth x
+// portion, centred at (0.5, 0.44) of the table.  An env whose clipped portion is the one the launch constants were made with (n = num_objects among them) reads
+// those, bit for bit.  `Args`: RaRecipeArgs, or RaPostArgs (mask_obs), which carries the same fields.
+struct RaArea { float off[2], size[2]; };
+template <class Args>
+__device__ inline RaArea ra_area(const Args& a, int n) {
+  RaArea A;
+  A.off[0] = a.area_offset[0]; A.off[1] = a.area_offset[1]; A.size[0] = a.area_size[0]; A.size[1] = a.area_size[1];
+  if (a.num_active) {
+    const float p_all = fminf(fmaxf(a.used_table_portion, 0.1f * (float)a.num_objects), 1.f), p = fminf(fmaxf(a.used_table_portion, 0.1f * (float)n), 1.f);
+    if (p != p_all) {
+      const float tsx = 2.f * a.table_size[0], tsy = 2.f * a.table_size[1];
+      A.size[0] = 0.5f * tsx * p; A.size[1] = 0.38f * tsy * p;
+      A.off[0] = 0.5f * tsx - 0.5f * A.size[0]; A.off[1] = 0.44f * tsy - 0.5f * A.size[1];
+    }
+  }
+  return A;
+}
+
+// check_objects_in_placement_area (simulation/base.py:847-902) for one point `p`, the one membership rule of the env kernel (the objects) and the recipe kernel (the
+// goals).  Boundary (extract_placement_area_boundary, :834-845): lo.xy = area offset + table_pos - table_size, lo.z = table_pos.z + table_size.z, hi = lo + (width,
+// height, area_height), in the area `ar` of the env's own count (ra_area: the reference's cached boundary and its on-the-fly one are then the same thing).
+// max_dist = the largest of max(p - hi, lo - p, 0) over x, y, z.  Hard: max_dist < margin.  Soft: u > clip(max_dist / margin, 0, 1), `u` the env's ONE uniform of
+// this call, shared by its objects (the reference draws a scalar).  Returns 1.0 / 0.0.
+template <class Args>
+__device__ inline float ra_in_area(const Args& a, const RaArea& ar, const float* p, bool soft, float u) {
+  const float lo[3] = {ar.off[0] + a.table_pos[0] - a.table_size[0], ar.off[1] + a.table_pos[1] - a.table_size[1], a.table_pos[2] + a.table_size[2]};
+  const float hi[3] = {lo[0] + ar.size[0], lo[1] + ar.size[1], lo[2] + a.area_height};
+  float max_dist = 0.f;
+  for (int k = 0; k < 3; k++) max_dist = fmaxf(max_dist, fmaxf(p[k] - hi[k], lo[k] - p[k]));
+  if (soft) return u > fminf(fmaxf(max_dist / a.mask_margin, 0.f), 1.f) ? 1.f : 0.f;
+  return max_dist < a.mask_margin ? 1.f : 0.f;
 }
 
 __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, RbBatchDev bt, RaPostArgs a) {
@@ -179,6 +216,23 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
     const float* so = a.static_obs + ((size_t)e * N + lane) * 7;
     for (int k = 0; k < 3; k++) o[g0 + 14 * N + 1 + 3 * lane + k] = so[k];
     for (int k = 0; k < 4; k++) o[g0 + 17 * N + 1 + 4 * lane + k] = so[3 + k];
+    if (a.mask_obs) {
+      // _mask_object_observation / _mask_goal_observation (common/base.py:311-374): the object's mask from the obj_pos written above, the goal's as it was frozen with
+      // the goal; the goal keys under the goal's mask, the object keys under the object's -- the value, or zero
+      const float u = a.soft_mask ? env_u01(a.seed ^ 0xA54FF53Au, a.step, (unsigned)e, 0u) : 0.f;
+      const bool pm = ra_in_area(a, ra_area(a, n), xpos + 3 * b, a.soft_mask != 0, u) != 0.f, gm_ = a.goal_in_area[(size_t)e * N + lane] != 0.f;
+      float* q = row + 36 * N + 23 + 2 * nq;
+      q[lane] = pm ? 1.f : 0.f; q[N + lane] = gm_ ? 1.f : 0.f;
+      for (int k = 0; k < 3; k++) {
+        q[2 * N + 3 * lane + k] = gm_ ? gp[k] : 0.f; q[5 * N + 3 * lane + k] = gm_ ? a.goal_rot[((size_t)e * N + lane) * 3 + k] : 0.f;
+        q[8 * N + 3 * lane + k] = gm_ ? (k == 0 ? rx : (k == 1 ? ry : rz)) : 0.f; q[11 * N + 3 * lane + k] = gm_ ? rel[k] : 0.f;
+        q[14 * N + 3 * lane + k] = pm ? xpos[3 * b + k] : 0.f; q[17 * N + 3 * lane + k] = pm ? eul[k] : 0.f; q[20 * N + 3 * lane + k] = pm ? xpos[3 * b + k] - tcp[k] : 0.f;
+        q[23 * N + 3 * lane + k] = pm ? vp[k] - tcp_vp[k] : 0.f; q[26 * N + 3 * lane + k] = pm ? vr[k] : 0.f;
+        q[31 * N + 3 * lane + k] = pm ? so[k] : 0.f;
+      }
+      q[29 * N + 2 * lane] = pm ? cl : 0.f; q[29 * N + 2 * lane + 1] = pm ? cr : 0.f;
+      for (int k = 0; k < 4; k++) q[34 * N + 4 * lane + k] = pm ? so[3 + k] : 0.f;
+    }
   } else if (lane < N) {      // a padded slot: zeros (simulation/base.py:222-224, 1015-1024; goals/object_state.py:556-580)
     float* o = row;
     const int g0 = 15 * N + 15 + 2 * nq;
@@ -189,6 +243,14 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
     }
     o[g0 + 12 * N + 1 + 2 * lane] = 0.f; o[g0 + 12 * N + 1 + 2 * lane + 1] = 0.f;
     for (int k = 0; k < 4; k++) o[g0 + 17 * N + 1 + 4 * lane + k] = 0.f;
+    if (a.mask_obs) {         // both masks 1.0 (the reference pads them with True, simulation/base.py:893-897), the masked values zero
+      float* q = row + 36 * N + 23 + 2 * nq;
+      q[lane] = 1.f; q[N + lane] = 1.f;
+      for (int c = 2; c < 29; c += 3) for (int k = 0; k < 3; k++) q[c * N + 3 * lane + k] = 0.f;      // the nine 3N keys in front of the contacts
+      q[29 * N + 2 * lane] = 0.f; q[29 * N + 2 * lane + 1] = 0.f;
+      for (int k = 0; k < 3; k++) q[31 * N + 3 * lane + k] = 0.f;
+      for (int k = 0; k < 4; k++) q[34 * N + 4 * lane + k] = 0.f;
+    }
   }
   const unsigned long long okmask = __ballot(ok_obj), offmask = __ballot(off_obj);
   const int nsucc = __popcll(okmask), any_off = offmask != 0;
@@ -312,25 +374,6 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
 //   place_targets_with_fixed_position                              envs/rearrange/common/utils.py:884-919 (ObjectFixedStateGoal, goals/object_state_fixed.py)
 //   AttachedBlockStateGoal                                         envs/rearrange/goals/attached_block_state.py:17-68
 struct RaRecipeLds { int started, ended, regoal, moved; float pos[RA_MAXOBJ][3], gpos[RA_MAXOBJ][3], gyaw[RA_MAXOBJ], opos[3]; int n; };
-
-// get_placement_area (simulation/base.py:980-1010) of one env: offset from the table's low corner and size.  Without per-env object counts the launch constants.
-// With them the area follows the env's own count n: used_table_portion clipped to [0.1 n, 1], width = 0.5 x table width x portion, height = 0.38 x table depth x
-// portion, centred at (0.5, 0.44) of the table.  An env whose clipped portion is the one the launch constants were made with (n = num_objects among them) reads
-// those, bit for bit.
-struct RaArea { float off[2], size[2]; };
-__device__ inline RaArea ra_area(const RaRecipeArgs& a, int n) {
-  RaArea A;
-  A.off[0] = a.area_offset[0]; A.off[1] = a.area_offset[1]; A.size[0] = a.area_size[0]; A.size[1] = a.area_size[1];
-  if (a.num_active) {
-    const float p_all = fminf(fmaxf(a.used_table_portion, 0.1f * (float)a.num_objects), 1.f), p = fminf(fmaxf(a.used_table_portion, 0.1f * (float)n), 1.f);
-    if (p != p_all) {
-      const float tsx = 2.f * a.table_size[0], tsy = 2.f * a.table_size[1];
-      A.size[0] = 0.5f * tsx * p; A.size[1] = 0.38f * tsy * p;
-      A.off[0] = 0.5f * tsx - 0.5f * A.size[0]; A.off[1] = 0.44f * tsy - 0.5f * A.size[1];
-    }
-  }
-  return A;
-}
 
 // One placement of the first N objects (rotated about z by yaw[i]) inside the placement area: body origins in world coordinates.  Returns false when the rejection
 // sampling ran out of restarts (out = its last proposal).  `k`: this env's running draw index.  `no_grid`: place_objects_with_no_constraint even where the grid
@@ -696,6 +739,11 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
       for (int c = 0; c < 7; c++) g[c] = c == 3 ? 1.f : 0.f;
       float* gr = a.goal_rot + ((size_t)e * N + lane) * 3;
       gr[0] = 0.f; gr[1] = 0.f; gr[2] = 0.f;
+    }
+    // the goal's mask of the placement area (goals/object_state.py:373-378): from the position written above, frozen until the next goal; a padded slot reads 1
+    if (a.goal_in_area && lane < N) {
+      const float u = a.soft_mask ? env_u01(a.seed ^ 0x3C6EF372u, a.step, (unsigned)e, 0u) : 0.f;
+      a.goal_in_area[(size_t)e * N + lane] = lane < n ? ra_in_area(a, ra_area(a, n), F.gpos[lane], a.soft_mask != 0, u) : 1.f;
     }
     for (int i = lane; i < nq; i += 64) {
       float v = bt.qpos[(size_t)e * nq + i];

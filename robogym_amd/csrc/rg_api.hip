@@ -1537,7 +1537,14 @@ int ra_env_post_step(rb_batch* b, rb_batch* solver, const ra_post_args* args, vo
       !a.static_obs || !a.reward || !a.goal_dist || !a.done || !a.goal_reset || !a.trial_success || !a.sub_goal_ok || !a.env_crash || !a.objects_off_table || !a.info_ssl)
     return fail("ra_env_post_step: a required array is NULL");
   if (a.num_objects < 1 || a.num_objects > RA_MAXOBJ) return fail("ra_env_post_step: num_objects out of range");
-  if (a.obs_dim != 36 * a.num_objects + 23 + 2 * d.nq) return fail("ra_env_post_step: obs_dim does not match the row layout");
+  if (a.mask_obs < 0 || a.mask_obs > 1 || a.soft_mask < 0 || a.soft_mask > 1) return fail("ra_env_post_step: mask_obs and soft_mask are 0 or 1");
+  if (a.obs_dim != (a.mask_obs ? 74 : 36) * a.num_objects + 23 + 2 * d.nq) return fail("ra_env_post_step: obs_dim does not match the row layout (36 N + 23 + 2 nq; 74 N + 23 + 2 nq with mask_obs)");
+  if (a.mask_obs) {      // masks of the placement area
+    if (!a.goal_in_area) return fail("ra_env_post_step: mask_obs needs goal_in_area");
+    if (!(a.area_size[0] > 0.f) || !(a.area_size[1] > 0.f) || !(a.area_height > 0.f)) return fail("ra_env_post_step: mask_obs needs a placement area (area_size, area_height > 0)");
+    if (a.soft_mask && !(a.mask_margin > 0.f)) return fail("ra_env_post_step: soft_mask needs mask_margin > 0");
+    if (a.num_active && (!(a.used_table_portion > 0.f) || !(a.used_table_portion <= 1.0e6f))) return fail("ra_env_post_step: mask_obs with num_active needs used_table_portion > 0");
+  }
   if (d.nsensordata < 1 || a.force_adr < 0 || a.force_adr + 3 > d.nsensordata || a.torque_adr < 0 || a.torque_adr + 3 > d.nsensordata) return fail("ra_env_post_step: sensor address out of range");
   for (int k = 0; k < a.num_objects; k++) if (a.obj_body[k] <= 0 || a.obj_body[k] >= d.nbody) return fail("ra_env_post_step: object body id out of range");
   if (a.tcp_body <= 0 || a.tcp_body >= d.nbody || a.grip_act < 0 || a.grip_act >= d.nu || a.grip_qposadr < 0 || a.grip_qposadr >= d.nq || a.grip_dofadr < 0 || a.grip_dofadr >= d.nv)
@@ -1622,6 +1629,11 @@ int ra_env_recipe_step(rb_batch* b, rb_batch* solver, const ra_recipe_args* args
   if (a.obj_group && (a.goal_kind == 3 || a.goal_kind == 4)) return fail("ra_env_recipe_step: obj_group with a reach goal (one object: nothing to group)");
   if (a.group_mode == 1 && !(a.sample_lam[0] >= 0.f && a.sample_lam[0] <= a.sample_lam[1])) return fail("ra_env_recipe_step: sample_lam is not a range of non-negative rates");
   if (a.sync_mode < 0 || a.sync_mode > RA_SYNC_REGOAL_ONLY) return fail("ra_env_recipe_step: sync_mode out of range (0 the pipelined stage machine, 1 forced end, 2 regoal only)");
+  if (a.goal_in_area) {      // the goal's mask of the placement area
+    if (a.soft_mask < 0 || a.soft_mask > 1) return fail("ra_env_recipe_step: soft_mask is 0 or 1");
+    if (!(a.area_height > 0.f)) return fail("ra_env_recipe_step: goal_in_area needs area_height > 0");
+    if (a.soft_mask && !(a.mask_margin > 0.f)) return fail("ra_env_recipe_step: soft_mask needs mask_margin > 0");
+  }
   if (a.num_active) {      // per-env object counts
     if (!a.num_objects_next) return fail("ra_env_recipe_step: num_active needs num_objects_next");
     if (!(a.goal_kind <= 2 || a.goal_kind == 5)) return fail("ra_env_recipe_step: per-env object counts are built for goal kinds 0, 1, 2 and 5");

@@ -34,7 +34,12 @@ Per-env object counts (`max_num_objects`; the reference's `simulation_params.max
 common/base.py:850-856, 919-927): the batch's world is the M-block world, env e uses its first `num_active[e]` blocks, `num_objects_next` is the device row a curriculum
 writes, latched at every episode start; unused blocks are parked.
 
-Not built for this env: vision, `teleport_to_goal`, masks of the placement area, per-group materials / colours / scales.
+Masks of the placement area (`mask_obs_outside_placement_area`; the reference's `constants.mask_obs_outside_placement_area` with `goal_args.soft_mask` /
+`mask_margin`, common/base.py:311-374, simulation/base.py:834-902, goals/object_state.py:373-378): opt-in; the env kernel appends `placement_mask`,
+`goal_placement_mask` and the twelve `masked_*` keys to the packed row (MASK_OBS_KEYS), the goal's mask is written with the goal and stays until the next one
+(DESIGN.md section 3.6c).
+
+Not built for this env: vision, `teleport_to_goal`, per-group materials / colours / scales.
 """
 import ctypes
 from typing import Optional
@@ -78,6 +83,21 @@ OBS_KEYS = [("obj_pos", "N3"), ("obj_rel_pos", "N3"), ("obj_vel_pos", "N3"), ("o
             ("gripper_velp", 3), ("gripper_controls", 1), ("gripper_qpos", 1), ("gripper_vel", 1), ("qpos", "nq"), ("qpos_goal", "nq"), ("goal_obj_pos", "N3"),
             ("goal_obj_rot", "N3"), ("is_goal_achieved", 1), ("rel_goal_obj_pos", "N3"), ("rel_goal_obj_rot", "N3"), ("obj_gripper_contact", "N2"), ("obj_bbox_size", "N3"),
             ("obj_colors", "N4"), ("safety_stop", 1), ("tcp_force", 3), ("tcp_torque", 3)]
+#: what `mask_obs_outside_placement_area` appends to the row (common/base.py:311-374), in the env kernel's order: 38 N columns
+MASK_OBS_KEYS = [("placement_mask", "N1"), ("goal_placement_mask", "N1"), ("masked_goal_obj_pos", "N3"), ("masked_goal_obj_rot", "N3"), ("masked_rel_goal_obj_pos", "N3"),
+                 ("masked_rel_goal_obj_rot", "N3"), ("masked_obj_pos", "N3"), ("masked_obj_rot", "N3"), ("masked_obj_rel_pos", "N3"), ("masked_obj_vel_pos", "N3"),
+                 ("masked_obj_vel_rot", "N3"), ("masked_obj_gripper_contact", "N2"), ("masked_obj_bbox_size", "N3"), ("masked_obj_colors", "N4")]
+#: the third size of `get_placement_area` (simulation/base.py:1002)
+PLACEMENT_AREA_HEIGHT = 0.26
+
+
+def objects_in_placement_area(pos, lo, hi, margin=0.02, soft=False, u=None):
+    """`check_objects_in_placement_area` (simulation/base.py:847-902) for points `pos` [.., 3] against the boundary `lo`, `hi` [3] (or [.., 1, 3] per env): max_dist =
+    the largest of max(p - hi, lo - p, 0) over x, y, z; hard: max_dist < margin; soft: u > clip(max_dist / margin, 0, 1) with ONE `u` per env (a scalar, or [.., 1]).
+    Host numpy, the goal's mask of the host route; ra_in_area (csrc/ra_env_kernel.h) is the same rule on the device.  -> bool [..]"""
+    pos = np.asarray(pos, dtype=np.float64)
+    max_dist = np.maximum(np.maximum(pos - hi, lo - pos), 0.0).max(-1)
+    return (u > np.clip(max_dist / margin, 0.0, 1.0)) if soft else (max_dist < margin)
 
 
 def euler2quat(e):
@@ -351,7 +371,7 @@ class BatchedBlockRearrangeEnv:
                  object_groups="distinct", sample_lam=SAMPLE_LAM, goal_distance_ratio=1.0, goal_distance_min: float = 0.06, pickup_proba: float = 0.0,
                  stacking_proba: float = 0.0, rot_dist_type: str = "full", randomize_goal_rot: bool = False, model=None, domino_distance_mul: float = 4.0,
                  relative_placements=None, init_quats=None, max_num_objects: Optional[int] = None, icp_max_num_vertices: int = 500, icp_error_threshold: float = 0.15,
-                 icp_use_bbox_precheck: bool = False):
+                 icp_use_bbox_precheck: bool = False, mask_obs_outside_placement_area: bool = False, soft_mask: bool = False, mask_margin: float = 0.02):
         """`per_env_parameters`: every env carries its own copy of the randomisable model fields (`self.sim.params`, LargeModelSimulation(env_params=True)) -- what
         the reference's simulation randomizers and `stabilize_objects` write into `sim.model`.  On by default (measured cost: 0.7 % of the step,
         profiles/r05_ab_rb_env_params.txt); off: the model's own arrays, no randomizers, no damping change while the objects stabilise.
@@ -388,8 +408,17 @@ class BatchedBlockRearrangeEnv:
         test, finger contacts, group matching, time-out (`max_timesteps_per_goal_per_obj * n`), placements and the placement area (`placement_area(n)`) follow the env's
         count.  An unused object is parked at `self.park_pose[i]`, its weight cancelled through the env's `xfrc_applied` row and its dof damping raised
         (`_apply_parking`); rb_step_kernel steps it like any other body.  Goal kinds object_state, pickandplace, stack and train; object_groups
-        "distinct" / "single" / "sample"."""
+        "distinct" / "single" / "sample".
+        `mask_obs_outside_placement_area` (the reference's constant of that name; `soft_mask`, `mask_margin`: GoalArgs): the env kernel appends `placement_mask` and
+        `goal_placement_mask` [B, N, 1] and a `masked_` copy of the twelve per-object keys, zero for objects (goals) outside the placement area, to every observation it
+        writes (MASK_OBS_KEYS; `obs_dim` = 74 N + 23 + 2 nq).  Outside: max over x, y, z of the distance to the area's box (`placement_area_boundary`, of the env's own
+        object count) >= `mask_margin`; with `soft_mask` inside with probability 1 - clip(distance / margin, 0, 1), one draw per env and step shared by its objects.  The
+        goal's mask (`self.goal_in_area` [B, N] floats; `goal_objects_in_placement_area`, `goal_in_placement_area`) is made with the goal -- ra_recipe_kernel or
+        `_write_goal` -- and keeps its value until the next goal; unused slots read 1.  Off (default): no row, no pointer, no draw, the 24 keys."""
         self.B, self.N = int(batch_size), int(num_objects)
+        self.mask_obs, self.soft_mask, self.mask_margin = bool(mask_obs_outside_placement_area), bool(soft_mask), float(mask_margin)
+        if self.soft_mask and not self.mask_margin > 0:
+            raise ValueError("soft_mask=True needs mask_margin > 0 (the probability is clip(distance / mask_margin, 0, 1)), got mask_margin=%r" % (mask_margin,))
         self.max_num_objects = None if max_num_objects is None else int(max_num_objects)
         if self.max_num_objects is not None:
             M = self.max_num_objects
@@ -495,7 +524,9 @@ class BatchedBlockRearrangeEnv:
         self.grip_q = int(A["jnt_qposadr"][jn.index("robot0:r_gripper_RJ0_outer")])
         self.grip_act = main.names["actuator"].index("robot0:r_gripper_finger_joint")
         self.nq, self.nu = self.sim.nq, self.sim.nu
-        self.obs_dim = 36 * self.N + 23 + 2 * self.nq
+        self.base_obs_dim = 36 * self.N + 23 + 2 * self.nq
+        self.obs_dim = self.base_obs_dim + (38 * self.N if self.mask_obs else 0)
+        self.obs_keys = OBS_KEYS + (MASK_OBS_KEYS if self.mask_obs else [])
         tb, tg = main.name2id("body", "table"), main.names["geom"].index("table")
         self.table_pos, self.table_size = A["body_pos"][tb].copy(), A["geom_size"][tg].copy()
         self.table_height = float(self.table_pos[2] + self.table_size[2])
@@ -514,6 +545,8 @@ class BatchedBlockRearrangeEnv:
         self.done, self.goal_reset, self.trial_success, self.sub_goal_ok, self.env_crash, self.objects_off_table = (z(B, dt=torch.bool) for _ in range(6))
         self.info_ssl = z(B, dt=torch.int32)
         self.goal[:, :, 3] = 1.0
+        self.goal_in_area = torch.ones(B, N, dtype=torch.float32, device=dev) if self.mask_obs else None      # (until the first goal is made: as the padded slots)
+        self._mask_step = 0           # ra_post_args.step: + 1 per step() / reset(); the re-observations in between carry the same value
         self.obj_group = None
         if self.group_mode != "distinct":      # ("sample": all distinct until the first reset draws the rows)
             ids = group_ids(self.group_counts if self.group_mode == "fixed" else [1] * N)
@@ -542,7 +575,7 @@ class BatchedBlockRearrangeEnv:
         # ---- the arguments of the TCP hook, the env kernel and, for rot_dist_type icp, the launch in front of it
         self._fill_tcp_args(max_position_change, arm_reset_controller_error)
         self._fill_post_args(dict(success_threshold or {"obj_pos": 0.04, "obj_rot": 0.2}), dict(penalty or dict(table_collision=0.0, objects_off_table=1.0, wrist_collision=0.0)),
-                             goal_reward_per_object, success_reward, max_timesteps_per_goal_per_obj, successes_needed, use_goal_distance_reward, reward_clip)
+                             goal_reward_per_object, success_reward, max_timesteps_per_goal_per_obj, successes_needed, use_goal_distance_reward, reward_clip, starting_seed)
         self.icp = self.icp_rel = self.icp_clouds = None
         if rot_dist_type == "icp":
             self._fill_icp_args()
@@ -609,7 +642,7 @@ class BatchedBlockRearrangeEnv:
             self.solver_grip_q = int(solver.arrays["jnt_qposadr"][wj.index("robot0:r_gripper_RJ0_outer")])
             self.solver_grip_act = solver.names["actuator"].index("robot0:r_gripper_finger_joint")
 
-    def _fill_post_args(self, st, pen, goal_reward_per_object, success_reward, max_timesteps_per_goal_per_obj, successes_needed, use_goal_distance_reward, reward_clip):
+    def _fill_post_args(self, st, pen, goal_reward_per_object, success_reward, max_timesteps_per_goal_per_obj, successes_needed, use_goal_distance_reward, reward_clip, starting_seed=0):
         """`self.post`, ra_post_args of the env kernel (csrc/ra_env_kernel.h): the env-level rows, where the robot, the objects and the table are in the main world, the
         thresholds `st`, the rewards and the penalties `pen`"""
         main, N = self.model, self.N
@@ -664,6 +697,13 @@ class BatchedBlockRearrangeEnv:
             a.reward_clip = float(reward_clip)
         if self.pipelined:
             a.frozen = self.frozen.data_ptr()
+        if self.mask_obs:
+            a.mask_obs, a.soft_mask, a.mask_margin, a.area_height, a.goal_in_area = 1, int(self.soft_mask), self.mask_margin, PLACEMENT_AREA_HEIGHT, _ptr(self.goal_in_area)
+            (off_x, off_y, _), (width, height, _) = self.placement_area(N)
+            a.area_offset[0], a.area_offset[1], a.area_size[0], a.area_size[1], a.used_table_portion = float(off_x), float(off_y), float(width), float(height), float(self.used_table_portion)
+            for k in range(3):
+                a.table_pos[k], a.table_size[k] = float(self.table_pos[k]), float(self.table_size[k])
+            a.seed, a.step = (int(starting_seed) * 2654435761 + 40503) & 0xFFFFFFFF, 0
 
     def _fill_icp_args(self):
         """rot_dist_type icp: the clouds (constant, per object), the angles ra_env_icp leaves for the env kernel, and `self.icp`, its arguments"""
@@ -726,6 +766,8 @@ class BatchedBlockRearrangeEnv:
             for i in range(N):
                 for k in range(7):
                     r.park_pose[i][k] = float(self.park_pose[i, k])
+        if self.mask_obs:
+            r.goal_in_area, r.soft_mask, r.mask_margin, r.area_height = _ptr(self.goal_in_area), int(self.soft_mask), self.mask_margin, PLACEMENT_AREA_HEIGHT
 
     def _fill_sync_reset_args(self):
         """What the synchronous episode API on the device adds to the recipe's arguments (`reset(mask, on_device=True)`, `reset_goals(on_device=True)`): the `active` row
@@ -853,12 +895,36 @@ class BatchedBlockRearrangeEnv:
             else:
                 assert actions.dtype == torch.float32 and actions.is_contiguous()
             self._phase_actions = actions
+        if phase in (None, "post"):
+            self._next_mask_step()
         if phase == "post":
             return self._post()
         sa = self.solver_active if self.pipelined else None
         self._physics(self._phase_actions, wrapped=self.wrapped, solver_active=sa, phase=phase)
         if phase is None:
             self._post()
+
+    def _next_mask_step(self):
+        """A new step() or reset(): the soft mask of the objects draws again (ra_post_args.step; the re-observations that follow carry the same value)"""
+        if self.mask_obs:
+            self._mask_step = (self._mask_step + 1) & 0xFFFFFFFF
+            self.post.step = self._mask_step
+
+    @property
+    def goal_objects_in_placement_area(self):
+        """[B, N] bool: the goal dict's `goal_objects_in_placement_area` (goals/object_state.py:404), an op on the device row; None without the masks"""
+        return None if self.goal_in_area is None else self.goal_in_area != 0
+
+    @property
+    def goal_in_placement_area(self):
+        """[B] bool: the goal dict's `goal_in_placement_area` (goals/object_state.py:403); None without the masks"""
+        return None if self.goal_in_area is None else (self.goal_in_area != 0).all(dim=1)
+
+    def placement_area_boundary(self, n=None):
+        """`extract_placement_area_boundary` (simulation/base.py:834-845) for an env that uses `n` objects: (lo [3], hi [3]) of the placement area's box in world coordinates"""
+        offset, size = self.placement_area(n)
+        lo = np.asarray(offset, dtype=np.float64) + self.table_pos - self.table_size
+        return lo, lo + np.asarray(size, dtype=np.float64)
 
     def _step_finish(self):
         if self.pipelined and self.device_reset:
@@ -876,11 +942,11 @@ class BatchedBlockRearrangeEnv:
         return out
 
     def observe(self, packed=None, action_ema=None):
-        """Views into the packed row, keys / shapes of `RearrangeEnv._observe_simple` (common/base.py:376-421).  (`packed` / `action_ema`: rows of several envs
-        put together by the caller, envs/rearrange/ycb.py.)"""
+        """Views into the packed row, keys / shapes of `RearrangeEnv._observe_simple` (common/base.py:376-421), with `mask_obs_outside_placement_area` followed by
+        MASK_OBS_KEYS (the two masks as [B, N, 1]).  (`packed` / `action_ema`: rows of several envs put together by the caller, envs/rearrange/ycb.py.)"""
         out, o, N = {}, 0, self.N
         packed = self.packed if packed is None else packed
-        for k, w in OBS_KEYS:
+        for k, w in self.obs_keys:
             if isinstance(w, str):
                 n = self.nq if w == "nq" else N * int(w[1])
                 v = packed[:, o:o + n]
@@ -1092,6 +1158,14 @@ class BatchedBlockRearrangeEnv:
         g[unused] = np.array([0, 0, 0, 1, 0, 0, 0], dtype=np.float32)
         self.goal[idx] = torch.tensor(g, device=dev)
         self.prev_valid[idx] = 0
+        if self.mask_obs and len(rows):
+            # the goal's mask of the placement area (goals/object_state.py:373-378), from the goal rows as written, in the area of each env's count; an unused slot
+            # reads 1.  soft_mask: one draw per env, after the positions' draws (the reference's np.random.random() inside check_objects_in_placement_area)
+            bounds = [self.placement_area_boundary(int(c)) for c in self._counts(rows)]
+            lo, hi = np.array([b[0] for b in bounds])[:, None, :], np.array([b[1] for b in bounds])[:, None, :]
+            u = self._rng.random(len(rows))[:, None] if self.soft_mask else None
+            inside = objects_in_placement_area(g[..., :3], lo, hi, self.mask_margin, self.soft_mask, u) | unused
+            self.goal_in_area[idx] = torch.tensor(inside.astype(np.float32), device=dev)
 
     def _begin_episode_state(self, rows, idx):
         """What RearrangeEnv._reset writes before anything is simulated (common/base.py:897-932): both worlds as freshly made, the arm's start pose, object
@@ -1243,6 +1317,7 @@ class BatchedBlockRearrangeEnv:
         (100 simulation steps), n_random_initial_steps of one random action then 100 zero-action steps, tracker reset, first goal.
         `on_device` (`_on_device`): the same recipe in ra_recipe_kernel with its draws (`_reset_device`: no readback of the mask, no host sampling) instead of the
         host recipe below."""
+        self._next_mask_step()
         if self._on_device(on_device):
             return self._reset_device(mask)
         rows = np.arange(self.B) if mask is None else np.nonzero(mask.cpu().numpy())[0]
@@ -1542,7 +1617,7 @@ SUPPORTED_PARAMETERS = {"simulation_params", "robot_control_params", "n_random_i
 SUPPORTED_SIMULATION_PARAMS = {"num_objects", "max_num_objects", "penalty", "used_table_portion", "object_groups", "goal_distance_ratio", "goal_distance_min"}
 SUPPORTED_ROBOT_CONTROL_PARAMS = {"max_position_change", "arm_reset_controller_error", "control_mode", "tcp_solver_mode"}
 SUPPORTED_CONSTANTS = {"success_threshold", "successes_needed", "success_reward", "max_timesteps_per_goal_per_obj", "n_action_bins", "action_spacing", "use_goal_distance_reward",
-                       "goal_reward_per_object", "normalize_mesh", "randomize", "sample_lam_low", "sample_lam_high"}
+                       "goal_reward_per_object", "normalize_mesh", "randomize", "sample_lam_low", "sample_lam_high", "mask_obs_outside_placement_area"}
 
 
 def _control_mode_name(mode) -> str:
@@ -1583,10 +1658,11 @@ def goal_rot_args(goal_args, where="constants.goal_args", other=(), icp=False):
     `icp_max_num_vertices`, `icp_error_threshold`, `icp_use_bbox_precheck`.  The last is accepted and has NO effect: the precheck compares current_state["bounding_box"]
     with goal_state["bounding_box"], and the reference fills BOTH from get_target_bounding_boxes_in_table_coordinates (goals/object_state.py:420-425 and 483-488) -- the
     IoU is 1 > 0.75, the ICP always runs.  `icp=True` (ycb.make_env) lets rot_dist_type "icp" and its three keys through; the block envs' surfaces keep refusing them by name.
+    `soft_mask` / `mask_margin` (:159-161; the placement-area masks, acting with constants.mask_obs_outside_placement_area) pass through under their own names.
     A key outside these and `other` raises, named."""
     goal_args = dict(goal_args or {})
     icp_keys = ("icp_max_num_vertices", "icp_error_threshold", "icp_use_bbox_precheck")
-    known = {"rot_dist_type", "randomize_goal_rot", "rot_randomize_type"} | set(other) | (set(icp_keys) if icp else set())
+    known = {"rot_dist_type", "randomize_goal_rot", "rot_randomize_type", "soft_mask", "mask_margin"} | set(other) | (set(icp_keys) if icp else set())
     unknown = sorted(set(goal_args) - known)
     if unknown:
         raise NotImplementedError("%s: %s not implemented by the batched rearrange env (supported: %s)" % (where, ", ".join(unknown), ", ".join(sorted(known))))
@@ -1603,6 +1679,10 @@ def goal_rot_args(goal_args, where="constants.goal_args", other=(), icp=False):
         raise NotImplementedError("%s.rot_randomize_type %r is not implemented by the batched rearrange env (z_axis)" % (where, goal_args["rot_randomize_type"]))
     if "randomize_goal_rot" in goal_args:
         out["randomize_goal_rot"] = bool(goal_args["randomize_goal_rot"])
+    if "soft_mask" in goal_args:      # the placement-area masks' two keys (they act with constants.mask_obs_outside_placement_area)
+        out["soft_mask"] = bool(goal_args["soft_mask"])
+    if "mask_margin" in goal_args:
+        out["mask_margin"] = float(goal_args["mask_margin"])
     return out
 
 
@@ -1619,7 +1699,8 @@ def group_args(sp, constants):
 def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants=None, starting_seed: int = 0, apply_wrappers: bool = True, **kw):
     """`BlockRearrangeEnv.build` surface (robot_env.py:1081-1089) for the batched env; `apply_wrappers` (default True, as in the reference) = the rearrange
     wrapper stack of common/base.py:986-996 (MultiDiscrete actions of `constants.n_action_bins` = 11 bins, action smoothing, reward clipping).  `parameters` / `constants` accept the subset this env
-    implements (`SUPPORTED_*` below, and `constants.goal_args` {rot_dist_type, randomize_goal_rot, rot_randomize_type}: `goal_rot_args`); any other name raises NotImplementedError."""
+    implements (`SUPPORTED_*` below, and `constants.goal_args` {rot_dist_type, randomize_goal_rot, rot_randomize_type, soft_mask, mask_margin}: `goal_rot_args`); any other
+    name raises NotImplementedError.  `constants.mask_obs_outside_placement_area`: the masks of the placement area and the masked observation keys (MASK_OBS_KEYS)."""
     parameters, constants = dict(parameters or {}), dict(constants or {})
     sp, rc = dict(parameters.get("simulation_params", {})), dict(parameters.get("robot_control_params", {}))
     rot_args = goal_rot_args(constants.pop("goal_args", None))      # constants.goal_args: rot_dist_type, randomize_goal_rot (the task modules take their own keys out first)
@@ -1632,6 +1713,8 @@ def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants
     for k in ("success_threshold", "successes_needed", "success_reward", "max_timesteps_per_goal_per_obj", "use_goal_distance_reward", "goal_reward_per_object"):
         if k in constants:
             args[k] = constants[k]
+    if "mask_obs_outside_placement_area" in constants:
+        args["mask_obs_outside_placement_area"] = bool(constants["mask_obs_outside_placement_area"])
     for k in ("penalty", "used_table_portion"):      # (a given penalty dict replaces the default one as a whole, as the reference's attrs field does)
         if k in sp:
             args[k] = sp[k]

@@ -166,6 +166,20 @@ class GroupedYcbRearrangeEnv:
         ema = self._to_envs(torch.cat([g.action_ema for g in self.groups])) if self.wrapped else None
         return self.groups[0].observe(packed, ema)
 
+    @property
+    def goal_objects_in_placement_area(self):
+        """[B, N] bool in env order, as BatchedBlockRearrangeEnv's; None without mask_obs_outside_placement_area"""
+        import torch
+
+        if self.groups[0].goal_in_area is None:
+            return None
+        return self._to_envs(torch.cat([g.goal_objects_in_placement_area for g in self.groups]))
+
+    @property
+    def goal_in_placement_area(self):
+        m = self.goal_objects_in_placement_area
+        return None if m is None else m.all(dim=1)
+
     def _names(self):
         return [self.object_names[s // self.b] for s in self._slot]
 
@@ -300,6 +314,8 @@ def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants
     for k in ("success_threshold", "successes_needed", "success_reward", "max_timesteps_per_goal_per_obj", "use_goal_distance_reward", "goal_reward_per_object"):
         if k in constants:
             args[k] = constants[k]
+    if "mask_obs_outside_placement_area" in constants:      # the placement-area masks (goal_args.soft_mask / mask_margin come through goal_rot_args)
+        args["mask_obs_outside_placement_area"] = bool(constants["mask_obs_outside_placement_area"])
     for k in ("penalty", "used_table_portion"):
         if k in sp:
             args[k] = sp[k]
