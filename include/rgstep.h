@@ -500,6 +500,38 @@ int rb_multi_launch(void* stream);
  * (goals/object_state.py:492-599), MultiGoalTracker.process and the gripper hand-over to the solver world (joint_controlled_tcp_arm.py:114-129).
  * The main batch must have been stepped with flags bit 5 (the row is read from the final forward's stage arrays).  goal_reset[e] = 1 asks the
  * host for a new goal (ObjectStateGoal.next_goal is placement sampling: host work). */
+/* Codes of the rearrange env kernels, each defined here once (robogym_amd/_native.py mirrors them).
+ * goal kinds (ra_post_args.goal_kind, ra_recipe_args.goal_kind), in the order of GOAL_KINDS (robogym_amd/envs/rearrange/blocks.py): */
+#define RA_GOAL_OBJECT_STATE 0
+#define RA_GOAL_PICKANDPLACE 1
+#define RA_GOAL_STACK 2
+#define RA_GOAL_REACH 3
+#define RA_GOAL_DET_REACH 4
+#define RA_GOAL_TRAIN 5
+#define RA_GOAL_DOMINOS 6
+#define RA_GOAL_ATTACHED 7
+#define RA_GOAL_FIXED 8
+/* ra_post_args.rot_dist_type */
+#define RA_ROT_FULL 0
+#define RA_ROT_MOD90 1
+#define RA_ROT_MOD180 2
+#define RA_ROT_ICP 3
+/* ra_post_args.frozen / ra_recipe_args.frozen and .reobserve: what one launch of ra_env_post_step does with an env.  Every code but RA_OBS_SKIP writes the
+ * observation entries of the row (the per-object keys, the robot read-outs, qpos, qpos_goal, the mask_obs keys, safety_stop / tcp_force / tcp_torque).
+ *   RA_OBS_STEP           a step of a live env: reward and done (the row's last four columns), the tracker's step, goal_dist, every flag and counter,
+ *                         is_goal_achieved, the count the next goal-distance reward is measured from, the gripper hand-over to the solver world.
+ *   RA_OBS_EPISODE_START  the first observation of a new episode (reset's _observe_sync): zero reward / done / flags (env_crash and objects_off_table as observed),
+ *                         is_goal_achieved 0, goal_dist, the count the first step's goal-distance reward is measured from, the gripper hand-over; no tracker step.
+ *   RA_OBS_SKIP           the env is left alone: no byte of it is written.
+ *   RA_OBS_NEW_GOAL       a live env whose goal was just replaced: the observation entries, is_goal_achieved and the count the next goal-distance reward is
+ *                         measured from under the new goal; reward / done / flags / counters / goal_dist of the step stay, no hand-over.
+ *   RA_OBS_IN_RECIPE      an env inside its reset recipe (pipelined resets; the recipe's steps are _set_action + mujoco_simulation.step(), no _observe_sync): as
+ *                         RA_OBS_EPISODE_START without the reward's count and without the hand-over. */
+#define RA_OBS_STEP 0
+#define RA_OBS_EPISODE_START 1
+#define RA_OBS_SKIP 2
+#define RA_OBS_NEW_GOAL 3
+#define RA_OBS_IN_RECIPE 4
 #define RA_MAXOBJ 16
 typedef struct ra_post_args {
   float* obs; int obs_dim;                       /* [B][obs_dim + 4] */
@@ -521,21 +553,19 @@ typedef struct ra_post_args {
   int max_timesteps_per_goal, successes_needed, use_goal_distance_reward;
   float *solver_qpos, *solver_ctrl;              /* rows of the solver batch (filled by ra_env_post_step), NULL: no hand-over */
   int solver_nq, solver_nu, solver_grip_qposadr, solver_grip_act;
-  const unsigned char* frozen;                   /* [B] or NULL.  1: an env inside its reset recipe (pipelined resets) or being re-observed after a goal change — observation
-                                                    row and gripper hand-over only: no reward, no tracker step, done = 0.  2: the env is skipped altogether.  3: the observation entries only (a live env
-                                                    whose goal was just replaced): reward / done / flags / counters of the step stay */
+  const unsigned char* frozen;                   /* [B] or NULL (= RA_OBS_STEP everywhere): what the launch does with each env, the RA_OBS_* codes above */
   float reward_clip;                             /* ClipRewardWrapper (wrappers/util.py:115-126; 100 in RearrangeEnv.apply_wrappers): every reward entry clipped to +- this; 0 = off */
   /* goal kinds (appended; zero-filled = the object-state task above).  0 ObjectStateGoal, 1 PickAndPlaceGoal (scored as 0), 2 ObjectStackGoal (goals/object_stack_goal.py:
    * + per object |obj_pos - grip site| and the two finger contacts, summed into goal_dist_extra), 3 ObjectReachGoal / 4 DeterministicReachGoal (goals/object_reach_goal.py:
    * the achieved position is the grip site, the achieved rotation zero; blocks_reach.py: the goal reward is the decrease of the summed obj_pos distance) */
   int goal_kind;
-  int grip_site;                                 /* site robot0:grip (kinds 2-4) */
-  float* goal_dist_extra;                        /* [B][2] kind 2: sums of the gripper_pos distances and of `grasped`; NULL otherwise */
+  int grip_site;                                 /* site robot0:grip (RA_GOAL_STACK and the reach goals) */
+  float* goal_dist_extra;                        /* [B][2] RA_GOAL_STACK: sums of the gripper_pos distances and of `grasped`; NULL otherwise */
   /* duplicated-object groups (appended; NULL = all objects distinct, the path above).  [B][N] group id of each object; objects with equal ids are interchangeable:
    * ObjectStateGoal.relative_goal (goals/object_state.py:520-554) matches objects to goals inside each group greedily by position distance, and the relative goal,
    * both distances and the success count go through that match.  goal_obj_pos / goal_obj_rot / qpos_goal stay indexed by goal.  Kinds 0-2 only. */
   const int* obj_group;
-  /* rotation distance modes (appended; zero-filled = "full", the path above; 3: icp, below).  rot_dist_type 0: full -- quat2euler(q_goal conj(q_obj)); 1: mod90, 2: mod180 --
+  /* rotation distance modes (appended; zero-filled = RA_ROT_FULL, the path above; RA_ROT_ICP: below).  RA_ROT_FULL: quat2euler(q_goal conj(q_obj)); RA_ROT_MOD90, RA_ROT_MOD180:
    * euler_angle_difference_single_pair (goals/object_state.py:25-64): of diff_p = quat_difference(q_goal p, q_obj) over the 24 (mod90) or 4 (mod180) parallel quaternions
    * p, in the table's order, the first with the smallest quat_magnitude; the relative rotation is its Euler angles, the distance its angle.  Without the reference's
    * np.allclose(q_goal, q_obj) -> zeros shortcut (p = identity gives the same zeros).  The tables are the caller's: device pointers to EXACTLY 24 x 4 and 4 x 4 floats (the kernel reads those lengths, nothing carries them)
@@ -551,13 +581,13 @@ typedef struct ra_post_args {
    * max_timesteps_per_goal_per_obj * n (common/base.py:919-927); max_timesteps_per_goal is not read then.  qpos / qpos_goal keep the world's full nq. */
   const int* num_active;
   int max_timesteps_per_goal_per_obj;
-  /* rot_dist_type 3: icp (appended; NULL = none, every path above as it is).  icp_rel [B][N][3]: what the ICP launch (rgstep_icp.h) wrote for this state -- per object the Euler angles of
+  /* rot_dist_type RA_ROT_ICP (appended; NULL = none, every path above as it is).  icp_rel [B][N][3]: what the ICP launch (rgstep_icp.h) wrote for this state -- per object the Euler angles of
    * the ICP fit against the goal it is measured against (the group matching is already applied), before normalize_angles, or (pi/2, pi/2, pi/2) where the fit was refused
-   * (goals/object_state.py:258-290).  With rot_dist_type 3 the relative rotation is normalize_angles(icp_rel) and the rotation distance the angle of euler2quat of it
-   * (goal_distance, :586-599); rot_dist_type 3 without icp_rel is an error.  Kinds 0-2. */
+   * (goals/object_state.py:258-290).  With RA_ROT_ICP the relative rotation is normalize_angles(icp_rel) and the rotation distance the angle of euler2quat of it
+   * (goal_distance, :586-599); RA_ROT_ICP without icp_rel is an error.  Not for the reach goals. */
   const float* icp_rel;
   /* masks of the placement area (appended; mask_obs 0 = none, every path above as it is, obs_dim = 36 N + 23 + 2 nq).  constants.mask_obs_outside_placement_area
-   * (common/base.py:311-374, 415-419): with mask_obs 1 every launch that writes observation entries (frozen 1 and 3 included) evaluates
+   * (common/base.py:311-374, 415-419): with mask_obs 1 every launch that writes observation entries (RA_OBS_EPISODE_START and RA_OBS_NEW_GOAL included) evaluates
    * check_objects_in_placement_area (simulation/base.py:847-902) on the obj_pos it just wrote, against the boundary of extract_placement_area_boundary (:834-845; the
    * reference caches it per episode, common/base.py:929-932) -- lo.xy = area offset + table_pos - table_size, lo.z = table_pos.z + table_size.z, hi = lo + (area_size,
    * area_height); with num_active the area of the env's own count (get_placement_area, :980-1010, from used_table_portion; area_offset / area_size are then the area of
@@ -585,14 +615,24 @@ int ra_post_args_size(void);
  * common/utils.py:719-829, with `place_objects_with_no_constraint`'s rejection sampling, :829-880, when the grid has fewer cells than objects; bounding boxes and colours
  * of the static observation); for a live env whose goal was reached `ObjectStateGoal.next_goal` (goals/object_state.py:355-418: a new placement, the goal keeps the
  * objects' initial yaw).  Draws come from a counter-based generator (seed, step, env, k).  Outputs for the NEXT step's launches: hold / hold_ctrl / scripted /
- * frozen / solver_active / nticks; `reobserve` is the `frozen` array of a second ra_env_post_step launch (1 = first observation of a new episode, 3 = a live env with
- * a new goal, 2 = skip); `ended` / `stabilised` / `episode_started` are masks for the host's tensor ops on the per-env parameter rows (stabilize_objects' damping,
+ * frozen / solver_active / nticks; `reobserve` is the `frozen` array of a second ra_env_post_step launch (RA_OBS_EPISODE_START, RA_OBS_NEW_GOAL for a live env
+ * with a new goal, RA_OBS_SKIP otherwise); `ended` / `stabilised` / `episode_started` are masks for the host's tensor ops on the per-env parameter rows (stabilize_objects' damping,
  * the simulation randomizers).  solver may be NULL (control_mode joint). */
+/* ra_recipe_args.stage: the recipe's stage machine */
+#define RA_STAGE_LIVE 0
+#define RA_STAGE_STABILISE 1
+#define RA_STAGE_RANDOM_ACTION 2
+#define RA_STAGE_SETTLE 3
+/* ra_recipe_args.group_mode: the obj_group rows are the caller's and stay / are sampled whenever an episode ends */
+#define RA_GROUPS_KEEP 0
+#define RA_GROUPS_SAMPLE 1
+/* ra_recipe_args.sync_mode */
+#define RA_SYNC_PIPELINED 0
 #define RA_SYNC_FORCED_END 1
 #define RA_SYNC_REGOAL_ONLY 2
 typedef struct ra_recipe_args {
   int num_objects, action_dim;
-  int *stage, *left;                             /* [B]: 0 live, 1 stabilise, 2 random action, 3 settle; steps left in the stage */
+  int *stage, *left;                             /* [B]: RA_STAGE_*; steps left in the stage */
   float* yaw;                                    /* [B][N] the episode's object rotations about z */
   const unsigned char *done, *goal_reset;        /* [B] as ra_env_post_step left them */
   int *hold, *hold_ctrl, *solver_active, *nticks;
@@ -617,9 +657,9 @@ typedef struct ra_recipe_args {
   int fixed_order;
   float target_height;
   float det_points[2][3];
-  int* goal_index;                               /* [B] kind 4 */
-  /* duplicated-object groups (appended; zero-filled = none).  obj_group: ra_post_args' [B][N] row, NULL = all distinct.  group_mode 0: the rows are the caller's
-   * and stay; 1: an env whose episode ends gets a new row from sample_group_counts (common/utils.py:47-73: until the objects are used up lam ~ U(sample_lam), then a
+  int* goal_index;                               /* [B] RA_GOAL_DET_REACH */
+  /* duplicated-object groups (appended; zero-filled = none).  obj_group: ra_post_args' [B][N] row, NULL = all distinct.  group_mode RA_GROUPS_KEEP: the rows are the caller's
+   * and stay; RA_GROUPS_SAMPLE: an env whose episode ends gets a new row from sample_group_counts (common/utils.py:47-73: until the objects are used up lam ~ U(sample_lam), then a
    * count k in 1..remaining with probability proportional to exp(-k lam)), ids 0, 1, ... over contiguous ranges of objects; draws (seed ^ 0x85EBCA6B, step, env, 3000 + ...): a stream of their own. */
   int* obj_group;
   int group_mode;

@@ -14,7 +14,7 @@ extern "C" {
  * ra_env_post_step.  All arrays are device pointers.  The clouds are in the objects' body frames (robogym_amd/envs/rearrange/icp.py object_point_clouds): src
  * [N][src_stride][3] with src_num[i] <= min(src_stride, 512) points in use, tgt [tgt_total][3] flat with object i's tgt_num[i] >= 1 points from row tgt_adr[i] on (the
  * kernel clamps what it reads to these bounds; an object whose cloud is empty or out of bounds gets the default).  icp_rel [B][N][3] receives, per active object of every
- * env whose frozen code is not 2, the Euler angles of the fit (before normalize_angles) or (pi/2, pi/2, pi/2); padded slots (object >= num_active[env]) and skipped envs
+ * env whose frozen code is not RA_OBS_SKIP, the Euler angles of the fit (before normalize_angles) or (pi/2, pi/2, pi/2); padded slots (object >= num_active[env]) and skipped envs
  * keep what they hold.  obj_group / num_active / frozen: ra_post_args' rows, NULL allowed; with obj_group object i is measured against the goal the post-step kernel's
  * matching gives it. */
 typedef struct ra_icp_args {

@@ -142,7 +142,13 @@ class RaRecipeArgs(ctypes.Structure):
     _fields_ = _ra_recipe_fields()
 
 
-RA_SYNC_FORCED_END, RA_SYNC_REGOAL_ONLY = 1, 2      # ra_recipe_args.sync_mode
+# the codes of the rearrange env kernels, as include/rgstep.h defines them (tests/test_rearrange_codes.py compares the two)
+RA_GOAL_OBJECT_STATE, RA_GOAL_PICKANDPLACE, RA_GOAL_STACK, RA_GOAL_REACH, RA_GOAL_DET_REACH, RA_GOAL_TRAIN, RA_GOAL_DOMINOS, RA_GOAL_ATTACHED, RA_GOAL_FIXED = range(9)
+RA_ROT_FULL, RA_ROT_MOD90, RA_ROT_MOD180, RA_ROT_ICP = range(4)                                          # ra_post_args.rot_dist_type
+RA_OBS_STEP, RA_OBS_EPISODE_START, RA_OBS_SKIP, RA_OBS_NEW_GOAL, RA_OBS_IN_RECIPE = range(5)            # ra_post_args.frozen, ra_recipe_args.frozen / reobserve
+RA_STAGE_LIVE, RA_STAGE_STABILISE, RA_STAGE_RANDOM_ACTION, RA_STAGE_SETTLE = range(4)                   # ra_recipe_args.stage
+RA_GROUPS_KEEP, RA_GROUPS_SAMPLE = 0, 1                                                                  # ra_recipe_args.group_mode
+RA_SYNC_PIPELINED, RA_SYNC_FORCED_END, RA_SYNC_REGOAL_ONLY = 0, 1, 2      # ra_recipe_args.sync_mode
 RA_ROWS_RESTORE, RA_ROWS_PARK = 1, 2                # ra_param_rows_args.stages
 
 

@@ -17,8 +17,19 @@
 // Rotation helpers follow robogym/utils/rotation.py (mat2euler, quat2mat, normalize_angles) as rb_env_kernel.h's rbc_* do.
 #pragma once
 #include "rb_env_kernel.h"
+#include "ra_row.h"
 
 namespace rgb {
+// what the kernels ask of a goal kind (RA_GOAL_*, include/rgstep.h)
+__host__ __device__ inline bool ra_kind_is_reach(int kind) { return kind == RA_GOAL_REACH || kind == RA_GOAL_DET_REACH; }            // one object, the achieved position the grip site's
+__host__ __device__ inline bool ra_kind_uses_grip_site(int kind) { return kind == RA_GOAL_STACK || ra_kind_is_reach(kind); }
+__host__ __device__ inline bool ra_kind_places_on_grid(int kind) { return kind == RA_GOAL_OBJECT_STATE || kind == RA_GOAL_PICKANDPLACE; }
+__host__ __device__ inline bool ra_kind_is_counted(int kind) { return ra_kind_places_on_grid(kind) || kind == RA_GOAL_STACK || kind == RA_GOAL_TRAIN; }   // built for per-env object counts
+// the draw streams env_u01(seed ^ stream, step, env, k) (the recipe's own is the plain seed), and the first draw index k of the sections that share a stream
+enum : unsigned { RA_STREAM_GOAL = 0x9E3779B9u, RA_STREAM_GOAL_YAW = 0xC2B2AE35u, RA_STREAM_GROUPS = 0x85EBCA6Bu, RA_STREAM_OBJ_MASK = 0xA54FF53Au, RA_STREAM_GOAL_MASK = 0x3C6EF372u,
+                  RA_DRAW_COLOURS = 500u, RA_DRAW_PLACEMENT = 1000u, RA_DRAW_GROUPS = 3000u };
+// one env's draws from one stream, in order
+struct RaDraws { unsigned seed, step, e, k; __device__ float operator()() { return env_u01(seed, step, e, k++); } };
 
 // ObjectStateGoal.relative_goal's matching of interchangeable objects to goals (goals/object_state.py:520-554), one wave per env: returns, on lane i < N, the goal j
 // that object i is measured against.  The reference goes group by group: the n x n matrix of |obj_pos[i] - goal_pos[j]| over the group's objects, n times
@@ -68,10 +79,9 @@ __device__ inline int ra_group_match(const int* grp, const float* xpos, const in
   return mine;
 }
 
-// get_placement_area (simulation/base.py:980-1010) of one env: offset from the table's low corner and size.  Without per-env object counts the launch constants.
-// With them the area follows the env's own count n: used_table_portion clipped to [0.1 n, 1], width = 0.5 x table width x portion, height = 0.38 x table depth x
-// portion, centred at (0.5, 0.44) of the table.  An env whose clipped portion is the one the launch constants were made with (n = num_objects among them) reads
-// those, bit for bit.  `Args`: RaRecipeArgs, or RaPostArgs (mask_obs), which carries the same fields.
+// get_placement_area (simulation/base.py:980-1010) of one env: offset from the table's low corner and size -- the launch constants, or with per-env object counts the
+// area of the env's own count n (ra_recipe_args.num_active, include/rgstep.h); an env whose clipped portion is the one the launch constants were made with (n =
+// num_objects among them) reads those, bit for bit.  `Args`: RaRecipeArgs, or RaPostArgs (mask_obs), which carries the same fields.
 struct RaArea { float off[2], size[2]; };
 template <class Args>
 __device__ inline RaArea ra_area(const Args& a, int n) {
@@ -89,10 +99,8 @@ __device__ inline RaArea ra_area(const Args& a, int n) {
 }
 
 // check_objects_in_placement_area (simulation/base.py:847-902) for one point `p`, the one membership rule of the env kernel (the objects) and the recipe kernel (the
-// goals).  Boundary (extract_placement_area_boundary, :834-845): lo.xy = area offset + table_pos - table_size, lo.z = table_pos.z + table_size.z, hi = lo + (width,
-// height, area_height), in the area `ar` of the env's own count (ra_area: the reference's cached boundary and its on-the-fly one are then the same thing).
-// max_dist = the largest of max(p - hi, lo - p, 0) over x, y, z.  Hard: max_dist < margin.  Soft: u > clip(max_dist / margin, 0, 1), `u` the env's ONE uniform of
-// this call, shared by its objects (the reference draws a scalar).  Returns 1.0 / 0.0.
+// goals), as ra_post_args.mask_obs describes it (include/rgstep.h), in the area `ar` of the env's own count (ra_area: the reference's cached boundary and its
+// on-the-fly one are then the same thing).  `u`: the env's ONE uniform of this call, shared by its objects (the reference draws a scalar).  Returns 1.0 / 0.0.
 template <class Args>
 __device__ inline float ra_in_area(const Args& a, const RaArea& ar, const float* p, bool soft, float u) {
   const float lo[3] = {ar.off[0] + a.table_pos[0] - a.table_size[0], ar.off[1] + a.table_pos[1] - a.table_size[1], a.table_pos[2] + a.table_size[2]};
@@ -103,21 +111,44 @@ __device__ inline float ra_in_area(const Args& a, const RaArea& ar, const float*
   return max_dist < a.mask_margin ? 1.f : 0.f;
 }
 
+// What one object contributes to the row: the per-object keys, collected by the object's lane.  Members are indexed with constants only (registers).
+struct RaObjVals { float pos[3], rel_pos[3], vel_pos[3], rot[3], vel_rot[3], goal_pos[3], goal_rot[3], rel_goal_pos[3], rel_goal_rot[3], contact[2], bbox[3], colors[4]; };
+// The per-object keys of one block of the row from `v` (ra_row.h has the layout): the plain keys, or with MASKED their masked_* copies -- the object keys where the
+// object's mask `obj_in` holds, the goal keys where the goal's mask `goal_in` does, zero elsewhere (_mask_object_observation / _mask_goal_observation, common/base.py:311-374)
+template <bool MASKED>
+__device__ inline void ra_write_object(float* row, int N, int nq, int lane, const RaObjVals& v, bool obj_in = true, bool goal_in = true) {
+#define RA_COL(NAME) (row + ra_key_offset<MASKED ? RA_K_MASKED_##NAME : RA_K_##NAME>(N, nq))
+  for (int k = 0; k < 3; k++) {
+    RA_COL(OBJ_POS)[3 * lane + k] = obj_in ? v.pos[k] : 0.f; RA_COL(OBJ_REL_POS)[3 * lane + k] = obj_in ? v.rel_pos[k] : 0.f; RA_COL(OBJ_VEL_POS)[3 * lane + k] = obj_in ? v.vel_pos[k] : 0.f;
+    RA_COL(OBJ_ROT)[3 * lane + k] = obj_in ? v.rot[k] : 0.f; RA_COL(OBJ_VEL_ROT)[3 * lane + k] = obj_in ? v.vel_rot[k] : 0.f; RA_COL(OBJ_BBOX_SIZE)[3 * lane + k] = obj_in ? v.bbox[k] : 0.f;
+    RA_COL(GOAL_OBJ_POS)[3 * lane + k] = goal_in ? v.goal_pos[k] : 0.f; RA_COL(GOAL_OBJ_ROT)[3 * lane + k] = goal_in ? v.goal_rot[k] : 0.f;
+    RA_COL(REL_GOAL_OBJ_POS)[3 * lane + k] = goal_in ? v.rel_goal_pos[k] : 0.f; RA_COL(REL_GOAL_OBJ_ROT)[3 * lane + k] = goal_in ? v.rel_goal_rot[k] : 0.f;
+  }
+  for (int k = 0; k < 2; k++) RA_COL(OBJ_GRIPPER_CONTACT)[2 * lane + k] = obj_in ? v.contact[k] : 0.f;
+  for (int k = 0; k < 4; k++) RA_COL(OBJ_COLORS)[4 * lane + k] = obj_in ? v.colors[k] : 0.f;
+#undef RA_COL
+}
+// safety_stop | tcp_force | tcp_torque (lane 0, under every observation code that writes)
+__device__ inline void ra_write_safety(const RaPostArgs& a, float* row, int nq, int safety, const float* sens) {
+  float* o = row + ra_key_offset<RA_K_SAFETY_STOP>(a.num_objects, nq);
+  o[0] = (float)safety;
+  for (int k = 0; k < 3; k++) { o[1 + k] = sens[a.force_adr + k]; o[4 + k] = sens[a.torque_adr + k]; }
+}
+
 __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, RbBatchDev bt, RaPostArgs a) {
   const RbModelDev& m = *mp;
   const int e = blockIdx.x, lane = threadIdx.x;
   if (e >= bt.B) return;
-  if (a.frozen && a.frozen[e] == 2) return;      // not this env's turn (re-observation of selected envs only)
+  if (a.frozen && a.frozen[e] == RA_OBS_SKIP) return;      // not this env's turn (re-observation of selected envs only)
   const int nq = m.nq, N = a.num_objects;
   // per-env object count: the env's first n objects are in use, slots n .. N - 1 are padding (zeros in every per-object key, no part in any sum, flag or match)
   int n = N;
   if (a.num_active) { n = a.num_active[e]; n = n < 1 ? 1 : (n > N ? N : n); }
-  const float* qrow = bt.qpos + (size_t)e * nq;
-  const float* vrow = bt.qvel + (size_t)e * m.nv;
-  const float* crow = bt.ctrl + (size_t)e * m.nu;
+  const float *qrow = bt.qpos + (size_t)e * nq, *vrow = bt.qvel + (size_t)e * m.nv, *crow = bt.ctrl + (size_t)e * m.nu;
   const float* S = bt.scratch + (size_t)e * m.scratch_words;
   const float *xpos = S + m.off[RB_O_XPOS], *xquat = S + m.off[RB_O_XQUAT], *cvel = S + m.off[RB_O_CVEL], *rootcom = S + m.off[RB_O_ROOTCOM];
   const float* sens = bt.sensordata + (size_t)e * m.nsensordata;
+  const float* con = S + m.off[RB_O_CON]; const int ncon = (int)S[m.off[RB_O_DBG] + 3];      // the contact records of the final forward
   float* row = a.obs + (size_t)e * (a.obs_dim + 4);
   const int crash = (bt.status[e] & RG_STATUS_BAD_STATE) != 0;
   // world velocity of a body frame's origin (mujoco-py body_xvelp / body_xvelr: Jacobian of the origin times qvel)
@@ -133,10 +164,12 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
   // ---- per object (lane k < N): pose, velocities, relative goal, distances, finger contacts, off-table test
   int ok_obj = 0, off_obj = 0;
   float dpos = 0.f, drot = 0.f, dgrip = 0.f, grasp = 0.f;
-  const int reach = a.goal_kind >= 3;
-  const float* grip = S + m.off[RB_O_SPOS] + 3 * a.grip_site;      // (kinds 2-4 only)
+  const int reach = ra_kind_is_reach(a.goal_kind);
+  const float* grip = S + m.off[RB_O_SPOS] + 3 * a.grip_site;      // (ra_kind_uses_grip_site only)
   int mgoal = lane;                              // the goal this lane's object is measured against: its own, or its match inside its group of duplicates
   if (a.obj_group) mgoal = ra_group_match(a.obj_group + (size_t)e * N, xpos, a.obj_body, a.goal + (size_t)e * N * 7, N, n, lane);
+  RaObjVals v = {};                              // (a padded slot keeps the zeros: simulation/base.py:222-224, 1015-1024; goals/object_state.py:556-580)
+  bool obj_in = true, goal_in = true;            // mask_obs: the two masks (a padded slot reads 1.0: the reference pads them with True, simulation/base.py:893-897)
   if (lane < n) {
     const int b = a.obj_body[lane];
     float M[9], eul[3], vp[3], vr[3];
@@ -148,21 +181,21 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
     const float* gm = a.goal + ((size_t)e * N + mgoal) * 7;
     float qc[4] = {xquat[4 * b], -xquat[4 * b + 1], -xquat[4 * b + 2], -xquat[4 * b + 3]}, qd[4], Md[9], rel[3];
     if (reach) { qc[0] = 1.f; qc[1] = qc[2] = qc[3] = 0.f; }      // ObjectReachGoal.current_state: the achieved rotation is zero
-    if (a.rot_dist_type == 3) {
+    if (a.rot_dist_type == RA_ROT_ICP) {
       // icp: _icp_euler_angle_difference's angles for this object against its matched goal, as ra_icp_kernel left them (ra_icp_kernel.h); relative_goal normalises them
       // and goal_distance takes the angle of euler2quat of the result (goals/object_state.py:579-599): q = qx(e0) qy(e1) qz(e2), robogym/utils/rotation.py euler2quat
       const float* ir = a.icp_rel + ((size_t)e * N + lane) * 3;
       for (int k = 0; k < 3; k++) rel[k] = rbc_wrap(ir[k]);
       const float cx = cosf(0.5f * rel[0]), sx = sinf(0.5f * rel[0]), cy = cosf(0.5f * rel[1]), sy = sinf(0.5f * rel[1]), cz = cosf(0.5f * rel[2]), sz = sinf(0.5f * rel[2]);
       qd[0] = cx * cy * cz - sx * sy * sz; qd[1] = sx * cy * cz + cx * sy * sz; qd[2] = cx * sy * cz - sx * cy * sz; qd[3] = cx * cy * sz + sx * sy * cz;
-    } else if (a.rot_dist_type == 0) {
+    } else if (a.rot_dist_type == RA_ROT_FULL) {
       rbc_qmul(gm + 3, qc, qd);               // subtract_euler(goal, current) = quat2euler(q_goal conj(q_obj))
     } else {
       // mod90 / mod180, euler_angle_difference_single_pair (goals/object_state.py:25-64): diff_p = quat_difference(q_goal p, q_obj) over the table's parallel
       // quaternions p (24 / 4 of them: fixed lengths, include/rgstep.h), the first with the smallest quat_magnitude = with the largest |w| (2 acos(w) falls with w; the
       // strict > keeps the first among equals); its Euler angles and its angle then come out of the lines below, which do not see the quaternion's sign
-      const float* tab = a.rot_dist_type == 1 ? a.parallel_quats : a.parallel_quats_180;
-      const int np_ = a.rot_dist_type == 1 ? 24 : 4;
+      const float* tab = a.rot_dist_type == RA_ROT_MOD90 ? a.parallel_quats : a.parallel_quats_180;
+      const int np_ = a.rot_dist_type == RA_ROT_MOD90 ? 24 : 4;
       float best = -1.f;
       qd[0] = 1.f; qd[1] = qd[2] = qd[3] = 0.f;
       for (int c = 0; c < np_; c++) {
@@ -173,7 +206,7 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
         if (w > best) { best = w; qd[0] = d[0]; qd[1] = d[1]; qd[2] = d[2]; qd[3] = d[3]; }
       }
     }
-    if (a.rot_dist_type != 3) {
+    if (a.rot_dist_type != RA_ROT_ICP) {
       rbc_quat2mat(qd, Md); rbc_mat2euler(Md, rel);
       for (int k = 0; k < 3; k++) rel[k] = rbc_wrap(rel[k]);
     }
@@ -185,19 +218,14 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
     drot = a.goal_rot_weight * rbc_qmag(qd);   // quat_magnitude(quat_normalize(euler2quat(rel))): the angle of the same rotation
     ok_obj = !crash && dpos < a.pos_threshold && drot < a.rot_threshold;
     off_obj = xpos[3 * b + 2] < a.table_height * 0.75f || xpos[3 * b] < a.table_min[0] || xpos[3 * b] > a.table_max[0] || xpos[3 * b + 1] < a.table_min[1] || xpos[3 * b + 1] > a.table_max[1];
-    float* o = row;
+    const float* so = a.static_obs + ((size_t)e * N + lane) * 7;
     for (int k = 0; k < 3; k++) {
-      o[3 * lane + k] = xpos[3 * b + k]; o[3 * N + 3 * lane + k] = xpos[3 * b + k] - tcp[k]; o[6 * N + 3 * lane + k] = vp[k] - tcp_vp[k];
-      o[9 * N + 3 * lane + k] = eul[k]; o[12 * N + 3 * lane + k] = vr[k];
+      v.pos[k] = xpos[3 * b + k]; v.rel_pos[k] = xpos[3 * b + k] - tcp[k]; v.vel_pos[k] = vp[k] - tcp_vp[k]; v.rot[k] = eul[k]; v.vel_rot[k] = vr[k];
+      v.goal_pos[k] = gp[k]; v.goal_rot[k] = a.goal_rot[((size_t)e * N + lane) * 3 + k]; v.rel_goal_rot[k] = rel[k]; v.bbox[k] = so[k];
     }
-    const int g0 = 15 * N + 15 + 2 * nq;
-    for (int k = 0; k < 3; k++) {
-      o[g0 + 3 * lane + k] = gp[k]; o[g0 + 3 * N + 3 * lane + k] = a.goal_rot[((size_t)e * N + lane) * 3 + k];
-      o[g0 + 6 * N + 1 + 3 * lane + k] = k == 0 ? rx : (k == 1 ? ry : rz); o[g0 + 9 * N + 1 + 3 * lane + k] = rel[k];
-    }
+    v.rel_goal_pos[0] = rx; v.rel_goal_pos[1] = ry; v.rel_goal_pos[2] = rz;
+    for (int k = 0; k < 4; k++) v.colors[k] = so[3 + k];
     // obj_gripper_contact: any contact (dist < 1e-5) between one of the object's geoms and the left / right finger pad
-    const float* con = S + m.off[RB_O_CON];
-    const int ncon = (int)S[m.off[RB_O_DBG] + 3];
     float cl = 0.f, cr = 0.f;
     for (int c = 0; c < ncon; c++) {
       const float* C = con + RB_CONREC * c;
@@ -208,48 +236,21 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
         if (other >= 0 && m.geom_bodyid[other] == b) { if (f == 0) cl = 1.f; else cr = 1.f; }
       }
     }
-    o[g0 + 12 * N + 1 + 2 * lane] = cl; o[g0 + 12 * N + 1 + 2 * lane + 1] = cr;
-    if (a.goal_kind == 2) {      // ObjectStackGoal.goal_distance: |obj_pos - gripper_pos| per object, grasped = the two finger contacts (is_object_grasped)
+    v.contact[0] = cl; v.contact[1] = cr;
+    if (a.goal_kind == RA_GOAL_STACK) {      // ObjectStackGoal.goal_distance: |obj_pos - gripper_pos| per object, grasped = the two finger contacts (is_object_grasped)
       const float gx = xpos[3 * b] - grip[0], gy = xpos[3 * b + 1] - grip[1], gz = xpos[3 * b + 2] - grip[2];
       dgrip = sqrtf(gx * gx + gy * gy + gz * gz); grasp = cl + cr;
     }
-    const float* so = a.static_obs + ((size_t)e * N + lane) * 7;
-    for (int k = 0; k < 3; k++) o[g0 + 14 * N + 1 + 3 * lane + k] = so[k];
-    for (int k = 0; k < 4; k++) o[g0 + 17 * N + 1 + 4 * lane + k] = so[3 + k];
+    if (a.mask_obs) {      // the object's mask from its obj_pos, the goal's as it was frozen with the goal
+      const float u = a.soft_mask ? env_u01(a.seed ^ RA_STREAM_OBJ_MASK, a.step, (unsigned)e, 0u) : 0.f;
+      obj_in = ra_in_area(a, ra_area(a, n), xpos + 3 * b, a.soft_mask != 0, u) != 0.f; goal_in = a.goal_in_area[(size_t)e * N + lane] != 0.f;
+    }
+  }
+  if (lane < N) {      // the object's keys, and with mask_obs the two masks and the masked copies
+    ra_write_object<false>(row, N, nq, lane, v);
     if (a.mask_obs) {
-      // _mask_object_observation / _mask_goal_observation (common/base.py:311-374): the object's mask from the obj_pos written above, the goal's as it was frozen with
-      // the goal; the goal keys under the goal's mask, the object keys under the object's -- the value, or zero
-      const float u = a.soft_mask ? env_u01(a.seed ^ 0xA54FF53Au, a.step, (unsigned)e, 0u) : 0.f;
-      const bool pm = ra_in_area(a, ra_area(a, n), xpos + 3 * b, a.soft_mask != 0, u) != 0.f, gm_ = a.goal_in_area[(size_t)e * N + lane] != 0.f;
-      float* q = row + 36 * N + 23 + 2 * nq;
-      q[lane] = pm ? 1.f : 0.f; q[N + lane] = gm_ ? 1.f : 0.f;
-      for (int k = 0; k < 3; k++) {
-        q[2 * N + 3 * lane + k] = gm_ ? gp[k] : 0.f; q[5 * N + 3 * lane + k] = gm_ ? a.goal_rot[((size_t)e * N + lane) * 3 + k] : 0.f;
-        q[8 * N + 3 * lane + k] = gm_ ? (k == 0 ? rx : (k == 1 ? ry : rz)) : 0.f; q[11 * N + 3 * lane + k] = gm_ ? rel[k] : 0.f;
-        q[14 * N + 3 * lane + k] = pm ? xpos[3 * b + k] : 0.f; q[17 * N + 3 * lane + k] = pm ? eul[k] : 0.f; q[20 * N + 3 * lane + k] = pm ? xpos[3 * b + k] - tcp[k] : 0.f;
-        q[23 * N + 3 * lane + k] = pm ? vp[k] - tcp_vp[k] : 0.f; q[26 * N + 3 * lane + k] = pm ? vr[k] : 0.f;
-        q[31 * N + 3 * lane + k] = pm ? so[k] : 0.f;
-      }
-      q[29 * N + 2 * lane] = pm ? cl : 0.f; q[29 * N + 2 * lane + 1] = pm ? cr : 0.f;
-      for (int k = 0; k < 4; k++) q[34 * N + 4 * lane + k] = pm ? so[3 + k] : 0.f;
-    }
-  } else if (lane < N) {      // a padded slot: zeros (simulation/base.py:222-224, 1015-1024; goals/object_state.py:556-580)
-    float* o = row;
-    const int g0 = 15 * N + 15 + 2 * nq;
-    for (int k = 0; k < 3; k++) {
-      o[3 * lane + k] = 0.f; o[3 * N + 3 * lane + k] = 0.f; o[6 * N + 3 * lane + k] = 0.f; o[9 * N + 3 * lane + k] = 0.f; o[12 * N + 3 * lane + k] = 0.f;
-      o[g0 + 3 * lane + k] = 0.f; o[g0 + 3 * N + 3 * lane + k] = 0.f; o[g0 + 6 * N + 1 + 3 * lane + k] = 0.f; o[g0 + 9 * N + 1 + 3 * lane + k] = 0.f;
-      o[g0 + 14 * N + 1 + 3 * lane + k] = 0.f;
-    }
-    o[g0 + 12 * N + 1 + 2 * lane] = 0.f; o[g0 + 12 * N + 1 + 2 * lane + 1] = 0.f;
-    for (int k = 0; k < 4; k++) o[g0 + 17 * N + 1 + 4 * lane + k] = 0.f;
-    if (a.mask_obs) {         // both masks 1.0 (the reference pads them with True, simulation/base.py:893-897), the masked values zero
-      float* q = row + 36 * N + 23 + 2 * nq;
-      q[lane] = 1.f; q[N + lane] = 1.f;
-      for (int c = 2; c < 29; c += 3) for (int k = 0; k < 3; k++) q[c * N + 3 * lane + k] = 0.f;      // the nine 3N keys in front of the contacts
-      q[29 * N + 2 * lane] = 0.f; q[29 * N + 2 * lane + 1] = 0.f;
-      for (int k = 0; k < 3; k++) q[31 * N + 3 * lane + k] = 0.f;
-      for (int k = 0; k < 4; k++) q[34 * N + 4 * lane + k] = 0.f;
+      row[ra_key_offset<RA_K_PLACEMENT_MASK>(N, nq) + lane] = obj_in ? 1.f : 0.f; row[ra_key_offset<RA_K_GOAL_PLACEMENT_MASK>(N, nq) + lane] = goal_in ? 1.f : 0.f;
+      ra_write_object<true>(row, N, nq, lane, v, obj_in, goal_in);
     }
   }
   const unsigned long long okmask = __ballot(ok_obj), offmask = __ballot(off_obj);
@@ -257,106 +258,81 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
   // sums of the distances over the objects (goal_info["goal_dist"])
   float sp = dpos, sr = drot;
   for (int o = 32; o > 0; o >>= 1) { sp += __shfl_xor(sp, o); sr += __shfl_xor(sr, o); }
-  if (a.goal_kind == 2) for (int o = 32; o > 0; o >>= 1) { dgrip += __shfl_xor(dgrip, o); grasp += __shfl_xor(grasp, o); }
+  if (a.goal_kind == RA_GOAL_STACK) for (int o = 32; o > 0; o >>= 1) { dgrip += __shfl_xor(dgrip, o); grasp += __shfl_xor(grasp, o); }
   // what the goal-distance reward is measured from: the count of objects within both thresholds (RearrangeEnv._calculate_num_success), for reach the summed obj_pos
   // distance (BlocksReachEnv._calculate_goal_distance_reward: its decrease)
   // (a padded slot reads distance 0 < threshold in _calculate_num_success, common/base.py:824-848 and its NOTE: N - n more, which cancel in the reward's difference)
   const float gscore = reach ? sp : (float)(nsucc + (N - n)) * a.goal_reward_per_object;
   // ---- robot read-outs and the copied blocks
-  {
-    float* o = row + 15 * N;
-    if (lane < 6) o[lane] = qrow[a.arm_qposadr[lane]];
-    if (lane < 3) { o[6 + lane] = tcp[lane]; o[9 + lane] = tcp_vp[lane]; }
-    if (lane == 0) { o[12] = crow[a.grip_act]; o[13] = qrow[a.grip_qposadr]; o[14] = vrow[a.grip_dofadr]; }
-    for (int k = lane; k < nq; k += 64) { o[15 + k] = qrow[k]; o[15 + nq + k] = a.qpos_goal[(size_t)e * nq + k]; }
+  if (lane < 6) row[ra_key_offset<RA_K_ROBOT_JOINT_POS>(N, nq) + lane] = qrow[a.arm_qposadr[lane]];
+  if (lane < 3) { row[ra_key_offset<RA_K_GRIPPER_POS>(N, nq) + lane] = tcp[lane]; row[ra_key_offset<RA_K_GRIPPER_VELP>(N, nq) + lane] = tcp_vp[lane]; }
+  if (lane == 0) {
+    row[ra_key_offset<RA_K_GRIPPER_CONTROLS>(N, nq)] = crow[a.grip_act]; row[ra_key_offset<RA_K_GRIPPER_QPOS>(N, nq)] = qrow[a.grip_qposadr];
+    row[ra_key_offset<RA_K_GRIPPER_VEL>(N, nq)] = vrow[a.grip_dofadr];
   }
+  for (int k = lane; k < nq; k += 64) { row[ra_key_offset<RA_K_QPOS>(N, nq) + k] = qrow[k]; row[ra_key_offset<RA_K_QPOS_GOAL>(N, nq) + k] = a.qpos_goal[(size_t)e * nq + k]; }
   // gripper - table-plane contact (any gripper geom against the table's collision plane)
   int table_hit = 0;
-  {
-    const float* con = S + m.off[RB_O_CON];
-    const int ncon = (int)S[m.off[RB_O_DBG] + 3];
-    for (int c = lane; c < ncon; c += 64) {
-      const float* C = con + RB_CONREC * c;
-      if ((int)C[RB_CR_KIND] == RB_KIND_EQUALITY) continue;
-      const int g1 = (int)C[RB_CR_G1], g2 = (int)C[RB_CR_G2];
-      const bool in1 = g1 < 64 && ((a.gripper_geom_mask >> g1) & 1ull), in2 = g2 < 64 && ((a.gripper_geom_mask >> g2) & 1ull);
-      const int other = in1 ? g2 : (in2 ? g1 : -1);
-      if (other == a.table_plane_geom) table_hit = 1;
-    }
+  for (int c = lane; c < ncon; c += 64) {
+    const float* C = con + RB_CONREC * c;
+    if ((int)C[RB_CR_KIND] == RB_KIND_EQUALITY) continue;
+    const int g1 = (int)C[RB_CR_G1], g2 = (int)C[RB_CR_G2];
+    const bool in1 = g1 < 64 && ((a.gripper_geom_mask >> g1) & 1ull), in2 = g2 < 64 && ((a.gripper_geom_mask >> g2) & 1ull);
+    const int other = in1 ? g2 : (in2 ? g1 : -1);
+    if (other == a.table_plane_geom) table_hit = 1;
   }
   const int table_contact = __ballot(table_hit) != 0;
   const float fx = sens[a.force_adr], fy = sens[a.force_adr + 1], fz = sens[a.force_adr + 2];
   const int safety = sqrtf(fx * fx + fy * fy + fz * fz) > a.safety_stop_force;
-  // frozen: 1 = the first observation of a new episode (reset's _observe_sync): observation row, gripper hand-over, zeroed outputs, the success count the next step's
-  // reward is measured from; 4 = an env INSIDE its reset recipe (pipelined resets): the recipe's steps are `_set_action + mujoco_simulation.step()`
-  // (common/base.py:484-496), no _observe_sync -- observation row and zeroed outputs only, no hand-over, no goal bookkeeping
-  const int frozen = a.frozen ? a.frozen[e] : 0;
-  if (lane == 0 && frozen == 3) {                  // 3: observation entries only (a live env whose goal was just replaced): reward / done / flags / counters untouched
-    const int g0 = 15 * N + 15 + 2 * nq;
-    row[g0 + 6 * N] = (float)(!crash && nsucc == n);
+  // ---- lane 0: what the env's observation code asks for (RA_OBS_*, include/rgstep.h)
+  const int frozen = a.frozen ? a.frozen[e] : RA_OBS_STEP;
+  float* achieved = row + ra_key_offset<RA_K_IS_GOAL_ACHIEVED>(N, nq);
+  if (lane == 0 && frozen == RA_OBS_NEW_GOAL) {    // observation entries only: reward / done / flags / counters untouched
+    *achieved = (float)(!crash && nsucc == n);
     // reset_goal -> _observe_sync -> update_goal_info (robot_env.py:893-909, 586-593): the re-observation under the new goal is what the next step's
     // goal-distance reward is measured from
     a.prev_nsucc[e] = gscore; a.prev_valid[e] = 1;
-    float* o = row + g0 + 21 * N + 1;
-    o[0] = (float)safety;
-    for (int k = 0; k < 3; k++) { o[1 + k] = sens[a.force_adr + k]; o[4 + k] = sens[a.torque_adr + k]; }
+    ra_write_safety(a, row, nq, safety, sens);
   }
-  if (lane == 0 && (frozen == 1 || frozen == 4)) {
-    float* rw = a.reward + 3 * (size_t)e;
-    rw[0] = rw[1] = rw[2] = 0.f;
-    a.goal_dist[2 * e] = sp; a.goal_dist[2 * e + 1] = sr;
-    if (a.goal_kind == 2) { a.goal_dist_extra[2 * e] = dgrip; a.goal_dist_extra[2 * e + 1] = grasp; }
-    a.done[e] = 0; a.goal_reset[e] = 0; a.trial_success[e] = 0; a.sub_goal_ok[e] = 0; a.env_crash[e] = crash; a.objects_off_table[e] = any_off;
-    a.info_ssl[e] = a.steps_since_last_goal[e];
-    // RobotEnv.reset -> reset_goal_generation -> _observe_sync -> update_goal_info (robot_env.py:757-792, 586-593): the observation that ends a reset
-    // establishes the success count the first step's goal-distance reward is measured from
-    if (frozen == 1) { a.prev_nsucc[e] = gscore; a.prev_valid[e] = 1; }
-    const int g0 = 15 * N + 15 + 2 * nq;
-    row[g0 + 6 * N] = 0.f;
-    float* o = row + g0 + 21 * N + 1;
-    o[0] = (float)safety;
-    for (int k = 0; k < 3; k++) { o[1 + k] = sens[a.force_adr + k]; o[4 + k] = sens[a.torque_adr + k]; }
-    float* tail = row + a.obs_dim;
-    tail[0] = tail[1] = tail[2] = tail[3] = 0.f;
-    if (a.solver_qpos && frozen == 1) {
-      a.solver_qpos[(size_t)e * a.solver_nq + a.solver_grip_qposadr] = qrow[a.grip_qposadr];
-      a.solver_ctrl[(size_t)e * a.solver_nu + a.solver_grip_act] = crow[a.grip_act];
+  // RA_OBS_STEP scores the step; RA_OBS_EPISODE_START and RA_OBS_IN_RECIPE write the same rows with zero reward, done and flags.  (RA_OBS_IN_RECIPE: the recipe's steps
+  // are `_set_action + mujoco_simulation.step()`, common/base.py:484-496, no _observe_sync -- no hand-over, no goal bookkeeping)
+  if (lane == 0 && (frozen == RA_OBS_STEP || frozen == RA_OBS_EPISODE_START || frozen == RA_OBS_IN_RECIPE)) {
+    float r[3] = {0.f, 0.f, 0.f};                                      // reward: env, goal, success
+    int done = 0, succ = 0;
+    EnvTracked tk = {false, false, false, false, a.steps_since_last_goal[e]};
+    if (frozen == RA_OBS_STEP) {
+      // ---- reward / done of the simulation (common/base.py:768-795)
+      if (table_contact) r[0] -= a.penalty_table_collision;
+      if (any_off) { done = 1; r[0] -= a.penalty_objects_off_table; }
+      if (safety) r[0] -= a.penalty_safety_stop;
+      // ---- _get_goal_info: reward = change of the number of objects within both thresholds (common/base.py:824-848)
+      a.t[e] += 1;
+      const float gdr = (a.prev_valid[e] && !crash) ? (reach ? a.prev_nsucc[e] - gscore : gscore - a.prev_nsucc[e]) : 0.f;
+      a.prev_nsucc[e] = gscore; a.prev_valid[e] = 1;
+      succ = !crash && nsucc == n;
+      // (max_timesteps_per_goal follows the env's own count, common/base.py:919-927)
+      const int max_t = a.num_active ? a.max_timesteps_per_goal_per_obj * n : a.max_timesteps_per_goal;
+      tk = env_tracker_process(e, a.steps, a.steps_since_last_goal, a.successes_so_far, a.consecutive, max_t, a.successes_needed, succ);
+      // reset_goal's reset_goal_steps and _previous_goal_distance = None (robot_env.py:893-909) inline: the goal itself comes from ra_recipe_kernel or the host
+      if (tk.newgoal) { tk.ssl = 0; a.steps_since_last_goal[e] = 0; a.prev_valid[e] = 0; }
+      r[1] = a.use_goal_distance_reward ? gdr : 0.f; r[2] = tk.got ? a.success_reward : 0.f;
+      if (a.reward_clip > 0.f) for (int k = 0; k < 3; k++) r[k] = fminf(fmaxf(r[k], -a.reward_clip), a.reward_clip);   // ClipRewardWrapper
+      done = done || tk.timeout || tk.trial || crash;
+    } else if (frozen == RA_OBS_EPISODE_START) {
+      // RobotEnv.reset -> reset_goal_generation -> _observe_sync -> update_goal_info (robot_env.py:757-792, 586-593): the observation that ends a reset
+      // establishes the success count the first step's goal-distance reward is measured from
+      a.prev_nsucc[e] = gscore; a.prev_valid[e] = 1;
     }
-  }
-  if (lane == 0 && frozen == 0) {
-    // ---- reward / done of the simulation (common/base.py:768-795)
-    float env_reward = 0.f;
-    int done = 0;
-    if (table_contact) env_reward -= a.penalty_table_collision;
-    if (any_off) { done = 1; env_reward -= a.penalty_objects_off_table; }
-    if (safety) env_reward -= a.penalty_safety_stop;
-    // ---- _get_goal_info: reward = change of the number of objects within both thresholds (common/base.py:824-848)
-    a.t[e] += 1;
-    const float gdr = (a.prev_valid[e] && !crash) ? (reach ? a.prev_nsucc[e] - gscore : gscore - a.prev_nsucc[e]) : 0.f;
-    a.prev_nsucc[e] = gscore; a.prev_valid[e] = 1;
-    const int succ = !crash && nsucc == n;
-    // (max_timesteps_per_goal follows the env's own count, common/base.py:919-927)
-    const int max_t = a.num_active ? a.max_timesteps_per_goal_per_obj * n : a.max_timesteps_per_goal;
-    EnvTracked tk = env_tracker_process(e, a.steps, a.steps_since_last_goal, a.successes_so_far, a.consecutive, max_t, a.successes_needed, succ);
-    // reset_goal's reset_goal_steps and _previous_goal_distance = None (robot_env.py:893-909) inline: the goal itself comes from ra_recipe_kernel or the host
-    if (tk.newgoal) { tk.ssl = 0; a.steps_since_last_goal[e] = 0; a.prev_valid[e] = 0; }
-    float* rw = a.reward + 3 * (size_t)e;
-    rw[0] = env_reward; rw[1] = a.use_goal_distance_reward ? gdr : 0.f; rw[2] = tk.got ? a.success_reward : 0.f;
-    if (a.reward_clip > 0.f) for (int k = 0; k < 3; k++) rw[k] = fminf(fmaxf(rw[k], -a.reward_clip), a.reward_clip);   // ClipRewardWrapper
+    float *rw = a.reward + 3 * (size_t)e, *tail = row + a.obs_dim;
+    for (int k = 0; k < 3; k++) rw[k] = tail[k] = r[k];
+    tail[3] = (float)done;
     a.goal_dist[2 * e] = sp; a.goal_dist[2 * e + 1] = sr;
-    if (a.goal_kind == 2) { a.goal_dist_extra[2 * e] = dgrip; a.goal_dist_extra[2 * e + 1] = grasp; }
-    done = done || tk.timeout || tk.trial || crash;
+    if (a.goal_kind == RA_GOAL_STACK) { a.goal_dist_extra[2 * e] = dgrip; a.goal_dist_extra[2 * e + 1] = grasp; }
     a.done[e] = done; a.goal_reset[e] = tk.newgoal; a.trial_success[e] = tk.trial; a.sub_goal_ok[e] = tk.got; a.env_crash[e] = crash;
     a.objects_off_table[e] = any_off; a.info_ssl[e] = tk.ssl;
-    const int g0 = 15 * N + 15 + 2 * nq;
-    row[g0 + 6 * N] = (float)succ;                          // is_goal_achieved
-    float* o = row + g0 + 21 * N + 1;
-    o[0] = (float)safety;
-    for (int k = 0; k < 3; k++) { o[1 + k] = sens[a.force_adr + k]; o[4 + k] = sens[a.torque_adr + k]; }
-    float* tail = row + a.obs_dim;
-    tail[0] = rw[0]; tail[1] = rw[1]; tail[2] = rw[2]; tail[3] = (float)done;
-    // ---- on_observations_updated: the solver world's gripper follows the main world's (joint position and control target)
-    if (a.solver_qpos) {
+    *achieved = (float)succ;
+    ra_write_safety(a, row, nq, safety, sens);
+    if (a.solver_qpos && frozen != RA_OBS_IN_RECIPE) {      // on_observations_updated: the solver world's gripper follows the main world's (joint position, control target)
       a.solver_qpos[(size_t)e * a.solver_nq + a.solver_grip_qposadr] = qrow[a.grip_qposadr];
       a.solver_ctrl[(size_t)e * a.solver_nu + a.solver_grip_act] = crow[a.grip_act];
     }
@@ -374,19 +350,23 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
 //   place_targets_with_fixed_position                              envs/rearrange/common/utils.py:884-919 (ObjectFixedStateGoal, goals/object_state_fixed.py)
 //   AttachedBlockStateGoal                                         envs/rearrange/goals/attached_block_state.py:17-68
 struct RaRecipeLds { int started, ended, regoal, moved; float pos[RA_MAXOBJ][3], gpos[RA_MAXOBJ][3], gyaw[RA_MAXOBJ], opos[3]; int n; };
+// rotate_bounding_box: half extents in x and y of object i's box turned about z by `yaw`
+__device__ inline void ra_yawed_half(const RaRecipeArgs& a, int i, float yaw, float& hx, float& hy) {
+  const float c = fabsf(cosf(yaw)), s_ = fabsf(sinf(yaw));
+  hx = c * a.obj_half[i][0] + s_ * a.obj_half[i][1]; hy = s_ * a.obj_half[i][0] + c * a.obj_half[i][1];
+}
+// world coordinate c (x: 0, y: 1) of the point at `v` in a placement area `off` from the table's low corner (summed left to right, at every call site)
+__device__ inline float ra_area_to_world(const RaRecipeArgs& a, float off, int c, float v) { return v + off - a.table_size[c] + a.table_pos[c]; }
+// z of object i's body origin when its box rests on the table top
+__device__ inline float ra_rest_z(const RaRecipeArgs& a, int i) { return a.obj_half[i][2] + 2.f * a.table_size[2] - a.table_size[2] + a.table_pos[2] - a.obj_center[i][2]; }
 
 // One placement of the first N objects (rotated about z by yaw[i]) inside the placement area: body origins in world coordinates.  Returns false when the rejection
-// sampling ran out of restarts (out = its last proposal).  `k`: this env's running draw index.  `no_grid`: place_objects_with_no_constraint even where the grid
+// sampling ran out of restarts (out = its last proposal).  `U`: this env's draws, in order.  `no_grid`: place_objects_with_no_constraint even where the grid
 // has cells enough (the stack and reach goals' own placement).  `ar`: the env's placement area (ra_area).
-__device__ inline bool ra_place(const RaRecipeArgs& a, const RaArea& ar, int N, bool no_grid, const float* yaw, int ystride, unsigned seed, unsigned step, unsigned e, unsigned& k, float (*out)[3]) {
-  auto U = [&]() -> float { return env_u01(seed, step, e, k++); };
+__device__ inline bool ra_place(const RaRecipeArgs& a, const RaArea& ar, int N, bool no_grid, const float* yaw, int ystride, RaDraws& U, float (*out)[3]) {
   float hx[RA_MAXOBJ], hy[RA_MAXOBJ], xy[RA_MAXOBJ][2];
   float mx = 0.f, my = 0.f;
-  for (int i = 0; i < N; i++) {      // rotate_bounding_box
-    const float c = fabsf(cosf(yaw[i * ystride])), s_ = fabsf(sinf(yaw[i * ystride]));
-    hx[i] = c * a.obj_half[i][0] + s_ * a.obj_half[i][1]; hy[i] = s_ * a.obj_half[i][0] + c * a.obj_half[i][1];
-    mx = fmaxf(mx, hx[i]); my = fmaxf(my, hy[i]);
-  }
+  for (int i = 0; i < N; i++) { ra_yawed_half(a, i, yaw[i * ystride], hx[i], hy[i]); mx = fmaxf(mx, hx[i]); my = fmaxf(my, hy[i]); }
   const float width = ar.size[0], height = ar.size[1];
   const int ncol = (int)floorf(width / (2.f * mx)), nrow = (int)floorf(height / (2.f * my));
   const int M = ncol * nrow;
@@ -434,25 +414,19 @@ __device__ inline bool ra_place(const RaRecipeArgs& a, const RaArea& ar, int N, 
   for (int i = 0; i < N; i++) {      // the body origin, from the centre of its bounding box
     const float c = cosf(yaw[i * ystride]), s_ = sinf(yaw[i * ystride]);
     const float ccx = c * a.obj_center[i][0] - s_ * a.obj_center[i][1], ccy = s_ * a.obj_center[i][0] + c * a.obj_center[i][1];
-    out[i][0] = xy[i][0] + ar.off[0] - a.table_size[0] + a.table_pos[0] - ccx;
-    out[i][1] = xy[i][1] + ar.off[1] - a.table_size[1] + a.table_pos[1] - ccy;
-    out[i][2] = a.obj_half[i][2] + 2.f * a.table_size[2] - a.table_size[2] + a.table_pos[2] - a.obj_center[i][2];
+    out[i][0] = ra_area_to_world(a, ar.off[0], 0, xy[i][0]) - ccx; out[i][1] = ra_area_to_world(a, ar.off[1], 1, xy[i][1]) - ccy; out[i][2] = ra_rest_z(a, i);
   }
   return ok;
 }
 
-// place_targets_with_goal_distance_ratio (common/utils.py:922-994) through _place_objects (:623-716): per object, in object order, a uniform proposal for the centre of
-// its bounding box inside the placement area, pulled toward the object's own position (`qrow`: the env's qpos row) by clip(ratio, dmin / dist if dist >= dmin else 0, 1),
-// rejected while its box overlaps a goal already placed; an object that runs out of its 1 + 20 proposals restarts the set, up to 100 sets.  Returns false when those ran
-// out (out = the last proposals).
-__device__ inline bool ra_place_near(const RaRecipeArgs& a, const RaArea& ar, int N, const float* yaw, int ystride, const float* qrow, float ratio_in, unsigned seed, unsigned step, unsigned e, unsigned& k,
-                                     float (*out)[3]) {
-  auto U = [&]() -> float { return env_u01(seed, step, e, k++); };
+// place_targets_with_goal_distance_ratio (common/utils.py:922-994) through _place_objects (:623-716), as ra_recipe_args' goal kind RA_GOAL_TRAIN describes it
+// (include/rgstep.h); `qrow`: the env's qpos row.  Returns false when the 100 sets of 1 + 20 proposals per object ran out (out = the last proposals).
+__device__ inline bool ra_place_near(const RaRecipeArgs& a, const RaArea& ar, int N, const float* yaw, int ystride, const float* qrow, float ratio_in, RaDraws& U, float (*out)[3]) {
   float hx[RA_MAXOBJ], hy[RA_MAXOBJ], cx[RA_MAXOBJ], cy[RA_MAXOBJ], px[RA_MAXOBJ], py[RA_MAXOBJ];
   const float width = ar.size[0], height = ar.size[1];
   for (int i = 0; i < N; i++) {
     const float c = cosf(yaw[i * ystride]), s_ = sinf(yaw[i * ystride]);
-    hx[i] = fabsf(c) * a.obj_half[i][0] + fabsf(s_) * a.obj_half[i][1]; hy[i] = fabsf(s_) * a.obj_half[i][0] + fabsf(c) * a.obj_half[i][1];
+    ra_yawed_half(a, i, yaw[i * ystride], hx[i], hy[i]);
     cx[i] = c * a.obj_center[i][0] - s_ * a.obj_center[i][1]; cy[i] = s_ * a.obj_center[i][0] + c * a.obj_center[i][1];
     px[i] = py[i] = 0.f;
   }
@@ -479,20 +453,15 @@ __device__ inline bool ra_place_near(const RaRecipeArgs& a, const RaArea& ar, in
     }
   }
   for (int i = 0; i < N; i++) {
-    out[i][0] = px[i] - cx[i] + ar.off[0] - a.table_size[0] + a.table_pos[0];
-    out[i][1] = py[i] - cy[i] + ar.off[1] - a.table_size[1] + a.table_pos[1];
-    out[i][2] = a.obj_half[i][2] + 2.f * a.table_size[2] - a.table_size[2] + a.table_pos[2] - a.obj_center[i][2];
+    out[i][0] = ra_area_to_world(a, ar.off[0], 0, px[i] - cx[i]); out[i][1] = ra_area_to_world(a, ar.off[1], 1, py[i] - cy[i]); out[i][2] = ra_rest_z(a, i);
   }
   return ok;
 }
 
-// DominoStateGoal._create_new_domino_position_and_rotation / _adjust_and_check_fit / _sample_next_goal_positions (goals/dominos.py:20-150): per attempt offset = u pi and
-// delta = u pi / 4 - pi / 8; domino k gets the yaw k delta + offset + delta / 2 and stands where the chain of steps object_size * domino_distance_mul along
-// (cos, sin)(j delta + offset), j = 1 .. k, ends (the first at the origin); an attempt is taken when the chain's extent with the yawed half sizes is STRICTLY smaller than
-// the placement area, and is then shifted by a uniform offset inside what is left.  z: the box's half height on the table top.  Returns false after MAX_RETRY = 1000
-// attempts, with zero positions as the reference returns them (gyaw = the last attempt's).  Two passes over the chain per attempt instead of per-domino arrays.
-__device__ inline bool ra_domino_arc(const RaRecipeArgs& a, int N, unsigned seed, unsigned step, unsigned e, unsigned& k, float* gyaw, float (*out)[3]) {
-  auto U = [&]() -> float { return env_u01(seed, step, e, k++); };
+// DominoStateGoal._create_new_domino_position_and_rotation / _adjust_and_check_fit / _sample_next_goal_positions (goals/dominos.py:20-150), as ra_recipe_args' goal kind
+// RA_GOAL_DOMINOS describes it (include/rgstep.h).  z: the box's half height on the table top.  Returns false after MAX_RETRY = 1000 attempts, with zero positions as
+// the reference returns them (gyaw = the last attempt's).  Two passes over the chain per attempt instead of per-domino arrays.
+__device__ inline bool ra_domino_arc(const RaRecipeArgs& a, int N, RaDraws& U, float* gyaw, float (*out)[3]) {
   const float dist = a.object_size * a.domino_distance_mul, width = a.area_size[0], height = a.area_size[1];
   for (int attempt = 0; attempt < 1000; attempt++) {
     const float offset = U() * RBC_PI, delta = U() * (0.25f * RBC_PI) - 0.125f * RBC_PI;
@@ -500,15 +469,14 @@ __device__ inline bool ra_domino_arc(const RaRecipeArgs& a, int N, unsigned seed
     for (int i = 0; i < N; i++) {
       if (i > 0) { const float t = (float)i * delta + offset; x += cosf(t) * dist; y += sinf(t) * dist; }
       const float yw = (float)i * delta + (offset + 0.5f * delta);
-      const float c = fabsf(cosf(yw)), s_ = fabsf(sinf(yw));
-      const float hx = c * a.obj_half[i][0] + s_ * a.obj_half[i][1], hy = s_ * a.obj_half[i][0] + c * a.obj_half[i][1];      // rotate_bounding_box
+      float hx, hy;
+      ra_yawed_half(a, i, yw, hx, hy);
       gyaw[i] = yw; out[i][0] = x; out[i][1] = y;
       min_x = fminf(min_x, x - hx); max_x = fmaxf(max_x, x + hx); min_y = fminf(min_y, y - hy); max_y = fmaxf(max_y, y + hy);
     }
     const float size_x = max_x - min_x, size_y = max_y - min_y;
     if (size_x < width && size_y < height) {
-      const float dx = -min_x + U() * (width - size_x) + a.area_offset[0] - a.table_size[0] + a.table_pos[0];
-      const float dy = -min_y + U() * (height - size_y) + a.area_offset[1] - a.table_size[1] + a.table_pos[1];
+      const float dx = ra_area_to_world(a, a.area_offset[0], 0, -min_x + U() * (width - size_x)), dy = ra_area_to_world(a, a.area_offset[1], 1, -min_y + U() * (height - size_y));
       for (int i = 0; i < N; i++) { out[i][0] += dx; out[i][1] += dy; out[i][2] = a.obj_half[i][2] + a.table_size[2] + a.table_pos[2]; }
       return true;
     }
@@ -521,8 +489,7 @@ __device__ inline bool ra_domino_arc(const RaRecipeArgs& a, int N, unsigned seed
 // inside the placement area -- no bounding-box-centre correction in x and y --, z from the box's half height and centre on the table top.  Always valid.
 __device__ inline void ra_place_fixed(const RaRecipeArgs& a, int N, const float (*rel)[2], float (*out)[3]) {
   for (int i = 0; i < N; i++) {
-    out[i][0] = rel[i][0] * a.area_size[0] + a.area_offset[0] - a.table_size[0] + a.table_pos[0];
-    out[i][1] = rel[i][1] * a.area_size[1] + a.area_offset[1] - a.table_size[1] + a.table_pos[1];
+    out[i][0] = ra_area_to_world(a, a.area_offset[0], 0, rel[i][0] * a.area_size[0]); out[i][1] = ra_area_to_world(a, a.area_offset[1], 1, rel[i][1] * a.area_size[1]);
     out[i][2] = a.obj_half[i][2] + 2.f * a.table_size[2] - a.obj_center[i][2] - a.table_size[2] + a.table_pos[2];
   }
 }
@@ -534,8 +501,7 @@ __device__ inline void ra_place_fixed(const RaRecipeArgs& a, int N, const float 
 // of cells 2 object_size apart (object_size: the HALF size).  Block i goes to cell order[i] of a random permutation (Fisher-Yates); the lattice's origin is one uniform
 // draw in [rel, 1 - extent - rel] per axis, rel = object_size / (width, height): the outermost boxes stay inside the placement area.  `rel`: the table ra_place_fixed takes.
 #define RA_ATTACHED_N 8
-__device__ inline void ra_attached_table(const RaRecipeArgs& a, unsigned seed, unsigned step, unsigned e, unsigned& k, float (*rel)[2]) {
-  auto U = [&]() -> float { return env_u01(seed, step, e, k++); };
+__device__ inline void ra_attached_table(const RaRecipeArgs& a, RaDraws& U, float (*rel)[2]) {
   const int cell_x[RA_ATTACHED_N] = {1, 2, 0, 1, 2, 3, 1, 2}, cell_y[RA_ATTACHED_N] = {0, 0, 1, 1, 1, 1, 2, 2};
   int order[RA_ATTACHED_N];
   for (int i = 0; i < RA_ATTACHED_N; i++) order[i] = i;
@@ -549,6 +515,153 @@ __device__ inline void ra_attached_table(const RaRecipeArgs& a, unsigned seed, u
   }
 }
 
+// ---- lane 0's sections of ra_recipe_kernel, in the order the kernel calls them
+// An env inside the recipe, one step counted: the stage that ran out hands over to the next -- stabilise -> (n_random_initial_steps >= 1: one random action -> zero
+// action while everything settles ->) the episode starts: tracker reset, a fresh smoothing filter (the first goal follows: ra_sample_goal).
+__device__ inline void ra_stage_step(const RaRecipeArgs& a, int e, int& st, int& lf, int& started, int& stabilised) {
+  const int AD = a.action_dim;
+  if (--lf > 0) return;
+  if (st == RA_STAGE_STABILISE) {
+    stabilised = 1;                                                    // stabilize_objects restores the objects' damping (ra_param_rows_kernel / a host tensor op on this mask)
+    if (a.n_random_initial_steps >= 1) {
+      st = RA_STAGE_RANDOM_ACTION; lf = a.n_random_initial_steps;
+      for (int d = 0; d < AD; d++) a.scripted[(size_t)e * AD + d] = 2.f * env_u01(a.seed, a.step, (unsigned)e, (unsigned)d) - 1.f;
+      a.solver_active[e] = 1; a.hold_ctrl[e] = 0;
+    } else started = 1;
+  } else if (st == RA_STAGE_RANDOM_ACTION) {
+    st = RA_STAGE_SETTLE; lf = a.settle_steps;
+    for (int d = 0; d < AD; d++) a.scripted[(size_t)e * AD + d] = 0.f;
+  } else started = 1;
+  if (!started) return;
+  st = RA_STAGE_LIVE; lf = 0;
+  a.t[e] = 0; a.steps[e] = 0; a.steps_since_last_goal[e] = 0; a.successes_so_far[e] = 0; a.consecutive[e] = 0; a.ema_t[e] = 0;
+  a.hold[e] = 0; a.hold_ctrl[e] = 0; a.frozen[e] = RA_OBS_STEP; a.solver_active[e] = 1; a.resetting[e] = 0; a.episode_started[e] = 1;
+  for (int d = 0; d < AD; d++) { a.scripted[(size_t)e * AD + d] = 0.f; a.ema_value[(size_t)e * AD + d] = 0.f; a.action_ema[(size_t)e * AD + d] = 0.f; }
+}
+// A new goal for env e into F.gyaw / F.gpos (F.opos, F.moved: the reach goals' moved object), from the yaws gy[i * gstride].  The goal's draws come from a stream of
+// their own, RA_STREAM_GOAL: an env can get a new goal and end its episode on the same step.
+__device__ inline void ra_sample_goal(const RaRecipeArgs& a, RaRecipeLds& F, int e, int n, const float* qrow, const float* gy, int gstride) {
+  const int N = a.num_objects, kind = a.goal_kind;
+  F.moved = 0;
+  RaDraws UG = {a.seed ^ RA_STREAM_GOAL, a.step, (unsigned)e, 0u};
+  // the goal's yaws: the ones it has, or -- randomize_quaternion_along_z, drawn before the positions -- those turned by U(0, 2 pi) each; the placements below work
+  // with the boxes rotated by THESE
+  for (int i = 0; i < N; i++) F.gyaw[i] = gy[i * gstride];
+  if (a.randomize_goal_rot) for (int i = 0; i < n; i++) F.gyaw[i] += 2.f * RBC_PI * env_u01(a.seed ^ RA_STREAM_GOAL_YAW, a.step, (unsigned)e, (unsigned)i);
+  // (the fixed placements call set_target_quat inside _sample_next_goal_positions, after the randomisation: their goals have init_quats' yaws, always)
+  if (kind == RA_GOAL_ATTACHED) for (int i = 0; i < N; i++) F.gyaw[i] = 0.f;
+  if (kind == RA_GOAL_FIXED) for (int i = 0; i < N; i++) F.gyaw[i] = a.fixed_yaw[i];
+  const RaArea ar = ra_area(a, n);
+  bool ok = true;
+  // (the kinds of ra_kind_is_counted place the env's n active objects; the others are built without per-env counts: n = N)
+  switch (kind) {
+    case RA_GOAL_OBJECT_STATE: case RA_GOAL_PICKANDPLACE:
+      ok = ra_place(a, ar, n, false, F.gyaw, 1, UG, F.gpos);
+      if (kind == RA_GOAL_PICKANDPLACE) {                              // move_one_object_to_the_air: height first, then the object
+        const float h = a.height_range[0] + UG() * (a.height_range[1] - a.height_range[0]);
+        int i = (int)(UG() * (float)n); i = i > n - 1 ? n - 1 : i;
+        F.gpos[i][2] += h;
+      }
+      break;
+    case RA_GOAL_STACK: {                                              // ObjectStackGoal: object 0's box placed, the others on top of it in block order
+      float bot[1][3];
+      ok = ra_place(a, ar, 1, true, F.gyaw, 1, UG, bot);
+      int order[RA_MAXOBJ];
+      for (int i = 0; i < n; i++) order[i] = i;
+      if (!a.fixed_order)
+        for (int i = n - 1; i > 0; i--) { int j = (int)(UG() * (float)(i + 1)); j = j > i ? i : j; const int tmp = order[i]; order[i] = order[j]; order[j] = tmp; }
+      for (int i = 0; i < n; i++) { F.gpos[order[i]][0] = bot[0][0]; F.gpos[order[i]][1] = bot[0][1]; F.gpos[order[i]][2] = bot[0][2] + (float)i * 2.f * a.object_size; }
+    } break;
+    case RA_GOAL_TRAIN: {                                              // TrainStateGoal (goals/train_state.py:81-113): goals near the objects, then one in the air or a tower
+      const float ratio = a.goal_distance_ratio ? a.goal_distance_ratio[e] : 1.f;
+      ok = ra_place_near(a, ar, n, F.gyaw, 1, qrow, ratio, UG, F.gpos);
+      if (a.pickup_proba + a.stacking_proba > 0.f) {                   // move_one_object_to_the_air_with_restrictions (:13-78)
+        const float p = UG();
+        if (p > a.pickup_proba + a.stacking_proba) {
+        } else if (p < a.pickup_proba) {
+          const float h = a.height_range[0] + UG() * (a.height_range[1] - a.height_range[0]);
+          int i = (int)(UG() * (float)n); i = i > n - 1 ? n - 1 : i;
+          F.gpos[i][2] += h * ratio;
+        } else if (n >= 2) {                                           // a tower of 2..n objects: a random subset in random order, from this env's stream
+          int tower = 2 + (int)(UG() * (float)(n - 1)); tower = tower > n ? n : tower;
+          int order[RA_MAXOBJ];
+          for (int i = 0; i < n; i++) order[i] = i;
+          for (int t = 0; t < tower; t++) { int j = t + (int)(UG() * (float)(n - t)); j = j > n - 1 ? n - 1 : j; const int tmp = order[t]; order[t] = order[j]; order[j] = tmp; }
+          for (int h = 1; h < tower; h++) {
+            F.gpos[order[h]][0] = F.gpos[order[0]][0]; F.gpos[order[h]][1] = F.gpos[order[0]][1]; F.gpos[order[h]][2] += a.object_size * (float)h * 2.f;
+          }
+        }
+      }
+    } break;
+    case RA_GOAL_DOMINOS:                                              // DominoStateGoal (goals/dominos.py:53-150): the dominos on a circle arc
+      ok = ra_domino_arc(a, N, UG, F.gyaw, F.gpos); break;
+    case RA_GOAL_ATTACHED: {                                           // AttachedBlockStateGoal: a permutation and an origin, then the fixed placement (N = 8: the host checks)
+      float rel[RA_ATTACHED_N][2];
+      ra_attached_table(a, UG, rel);
+      ra_place_fixed(a, RA_ATTACHED_N, rel, F.gpos);
+    } break;
+    case RA_GOAL_FIXED:                                                // ObjectFixedStateGoal: the caller's table
+      ra_place_fixed(a, N, a.fixed_xy, F.gpos); break;
+    case RA_GOAL_REACH: case RA_GOAL_DET_REACH:                        // the object goes to the placement, the goal target_height above it
+      if (kind == RA_GOAL_REACH) {
+        ok = ra_place(a, ar, 1, true, F.gyaw, 1, UG, F.gpos);
+      } else {
+        const int gi = (a.goal_index[e] + 1) & 1;
+        a.goal_index[e] = gi;
+        for (int c = 0; c < 3; c++) F.gpos[0][c] = a.det_points[gi][c];
+      }
+      for (int c = 0; c < 3; c++) F.opos[c] = F.gpos[0][c];
+      F.gpos[0][2] += a.target_height; F.moved = 1;
+      break;
+  }
+  if (!ok) a.placement_failed[e] += 1;
+}
+// _randomize_object_groups, the first act of RearrangeEnv._reset: sample_group_counts (common/utils.py:47-73) over the env's n objects -- until they are used up:
+// lam ~ U(sample_lam), a count c in 1..remaining with probability proportional to exp(-c lam) (the inverse of its cumulative sum at a second uniform); group g = the
+// next c objects.  A stream of its own, RA_STREAM_GROUPS from RA_DRAW_GROUPS: disjoint from the placement's draws however often that restarts.
+__device__ inline void ra_sample_groups(const RaRecipeArgs& a, int e, int n) {
+  const int N = a.num_objects;
+  RaDraws UR = {a.seed ^ RA_STREAM_GROUPS, a.step, (unsigned)e, RA_DRAW_GROUPS};
+  int* grow = a.obj_group + (size_t)e * N;
+  for (int i = n; i < N; i++) grow[i] = -1;                             // (a padded slot belongs to no group)
+  for (int first = 0, g = 0; first < n; g++) {
+    const int rem = n - first;
+    const float lam = a.sample_lam[0] + UR() * (a.sample_lam[1] - a.sample_lam[0]);
+    const float q = expf(-lam);
+    float total = 0.f, w = 1.f;                                        // weights exp(-(c - 1) lam): the common factor exp(-lam) cancels
+    for (int c = 1; c <= rem; c++) { total += w; w *= q; }
+    const float target = UR() * total;
+    int c = 1; float cum = 1.f; w = q;
+    while (c < rem && !(target < cum)) { cum += w; w *= q; c++; }
+    for (int i = 0; i < c; i++) grow[first + i] = g;
+    first += c;
+  }
+}
+// An episode ended: its recipe begins.  The count of the episode that begins is latched (RearrangeEnv._reset re-creates the simulation with the current num_objects,
+// common/base.py:850-856, 904), the groups sampled, the objects' yaws and placement drawn into a.yaw / F.pos, and the rows that hold the env set.
+__device__ inline void ra_begin_recipe(const RaRecipeArgs& a, RaRecipeLds& F, int e, int& n, int& st, int& lf) {
+  const int N = a.num_objects, AD = a.action_dim;
+  if (a.num_active) { n = a.num_objects_next[e]; n = n < 1 ? 1 : (n > N ? N : n); a.num_active[e] = n; }
+  if (a.obj_group && a.group_mode == RA_GROUPS_SAMPLE) ra_sample_groups(a, e, n);
+  RaDraws U = {a.seed, a.step, (unsigned)e, RA_DRAW_PLACEMENT};
+  float* yw = a.yaw + (size_t)e * N;
+  for (int i = 0; i < N; i++) yw[i] = i < n ? 2.f * RBC_PI * U() : 0.f;
+  if (!ra_place(a, ra_area(a, n), n, false, yw, 1, U, F.pos)) a.placement_failed[e] += 1;
+  st = RA_STAGE_STABILISE; lf = a.stabilize_steps > 0 ? a.stabilize_steps : 1;
+  a.hold[e] = 1; a.hold_ctrl[e] = 1; a.frozen[e] = RA_OBS_IN_RECIPE; a.solver_active[e] = 0; a.resetting[e] = 1;
+  for (int d = 0; d < AD; d++) a.scripted[(size_t)e * AD + d] = 0.f;
+}
+// Entry i of a qpos row in which the env's n active objects sit at pos[o], turned about z by yaw[o] (`wrap`: normalised first), and the others at their parking
+// poses (ra_recipe_args.park_pose); `v` where no object lives.
+__device__ inline float ra_qpos_with_objects(const RaRecipeArgs& a, int i, int n, float v, const float (*pos)[3], const float* yaw, bool wrap) {
+  for (int o = 0; o < a.num_objects; o++) {
+    const int d = i - a.obj_qposadr[o];
+    if (d < 0 || d >= 7) continue;
+    const float ez = wrap ? rbc_wrap(yaw[o]) : yaw[o];
+    v = o >= n ? a.park_pose[o][d] : (d < 3 ? pos[o][d] : (d == 3 ? cosf(0.5f * ez) : (d == 6 ? sinf(0.5f * ez) : 0.f)));
+  }
+  return v;
+}
 __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbBatchDev bt, const RbModelDev* sp, RbBatchDev sb, RaRecipeArgs a) {
 #ifdef RG_EMUL
   RaRecipeLds& F = *(RaRecipeLds*)emul_lds();
@@ -558,167 +671,40 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
   const RbModelDev& m = *mp;
   const int e = blockIdx.x, lane = threadIdx.x;
   if (e >= bt.B) return;
-  const int N = a.num_objects, AD = a.action_dim, nq = m.nq;
+  const int N = a.num_objects, nq = m.nq;
   if (a.active && !a.active[e]) return;                                // (uniform over the workgroup: an env outside the launch keeps every row)
   // the synchronous episode API (ra_recipe_args.sync_mode): a forced end takes the env out of whatever stage it was in and ends its episode whatever `done` says; a
   // regoal-only launch runs the live env's next-goal branch and neither counts a stage nor ends an episode.  Both draw what the pipelined launch of this `step` draws
   const bool forced = a.sync_mode == RA_SYNC_FORCED_END, regoal_only = a.sync_mode == RA_SYNC_REGOAL_ONLY;
   if (lane == 0) {
-    int st = forced ? 0 : a.stage[e], lf = forced ? 0 : a.left[e];
+    int st = forced ? RA_STAGE_LIVE : a.stage[e], lf = forced ? 0 : a.left[e];
     int started = 0, ended = 0, regoal = 0, stabilised = 0;
-    unsigned k = 0;
-    auto U = [&]() -> float { return env_u01(a.seed, a.step, (unsigned)e, k++); };
-    // per-env object counts: the env's first n objects are in use (latched below when an episode ends); without them n = N and every line is the one it was
+    // per-env object counts: the env's first n objects are in use (latched by ra_begin_recipe when an episode ends); without them n = N and every line is the one it was
     int n = N;
     if (a.num_active) { n = a.num_active[e]; n = n < 1 ? 1 : (n > N ? N : n); }
     if (!regoal_only) a.episode_started[e] = 0;
-    // ---- an env inside the recipe: this step counted
-    if (st > 0 && !regoal_only) {
-      lf -= 1;
-      if (lf <= 0) {
-        if (st == 1) {
-          stabilised = 1;                                              // stabilize_objects restores the objects' damping (host tensor op on this mask)
-          if (a.n_random_initial_steps >= 1) {                         // -> one random action for n_random_initial_steps steps
-            st = 2; lf = a.n_random_initial_steps;
-            for (int d = 0; d < AD; d++) a.scripted[(size_t)e * AD + d] = 2.f * U() - 1.f;
-            a.solver_active[e] = 1; a.hold_ctrl[e] = 0;
-          } else started = 1;
-        } else if (st == 2) {                                          // -> zero action while everything settles
-          st = 3; lf = a.settle_steps;
-          for (int d = 0; d < AD; d++) a.scripted[(size_t)e * AD + d] = 0.f;
-        } else started = 1;
-      }
-    }
-    const float* gy = 0; int gstride = 1;
-    if (started) {                                                     // -> the episode starts: tracker reset, a fresh smoothing filter, the first goal
-      st = 0; lf = 0;
-      a.t[e] = 0; a.steps[e] = 0; a.steps_since_last_goal[e] = 0; a.successes_so_far[e] = 0; a.consecutive[e] = 0; a.ema_t[e] = 0;
-      a.hold[e] = 0; a.hold_ctrl[e] = 0; a.frozen[e] = 0; a.solver_active[e] = 1; a.resetting[e] = 0; a.episode_started[e] = 1;
-      for (int d = 0; d < AD; d++) { a.scripted[(size_t)e * AD + d] = 0.f; a.ema_value[(size_t)e * AD + d] = 0.f; a.action_ema[(size_t)e * AD + d] = 0.f; }
-      gy = a.yaw + (size_t)e * N; gstride = 1;
-    } else if (!forced && st == 0 && a.goal_reset[e] && !a.done[e]) {  // a live env that reached its goal: ObjectStateGoal.next_goal keeps the goal's yaw
+    if (st != RA_STAGE_LIVE && !regoal_only) ra_stage_step(a, e, st, lf, started, stabilised);      // an env inside the recipe: this step counted
+    const float* gy = 0; int gstride = 1;                              // the yaws the new goal starts from, if this step makes one
+    if (started) {                                                     // the episode's first goal: the objects' yaws
+      gy = a.yaw + (size_t)e * N;
+    } else if (!forced && st == RA_STAGE_LIVE && a.goal_reset[e] && !a.done[e]) {  // a live env that reached its goal: ObjectStateGoal.next_goal keeps the goal's yaw
       // (not when the episode ends on the same step -- objects off the table while every object sits within its thresholds --: the begin-of-episode state written
       //  below would be what the goal's re-observation reads; the terminal observation keeps the reached goal's entries, on this path and on the host path alike)
       regoal = 1;
       gy = a.goal_rot + (size_t)e * N * 3 + 2; gstride = 3;
     }
-    if (gy) {
-      k = 0u;     // (the goal's placement draws from its own stream: an env can get a new goal and end its episode on the same step)
-      const unsigned gseed = a.seed ^ 0x9E3779B9u;
-      auto UG = [&]() -> float { return env_u01(gseed, a.step, (unsigned)e, k++); };
-      const int kind = a.goal_kind;
-      F.moved = 0;
-      // the goal's yaws: the ones it has, or -- randomize_quaternion_along_z, drawn before the positions -- those turned by U(0, 2 pi) each; the placements below work
-      // with the boxes rotated by THESE
-      for (int i = 0; i < N; i++) F.gyaw[i] = gy[i * gstride];
-      if (a.randomize_goal_rot) for (int i = 0; i < n; i++) F.gyaw[i] += 2.f * RBC_PI * env_u01(a.seed ^ 0xC2B2AE35u, a.step, (unsigned)e, (unsigned)i);
-      // (the fixed placements call set_target_quat inside _sample_next_goal_positions, after the randomisation: their goals have init_quats' yaws, always)
-      if (kind == 7) for (int i = 0; i < N; i++) F.gyaw[i] = 0.f;
-      if (kind == 8) for (int i = 0; i < N; i++) F.gyaw[i] = a.fixed_yaw[i];
-      gy = F.gyaw; gstride = 1;
-      const RaArea ar = ra_area(a, n);
-      // (kinds 0, 1, 2 and 5 place the env's n active objects; the others are built without per-env counts: n = N)
-      if (kind <= 1) {
-        if (!ra_place(a, ar, n, false, gy, gstride, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
-        if (kind == 1) {                                               // move_one_object_to_the_air: height first, then the object
-          const float h = a.height_range[0] + UG() * (a.height_range[1] - a.height_range[0]);
-          int i = (int)(UG() * (float)n); i = i > n - 1 ? n - 1 : i;
-          F.gpos[i][2] += h;
-        }
-      } else if (kind == 2) {                                          // ObjectStackGoal: object 0's box placed, the others on top of it in block order
-        float bot[1][3];
-        if (!ra_place(a, ar, 1, true, gy, gstride, gseed, a.step, (unsigned)e, k, bot)) a.placement_failed[e] += 1;
-        int order[RA_MAXOBJ];
-        for (int i = 0; i < n; i++) order[i] = i;
-        if (!a.fixed_order)
-          for (int i = n - 1; i > 0; i--) { int j = (int)(UG() * (float)(i + 1)); j = j > i ? i : j; const int tmp = order[i]; order[i] = order[j]; order[j] = tmp; }
-        for (int i = 0; i < n; i++) { F.gpos[order[i]][0] = bot[0][0]; F.gpos[order[i]][1] = bot[0][1]; F.gpos[order[i]][2] = bot[0][2] + (float)i * 2.f * a.object_size; }
-      } else if (kind == 5) {                                          // TrainStateGoal (goals/train_state.py:81-113): goals near the objects, then one in the air or a tower
-        const float ratio = a.goal_distance_ratio ? a.goal_distance_ratio[e] : 1.f;
-        if (!ra_place_near(a, ar, n, gy, gstride, bt.qpos + (size_t)e * nq, ratio, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
-        if (a.pickup_proba + a.stacking_proba > 0.f) {                 // move_one_object_to_the_air_with_restrictions (:13-78)
-          const float p = UG();
-          if (p > a.pickup_proba + a.stacking_proba) {
-          } else if (p < a.pickup_proba) {
-            const float h = a.height_range[0] + UG() * (a.height_range[1] - a.height_range[0]);
-            int i = (int)(UG() * (float)n); i = i > n - 1 ? n - 1 : i;
-            F.gpos[i][2] += h * ratio;
-          } else if (n >= 2) {                                         // a tower of 2..n objects: a random subset in random order, from this env's stream
-            int tower = 2 + (int)(UG() * (float)(n - 1)); tower = tower > n ? n : tower;
-            int order[RA_MAXOBJ];
-            for (int i = 0; i < n; i++) order[i] = i;
-            for (int t = 0; t < tower; t++) { int j = t + (int)(UG() * (float)(n - t)); j = j > n - 1 ? n - 1 : j; const int tmp = order[t]; order[t] = order[j]; order[j] = tmp; }
-            for (int h = 1; h < tower; h++) {
-              F.gpos[order[h]][0] = F.gpos[order[0]][0]; F.gpos[order[h]][1] = F.gpos[order[0]][1]; F.gpos[order[h]][2] += a.object_size * (float)h * 2.f;
-            }
-          }
-        }
-      } else if (kind == 6) {                                          // DominoStateGoal (goals/dominos.py:53-150): the dominos on a circle arc
-        if (!ra_domino_arc(a, N, gseed, a.step, (unsigned)e, k, F.gyaw, F.gpos)) a.placement_failed[e] += 1;
-      } else if (kind == 7) {                                          // AttachedBlockStateGoal: a permutation and an origin, then the fixed placement (N = 8: the host checks)
-        float rel[RA_ATTACHED_N][2];
-        ra_attached_table(a, gseed, a.step, (unsigned)e, k, rel);
-        ra_place_fixed(a, RA_ATTACHED_N, rel, F.gpos);
-      } else if (kind == 8) {                                          // ObjectFixedStateGoal: the caller's table
-        ra_place_fixed(a, N, a.fixed_xy, F.gpos);
-      } else {                                                         // reach: the object goes to the placement, the goal target_height above it
-        if (kind == 3) {
-          if (!ra_place(a, ar, 1, true, gy, gstride, gseed, a.step, (unsigned)e, k, F.gpos)) a.placement_failed[e] += 1;
-        } else {
-          const int gi = (a.goal_index[e] + 1) & 1;
-          a.goal_index[e] = gi;
-          for (int c = 0; c < 3; c++) F.gpos[0][c] = a.det_points[gi][c];
-        }
-        for (int c = 0; c < 3; c++) F.opos[c] = F.gpos[0][c];
-        F.gpos[0][2] += a.target_height;
-        F.moved = 1;
-      }
-    }
+    if (gy) ra_sample_goal(a, F, e, n, bt.qpos + (size_t)e * nq, gy, gstride);
     // ---- an episode that ended on this step: its recipe begins (the returned observation / reward / done are the terminal ones)
-    if (!started && st == 0 && (forced || a.done[e]) && !regoal_only) {
-      ended = 1;
-      // the count of the episode that begins: RearrangeEnv._reset re-creates the simulation with the current num_objects (common/base.py:850-856, 904)
-      if (a.num_active) { n = a.num_objects_next[e]; n = n < 1 ? 1 : (n > N ? N : n); a.num_active[e] = n; }
-      if (a.obj_group && a.group_mode == 1) {                          // _randomize_object_groups, the first act of RearrangeEnv._reset: sample_group_counts
-        // (common/utils.py:47-73) -- until the objects are used up: lam ~ U(sample_lam), a count c in 1..remaining with probability proportional to exp(-c lam)
-        // (the inverse of its cumulative sum at a second uniform); group g = the next c objects.  A stream of its own (seed ^ constant, as the goal's): disjoint from
-        // the placement's draws however often that restarts
-        k = 3000u;
-        const unsigned grseed = a.seed ^ 0x85EBCA6Bu;
-        auto UR = [&]() -> float { return env_u01(grseed, a.step, (unsigned)e, k++); };
-        int* grow = a.obj_group + (size_t)e * N;
-        for (int i = n; i < N; i++) grow[i] = -1;                       // (a padded slot belongs to no group)
-        for (int first = 0, g = 0; first < n; g++) {
-          const int rem = n - first;
-          const float lam = a.sample_lam[0] + UR() * (a.sample_lam[1] - a.sample_lam[0]);
-          const float q = expf(-lam);
-          float total = 0.f, w = 1.f;                                  // weights exp(-(c - 1) lam): the common factor exp(-lam) cancels
-          for (int c = 1; c <= rem; c++) { total += w; w *= q; }
-          const float target = UR() * total;
-          int c = 1; float cum = 1.f; w = q;
-          while (c < rem && !(target < cum)) { cum += w; w *= q; c++; }
-          for (int i = 0; i < c; i++) grow[first + i] = g;
-          first += c;
-        }
-      }
-      k = 1000u;
-      float* yw = a.yaw + (size_t)e * N;
-      for (int i = 0; i < n; i++) yw[i] = 2.f * RBC_PI * U();
-      for (int i = n; i < N; i++) yw[i] = 0.f;
-      if (!ra_place(a, ra_area(a, n), n, false, yw, 1, a.seed, a.step, (unsigned)e, k, F.pos)) a.placement_failed[e] += 1;
-      st = 1; lf = a.stabilize_steps > 0 ? a.stabilize_steps : 1;
-      a.hold[e] = 1; a.hold_ctrl[e] = 1; a.frozen[e] = 4; a.solver_active[e] = 0; a.resetting[e] = 1;
-      for (int d = 0; d < AD; d++) a.scripted[(size_t)e * AD + d] = 0.f;
-    }
+    if (!started && st == RA_STAGE_LIVE && (forced || a.done[e]) && !regoal_only) { ended = 1; ra_begin_recipe(a, F, e, n, st, lf); }
     // controller ticks of the NEXT step's main-world launch: two for live envs, one inside the recipe, two on the recipe's last step
     // (reach: one on the recipe's last step -- the goal moves the object, the forward of _observe_sync follows it: the host's launch over the reobserve codes)
-    const int last_stage = a.n_random_initial_steps >= 1 ? 3 : 1;
+    const int last_stage = a.n_random_initial_steps >= 1 ? RA_STAGE_SETTLE : RA_STAGE_STABILISE;
     if (!regoal_only) {                                                // (a regoal-only launch leaves stage, left and the next step's launch rows as they are)
-      a.nticks[e] = st > 0 ? ((st == last_stage && lf <= 1 && !(a.goal_kind == 3 || a.goal_kind == 4)) ? 2 : 1) : 2;
+      a.nticks[e] = st != RA_STAGE_LIVE ? ((st == last_stage && lf <= 1 && !ra_kind_is_reach(a.goal_kind)) ? 2 : 1) : 2;
       a.stage[e] = st; a.left[e] = lf;
       a.ended[e] = (unsigned char)ended; a.stabilised[e] = (unsigned char)stabilised;
     }
-    a.reobserve[e] = started ? 1 : (regoal ? 3 : 2);
+    a.reobserve[e] = started ? RA_OBS_EPISODE_START : (regoal ? RA_OBS_NEW_GOAL : RA_OBS_SKIP);
     F.started = started; F.ended = ended; F.regoal = regoal; F.n = n;
   }
   __syncthreads();
@@ -727,36 +713,21 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
   if (F.started || F.regoal) {
     if (F.moved && lane < 3) bt.qpos[(size_t)e * nq + a.obj_qposadr[0] + lane] = F.opos[lane];      // set_object_pos: the position only
     const int n = F.n;
-    if (lane < n) {
-      const float ez = rbc_wrap(F.gyaw[lane]);        // mat2euler of a z rotation, normalised
+    if (lane < N) {                                   // (a padded slot: a zero goal, identity orientation)
+      const bool act = lane < n;
+      const float ez = act ? rbc_wrap(F.gyaw[lane]) : 0.f;        // mat2euler of a z rotation, normalised
       float* g = a.goal + ((size_t)e * N + lane) * 7;
-      g[0] = F.gpos[lane][0]; g[1] = F.gpos[lane][1]; g[2] = F.gpos[lane][2];
-      g[3] = cosf(0.5f * ez); g[4] = 0.f; g[5] = 0.f; g[6] = sinf(0.5f * ez);
+      for (int c = 0; c < 3; c++) g[c] = act ? F.gpos[lane][c] : 0.f;
+      g[3] = act ? cosf(0.5f * ez) : 1.f; g[4] = 0.f; g[5] = 0.f; g[6] = act ? sinf(0.5f * ez) : 0.f;
       float* gr = a.goal_rot + ((size_t)e * N + lane) * 3;
       gr[0] = 0.f; gr[1] = 0.f; gr[2] = ez;
-    } else if (lane < N) {                            // a padded slot: a zero goal (identity orientation)
-      float* g = a.goal + ((size_t)e * N + lane) * 7;
-      for (int c = 0; c < 7; c++) g[c] = c == 3 ? 1.f : 0.f;
-      float* gr = a.goal_rot + ((size_t)e * N + lane) * 3;
-      gr[0] = 0.f; gr[1] = 0.f; gr[2] = 0.f;
     }
     // the goal's mask of the placement area (goals/object_state.py:373-378): from the position written above, frozen until the next goal; a padded slot reads 1
     if (a.goal_in_area && lane < N) {
-      const float u = a.soft_mask ? env_u01(a.seed ^ 0x3C6EF372u, a.step, (unsigned)e, 0u) : 0.f;
+      const float u = a.soft_mask ? env_u01(a.seed ^ RA_STREAM_GOAL_MASK, a.step, (unsigned)e, 0u) : 0.f;
       a.goal_in_area[(size_t)e * N + lane] = lane < n ? ra_in_area(a, ra_area(a, n), F.gpos[lane], a.soft_mask != 0, u) : 1.f;
     }
-    for (int i = lane; i < nq; i += 64) {
-      float v = bt.qpos[(size_t)e * nq + i];
-      for (int o = 0; o < n; o++) {
-        const int d = i - a.obj_qposadr[o];
-        if (d >= 0 && d < 7) { const float ez = rbc_wrap(F.gyaw[o]); v = d < 3 ? F.gpos[o][d] : (d == 3 ? cosf(0.5f * ez) : (d == 6 ? sinf(0.5f * ez) : 0.f)); }
-      }
-      for (int o = n; o < N; o++) {                   // (a parked object keeps its parked pose in qpos_goal)
-        const int d = i - a.obj_qposadr[o];
-        if (d >= 0 && d < 7) v = a.park_pose[o][d];
-      }
-      a.qpos_goal[(size_t)e * nq + i] = v;
-    }
+    for (int i = lane; i < nq; i += 64) a.qpos_goal[(size_t)e * nq + i] = ra_qpos_with_objects(a, i, n, bt.qpos[(size_t)e * nq + i], F.gpos, F.gyaw, true);
     if (lane == 0) a.prev_valid[e] = 0;
   }
   __syncthreads();
@@ -767,15 +738,7 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
     for (int i = lane; i < nq; i += 64) {
       float v = m.qpos0[i];
       for (int j = 0; j < 6; j++) if (i == a.arm_qposadr[j]) v = a.arm_start[j];
-      for (int o = 0; o < n; o++) {
-        const int d = i - a.obj_qposadr[o];
-        if (d >= 0 && d < 7) v = d < 3 ? F.pos[o][d] : (d == 3 ? cosf(0.5f * yw[o]) : (d == 6 ? sinf(0.5f * yw[o]) : 0.f));
-      }
-      for (int o = n; o < N; o++) {                   // objects beyond the env's count are parked (ra_recipe_args.park_pose), at rest: qvel is zeroed below
-        const int d = i - a.obj_qposadr[o];
-        if (d >= 0 && d < 7) v = a.park_pose[o][d];
-      }
-      bt.qpos[(size_t)e * nq + i] = v;
+      bt.qpos[(size_t)e * nq + i] = ra_qpos_with_objects(a, i, n, v, F.pos, yw, false);      // (the parked objects are at rest: qvel is zeroed below)
     }
     for (int i = lane; i < m.nv; i += 64) { bt.qvel[(size_t)e * m.nv + i] = 0.f; bt.qacc_warmstart[(size_t)e * m.nv + i] = 0.f; }
     for (int i = lane; i < m.nu; i += 64) bt.ctrl[(size_t)e * m.nu + i] = i < 6 ? a.arm_start[i] : 0.f;
@@ -796,10 +759,9 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
     }
     if (lane >= n && lane < N) { float* so = a.static_obs + ((size_t)e * N + lane) * 7; for (int q = 0; q < 7; q++) so[q] = 0.f; }
     if (lane < n) {      // the static observation: bounding box of the yawed object, a random colour
-      const float c = fabsf(cosf(yw[lane])), s_ = fabsf(sinf(yw[lane]));
       float* so = a.static_obs + ((size_t)e * N + lane) * 7;
-      so[0] = c * a.obj_half[lane][0] + s_ * a.obj_half[lane][1]; so[1] = s_ * a.obj_half[lane][0] + c * a.obj_half[lane][1]; so[2] = a.obj_half[lane][2];
-      for (int q = 0; q < 3; q++) so[3 + q] = env_u01(a.seed, a.step, (unsigned)e, 500u + 3u * lane + q);
+      ra_yawed_half(a, lane, yw[lane], so[0], so[1]); so[2] = a.obj_half[lane][2];
+      for (int q = 0; q < 3; q++) so[3 + q] = env_u01(a.seed, a.step, (unsigned)e, RA_DRAW_COLOURS + 3u * lane + q);
       so[6] = 1.f;
     }
   }

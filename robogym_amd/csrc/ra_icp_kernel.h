@@ -124,7 +124,7 @@ __global__ void __launch_bounds__(RA_ICP_THREADS, 4) ra_icp_kernel(const RbModel
   const int N = a.num_objects, tid = threadIdx.x;
   const int e = (int)blockIdx.x / N, obj = (int)blockIdx.x - e * N;
   if (e >= bt.B) return;
-  if (a.frozen && a.frozen[e] == 2) return;      // not this env's turn: its row of icp_rel stays
+  if (a.frozen && a.frozen[e] == RA_OBS_SKIP) return;      // not this env's turn: its row of icp_rel stays
   int n = N;
   if (a.num_active) { n = a.num_active[e]; n = n < 1 ? 1 : (n > N ? N : n); }
   if (obj >= n) return;                          // a padded slot: nothing is written

@@ -1538,7 +1538,7 @@ int ra_env_post_step(rb_batch* b, rb_batch* solver, const ra_post_args* args, vo
     return fail("ra_env_post_step: a required array is NULL");
   if (a.num_objects < 1 || a.num_objects > RA_MAXOBJ) return fail("ra_env_post_step: num_objects out of range");
   if (a.mask_obs < 0 || a.mask_obs > 1 || a.soft_mask < 0 || a.soft_mask > 1) return fail("ra_env_post_step: mask_obs and soft_mask are 0 or 1");
-  if (a.obs_dim != (a.mask_obs ? 74 : 36) * a.num_objects + 23 + 2 * d.nq) return fail("ra_env_post_step: obs_dim does not match the row layout (36 N + 23 + 2 nq; 74 N + 23 + 2 nq with mask_obs)");
+  if (a.obs_dim != rgb::ra_row_width(a.num_objects, d.nq, a.mask_obs)) return fail("ra_env_post_step: obs_dim does not match the row layout (36 N + 23 + 2 nq; 74 N + 23 + 2 nq with mask_obs)");
   if (a.mask_obs) {      // masks of the placement area
     if (!a.goal_in_area) return fail("ra_env_post_step: mask_obs needs goal_in_area");
     if (!(a.area_size[0] > 0.f) || !(a.area_size[1] > 0.f) || !(a.area_height > 0.f)) return fail("ra_env_post_step: mask_obs needs a placement area (area_size, area_height > 0)");
@@ -1553,16 +1553,16 @@ int ra_env_post_step(rb_batch* b, rb_batch* solver, const ra_post_args* args, vo
   for (int k = 0; k < 2; k++) if (a.finger_geom[k] < 0 || a.finger_geom[k] >= d.ngeom) return fail("ra_env_post_step: finger pad geom id out of range");
   if (a.table_plane_geom < 0 || a.table_plane_geom >= d.ngeom) return fail("ra_env_post_step: table plane geom id out of range");
   if (d.ngeom < 64 && (a.gripper_geom_mask >> d.ngeom) != 0) return fail("ra_env_post_step: gripper_geom_mask names a geom the model does not have (bit g = geom g, g < 64)");
-  if (a.goal_kind < 0 || a.goal_kind > 4) return fail("ra_env_post_step: goal_kind out of range (0 object state, 1 pick-and-place, 2 stack, 3 reach, 4 deterministic reach)");
-  if (a.goal_kind >= 2 && (a.grip_site < 0 || a.grip_site >= d.nsite)) return fail("ra_env_post_step: grip site id out of range");
-  if (a.goal_kind == 2 && !a.goal_dist_extra) return fail("ra_env_post_step: the stack goal needs goal_dist_extra");
-  if (a.goal_kind >= 3 && a.num_objects != 1) return fail("ra_env_post_step: the reach goals take exactly one object");
-  if (a.obj_group && a.goal_kind >= 3) return fail("ra_env_post_step: obj_group with a reach goal (one object: nothing to match)");
-  if (a.rot_dist_type < 0 || a.rot_dist_type > 3) return fail("ra_env_post_step: rot_dist_type out of range (0 full, 1 mod90, 2 mod180, 3 icp)");
-  if (a.rot_dist_type == 3 && !a.icp_rel) return fail("ra_env_post_step: rot_dist_type icp needs icp_rel (ra_env_icp writes it)");
-  if (a.rot_dist_type == 3 && a.goal_kind >= 3) return fail("ra_env_post_step: rot_dist_type icp with a reach goal (the achieved rotation is zero: no object cloud to fit)");
-  if ((a.rot_dist_type == 1 && !a.parallel_quats) || (a.rot_dist_type == 2 && !a.parallel_quats_180)) return fail("ra_env_post_step: rot_dist_type mod90 / mod180 needs its table of parallel quaternions");
-  if (a.num_active && a.goal_kind >= 3) return fail("ra_env_post_step: num_active with a reach goal (one object)");
+  if (a.goal_kind < RA_GOAL_OBJECT_STATE || a.goal_kind > RA_GOAL_DET_REACH) return fail("ra_env_post_step: goal_kind out of range (0 object state, 1 pick-and-place, 2 stack, 3 reach, 4 deterministic reach)");
+  if (rgb::ra_kind_uses_grip_site(a.goal_kind) && (a.grip_site < 0 || a.grip_site >= d.nsite)) return fail("ra_env_post_step: grip site id out of range");
+  if (a.goal_kind == RA_GOAL_STACK && !a.goal_dist_extra) return fail("ra_env_post_step: the stack goal needs goal_dist_extra");
+  if (rgb::ra_kind_is_reach(a.goal_kind) && a.num_objects != 1) return fail("ra_env_post_step: the reach goals take exactly one object");
+  if (a.obj_group && rgb::ra_kind_is_reach(a.goal_kind)) return fail("ra_env_post_step: obj_group with a reach goal (one object: nothing to match)");
+  if (a.rot_dist_type < RA_ROT_FULL || a.rot_dist_type > RA_ROT_ICP) return fail("ra_env_post_step: rot_dist_type out of range (0 full, 1 mod90, 2 mod180, 3 icp)");
+  if (a.rot_dist_type == RA_ROT_ICP && !a.icp_rel) return fail("ra_env_post_step: rot_dist_type icp needs icp_rel (ra_env_icp writes it)");
+  if (a.rot_dist_type == RA_ROT_ICP && rgb::ra_kind_is_reach(a.goal_kind)) return fail("ra_env_post_step: rot_dist_type icp with a reach goal (the achieved rotation is zero: no object cloud to fit)");
+  if ((a.rot_dist_type == RA_ROT_MOD90 && !a.parallel_quats) || (a.rot_dist_type == RA_ROT_MOD180 && !a.parallel_quats_180)) return fail("ra_env_post_step: rot_dist_type mod90 / mod180 needs its table of parallel quaternions");
+  if (a.num_active && rgb::ra_kind_is_reach(a.goal_kind)) return fail("ra_env_post_step: num_active with a reach goal (one object)");
   if (a.num_active && a.max_timesteps_per_goal_per_obj < 0) return fail("ra_env_post_step: negative max_timesteps_per_goal_per_obj");
   if (solver) {
     if (solver->dev.B != b->dev.B || solver->device != b->device) return fail("ra_env_post_step: the two batches must have the same size and device");
@@ -1609,26 +1609,26 @@ int ra_env_recipe_step(rb_batch* b, rb_batch* solver, const ra_recipe_args* args
   for (int k = 0; k < 6; k++) if (a.arm_qposadr[k] < 0 || a.arm_qposadr[k] >= d.nq) return fail("ra_env_recipe_step: arm joint address out of range");
   if (!(a.area_size[0] > 0.f) || !(a.area_size[1] > 0.f)) return fail("ra_env_recipe_step: empty placement area");
   if (a.stabilize_steps < 0 || a.n_random_initial_steps < 0 || a.settle_steps < 0) return fail("ra_env_recipe_step: negative step count");
-  if (a.goal_kind < 0 || a.goal_kind > 8)
+  if (a.goal_kind < RA_GOAL_OBJECT_STATE || a.goal_kind > RA_GOAL_FIXED)
     return fail("ra_env_recipe_step: goal_kind out of range (0 object state, 1 pick-and-place, 2 stack, 3 reach, 4 deterministic reach, 5 train, 6 dominos, 7 attached, 8 fixed)");
-  if (a.goal_kind == 7 && !(a.num_objects == 8 && a.object_size > 0.f)) return fail("ra_env_recipe_step: the attached goal needs num_objects == 8 and object_size > 0");
-  if (a.goal_kind == 7 && !(8.f * a.object_size <= a.area_size[0] && 6.f * a.object_size <= a.area_size[1])) return fail("ra_env_recipe_step: the attached goal's lattice does not fit the placement area");
-  if (a.goal_kind == 8)
+  if (a.goal_kind == RA_GOAL_ATTACHED && !(a.num_objects == 8 && a.object_size > 0.f)) return fail("ra_env_recipe_step: the attached goal needs num_objects == 8 and object_size > 0");
+  if (a.goal_kind == RA_GOAL_ATTACHED && !(8.f * a.object_size <= a.area_size[0] && 6.f * a.object_size <= a.area_size[1])) return fail("ra_env_recipe_step: the attached goal's lattice does not fit the placement area");
+  if (a.goal_kind == RA_GOAL_FIXED)
     for (int k = 0; k < a.num_objects; k++)
       if (!(a.fixed_xy[k][0] >= 0.f && a.fixed_xy[k][0] <= 1.f && a.fixed_xy[k][1] >= 0.f && a.fixed_xy[k][1] <= 1.f) || !(fabsf(a.fixed_yaw[k]) <= 1.0e4f))
         return fail("ra_env_recipe_step: the fixed goal needs fixed_xy in [0, 1] and finite fixed_yaw");
-  if (a.goal_kind == 6 && !(a.object_size > 0.f && a.domino_distance_mul > 0.f)) return fail("ra_env_recipe_step: the domino goal needs object_size > 0 and domino_distance_mul > 0");
+  if (a.goal_kind == RA_GOAL_DOMINOS && !(a.object_size > 0.f && a.domino_distance_mul > 0.f)) return fail("ra_env_recipe_step: the domino goal needs object_size > 0 and domino_distance_mul > 0");
   if (a.randomize_goal_rot < 0 || a.randomize_goal_rot > 1) return fail("ra_env_recipe_step: randomize_goal_rot is 0 or 1");
-  if ((a.goal_kind == 1 || a.goal_kind == 5) && !(a.height_range[0] <= a.height_range[1])) return fail("ra_env_recipe_step: empty height_range");
-  if ((a.goal_kind == 3 || a.goal_kind == 4) && a.num_objects != 1) return fail("ra_env_recipe_step: the reach goals take exactly one object");
-  if (a.goal_kind == 5 && !(a.goal_distance_min >= 0.f && a.pickup_proba >= 0.f && a.stacking_proba >= 0.f && a.pickup_proba + a.stacking_proba <= 1.f))
+  if ((a.goal_kind == RA_GOAL_PICKANDPLACE || a.goal_kind == RA_GOAL_TRAIN) && !(a.height_range[0] <= a.height_range[1])) return fail("ra_env_recipe_step: empty height_range");
+  if (rgb::ra_kind_is_reach(a.goal_kind) && a.num_objects != 1) return fail("ra_env_recipe_step: the reach goals take exactly one object");
+  if (a.goal_kind == RA_GOAL_TRAIN && !(a.goal_distance_min >= 0.f && a.pickup_proba >= 0.f && a.stacking_proba >= 0.f && a.pickup_proba + a.stacking_proba <= 1.f))
     return fail("ra_env_recipe_step: the train goal needs goal_distance_min >= 0 and 0 <= pickup_proba + stacking_proba <= 1");
-  if (a.goal_kind == 4 && !a.goal_index) return fail("ra_env_recipe_step: the deterministic reach goal needs goal_index");
-  if (a.group_mode < 0 || a.group_mode > 1) return fail("ra_env_recipe_step: group_mode out of range (0 the rows stay, 1 sampled at every episode start)");
-  if (a.group_mode == 1 && !a.obj_group) return fail("ra_env_recipe_step: group_mode 1 needs obj_group");
-  if (a.obj_group && (a.goal_kind == 3 || a.goal_kind == 4)) return fail("ra_env_recipe_step: obj_group with a reach goal (one object: nothing to group)");
-  if (a.group_mode == 1 && !(a.sample_lam[0] >= 0.f && a.sample_lam[0] <= a.sample_lam[1])) return fail("ra_env_recipe_step: sample_lam is not a range of non-negative rates");
-  if (a.sync_mode < 0 || a.sync_mode > RA_SYNC_REGOAL_ONLY) return fail("ra_env_recipe_step: sync_mode out of range (0 the pipelined stage machine, 1 forced end, 2 regoal only)");
+  if (a.goal_kind == RA_GOAL_DET_REACH && !a.goal_index) return fail("ra_env_recipe_step: the deterministic reach goal needs goal_index");
+  if (a.group_mode < RA_GROUPS_KEEP || a.group_mode > RA_GROUPS_SAMPLE) return fail("ra_env_recipe_step: group_mode out of range (0 the rows stay, 1 sampled at every episode start)");
+  if (a.group_mode == RA_GROUPS_SAMPLE && !a.obj_group) return fail("ra_env_recipe_step: group_mode 1 needs obj_group");
+  if (a.obj_group && rgb::ra_kind_is_reach(a.goal_kind)) return fail("ra_env_recipe_step: obj_group with a reach goal (one object: nothing to group)");
+  if (a.group_mode == RA_GROUPS_SAMPLE && !(a.sample_lam[0] >= 0.f && a.sample_lam[0] <= a.sample_lam[1])) return fail("ra_env_recipe_step: sample_lam is not a range of non-negative rates");
+  if (a.sync_mode < RA_SYNC_PIPELINED || a.sync_mode > RA_SYNC_REGOAL_ONLY) return fail("ra_env_recipe_step: sync_mode out of range (0 the pipelined stage machine, 1 forced end, 2 regoal only)");
   if (a.goal_in_area) {      // the goal's mask of the placement area
     if (a.soft_mask < 0 || a.soft_mask > 1) return fail("ra_env_recipe_step: soft_mask is 0 or 1");
     if (!(a.area_height > 0.f)) return fail("ra_env_recipe_step: goal_in_area needs area_height > 0");
@@ -1636,7 +1636,7 @@ int ra_env_recipe_step(rb_batch* b, rb_batch* solver, const ra_recipe_args* args
   }
   if (a.num_active) {      // per-env object counts
     if (!a.num_objects_next) return fail("ra_env_recipe_step: num_active needs num_objects_next");
-    if (!(a.goal_kind <= 2 || a.goal_kind == 5)) return fail("ra_env_recipe_step: per-env object counts are built for goal kinds 0, 1, 2 and 5");
+    if (!rgb::ra_kind_is_counted(a.goal_kind)) return fail("ra_env_recipe_step: per-env object counts are built for goal kinds 0, 1, 2 and 5");
     if (!(a.used_table_portion > 0.f) || !(a.used_table_portion <= 1.0e6f)) return fail("ra_env_recipe_step: num_active needs used_table_portion > 0");
     for (int k = 0; k < a.num_objects; k++)
       for (int c = 0; c < 7; c++)

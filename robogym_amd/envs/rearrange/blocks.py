@@ -59,7 +59,9 @@ FLAG_FULL_FORWARD = 32
 #: ObjectStackGoal (goals/object_stack_goal.py), ObjectReachGoal / DeterministicReachGoal (goals/object_reach_goal.py)
 #: (train: TrainStateGoal, goals/train_state.py; dominos: DominoStateGoal, goals/dominos.py; attached: AttachedBlockStateGoal, goals/attached_block_state.py; fixed:
 #: ObjectFixedStateGoal, goals/object_state_fixed.py)
-GOAL_KINDS = {"object_state": 0, "pickandplace": 1, "stack": 2, "reach": 3, "det-reach": 4, "train": 5, "dominos": 6, "attached": 7, "fixed": 8}
+GOAL_KINDS = {"object_state": _native.RA_GOAL_OBJECT_STATE, "pickandplace": _native.RA_GOAL_PICKANDPLACE, "stack": _native.RA_GOAL_STACK, "reach": _native.RA_GOAL_REACH,
+              "det-reach": _native.RA_GOAL_DET_REACH, "train": _native.RA_GOAL_TRAIN, "dominos": _native.RA_GOAL_DOMINOS, "attached": _native.RA_GOAL_ATTACHED,
+              "fixed": _native.RA_GOAL_FIXED}
 #: the reach goals: one object, which the goal itself moves; the target is a point above it
 REACH_KINDS = ("reach", "det-reach")
 #: the kinds whose generator sets the goals' yaws itself (set_target_quat inside _sample_next_goal_positions): the arc's / init_quats', whatever the goals had
@@ -71,7 +73,7 @@ POST_KINDS = ("object_state", "pickandplace", "stack", "reach", "det-reach")
 #: AttachedBlockStateGoal's cells (goals/attached_block_state.py:34-49), in steps of one block: a row of 2, a row of 4, a row of 2
 ATTACHED_LATTICE = np.array([[1, 0], [2, 0], [0, 1], [1, 1], [2, 1], [3, 1], [1, 2], [2, 2]], dtype=np.float64)
 #: GoalArgs.rot_dist_type (goals/object_state.py:127-131) -> ra_post_args.rot_dist_type; "icp": one more launch in front of the env kernel (ra_env_icp, csrc/ra_icp_kernel.h)
-ROT_DIST_TYPES = {"full": 0, "mod90": 1, "mod180": 2, "icp": 3}
+ROT_DIST_TYPES = {"full": _native.RA_ROT_FULL, "mod90": _native.RA_ROT_MOD90, "mod180": _native.RA_ROT_MOD180, "icp": _native.RA_ROT_ICP}
 #: DominoStateGoal's attempts per goal (goals/dominos.py:10)
 DOMINO_MAX_RETRY = 1000
 #: DeterministicReachGoal's two object positions (goals/object_reach_goal.py:65-66)
@@ -564,7 +566,7 @@ class BatchedBlockRearrangeEnv:
         # readback of the flags per step -- a step is 70 ms of GPU work), its physics goes through the same three launches as the live envs': `hold` /
         # `scripted` feed the recipe's actions to the solver world's launch, `frozen` keeps the env kernel from scoring those envs.
         self.pipelined = bool(pipelined_reset)
-        self._stage, self._left = np.zeros(B, dtype=np.int8), np.zeros(B, dtype=np.int32)      # 0 live, 1 stabilise, 2 random action, 3 settle
+        self._stage, self._left = np.zeros(B, dtype=np.int8), np.zeros(B, dtype=np.int32)      # _native.RA_STAGE_*
         self._yaw = np.zeros((B, N))
         self.ended_rows = np.zeros(0, dtype=np.int64)          # rows whose episode ended on the last step (pipelined resets)
         self.hold, self.scripted, self.frozen, self.solver_active = z(B, dt=torch.int32), z(B, AD), z(B, dt=torch.uint8), torch.ones(B, dtype=torch.int32, device=dev)
@@ -603,7 +605,7 @@ class BatchedBlockRearrangeEnv:
         self.device_reset = bool(device_reset)
         if self.device_reset:
             self.stage, self.left, self.yaw, self.placement_failed = z(B, dt=torch.int32), z(B, dt=torch.int32), z(B, N), z(B, dt=torch.int32)
-            self.reobserve, self.ended, self.stabilised = torch.full((B,), 2, dtype=torch.uint8, device=dev), z(B, dt=torch.bool), z(B, dt=torch.bool)
+            self.reobserve, self.ended, self.stabilised = torch.full((B,), _native.RA_OBS_SKIP, dtype=torch.uint8, device=dev), z(B, dt=torch.bool), z(B, dt=torch.bool)
             self._fill_recipe_args(starting_seed)
             self._fill_sync_reset_args()
 
@@ -755,7 +757,7 @@ class BatchedBlockRearrangeEnv:
                 r.det_points[j][k] = float(DET_REACH_POINTS[j, k])
         r.goal_distance_ratio, r.goal_distance_min, r.pickup_proba, r.stacking_proba = _ptr(self.goal_distance_ratio), self.goal_distance_min, self.pickup_proba, self.stacking_proba
         if self.obj_group is not None:
-            r.obj_group, r.group_mode = _ptr(self.obj_group), int(self.group_mode == "sample")
+            r.obj_group, r.group_mode = _ptr(self.obj_group), _native.RA_GROUPS_SAMPLE if self.group_mode == "sample" else _native.RA_GROUPS_KEEP
             r.sample_lam[0], r.sample_lam[1] = self.sample_lam
         r.randomize_goal_rot, r.domino_distance_mul = int(self.randomize_goal_rot), self.domino_distance_mul
         if self.goal_kind_name == "fixed":
@@ -1280,7 +1282,7 @@ class BatchedBlockRearrangeEnv:
         both = _native.RA_ROWS_RESTORE | _native.RA_ROWS_PARK
         try:
             self._recipe_launch()
-            r.sync_mode = 0
+            r.sync_mode = _native.RA_SYNC_PIPELINED
             if self.param_rows is not None:
                 self._param_rows_launch(both)
             iterations, stabilising = self.sync_reset_iterations(), max(int(self.stabilize_steps), 1)
@@ -1297,7 +1299,7 @@ class BatchedBlockRearrangeEnv:
                 if self.param_rows is not None:
                     self._param_rows_launch(both)
         finally:
-            r.active, r.sync_mode = None, 0
+            r.active, r.sync_mode = None, _native.RA_SYNC_PIPELINED
         # the last launch started the episodes (the envs of the mask run the stages in lockstep)
         if self.randomizers:
             started = self.episode_started & act
@@ -1307,7 +1309,7 @@ class BatchedBlockRearrangeEnv:
                 self._param_rows_launch(_native.RA_ROWS_PARK)
         if self.reach:
             self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=act32)
-        self._post(frozen=torch.where(act, self.reobserve, torch.full_like(self.reobserve, 2)))
+        self._post(frozen=torch.where(act, self.reobserve, torch.full_like(self.reobserve, _native.RA_OBS_SKIP)))
         self.episode_started.masked_fill_(act, False)      # (as after the host recipe: the flag belongs to the step calls of a pipelined env)
         self.ended_rows = np.zeros(0, dtype=np.int64)
         return self.observe()
@@ -1327,10 +1329,10 @@ class BatchedBlockRearrangeEnv:
         idx = torch.as_tensor(rows, device=dev, dtype=torch.long)
         active = self._mask_of(idx, torch.int32)
         if self.pipelined:       # a synchronous reset ends whatever recipe those envs were in
-            self._stage[rows] = 0; self._left[rows] = 0
+            self._stage[rows] = _native.RA_STAGE_LIVE; self._left[rows] = 0
             if self.device_reset:
-                self.stage[idx] = 0; self.left[idx] = 0
-            self.hold[idx] = 0; self.hold_ctrl[idx] = 0; self.frozen[idx] = 0; self.solver_active[idx] = 1; self.resetting[idx] = False; self.episode_started[idx] = False
+                self.stage[idx] = _native.RA_STAGE_LIVE; self.left[idx] = 0
+            self.hold[idx] = 0; self.hold_ctrl[idx] = 0; self.frozen[idx] = _native.RA_OBS_STEP; self.solver_active[idx] = 1; self.resetting[idx] = False; self.episode_started[idx] = False
             self.nticks[idx] = 2; self._nticks_host = None
         yaw = self._begin_episode_state(rows, idx)
         # stabilize_objects (common/utils.py:76-92): the objects' dof damping is lowered to 1e-3 while they settle and restored afterwards -- with per-env parameter
@@ -1375,9 +1377,9 @@ class BatchedBlockRearrangeEnv:
         if len(started) + len(regoaled) == 0:
             return
         saved = self.frozen.clone()
-        self.frozen.fill_(2)
-        self.frozen[torch.as_tensor(started, device=self.device, dtype=torch.long)] = 1
-        self.frozen[torch.as_tensor(regoaled, device=self.device, dtype=torch.long)] = 3
+        self.frozen.fill_(_native.RA_OBS_SKIP)
+        self.frozen[torch.as_tensor(started, device=self.device, dtype=torch.long)] = _native.RA_OBS_EPISODE_START
+        self.frozen[torch.as_tensor(regoaled, device=self.device, dtype=torch.long)] = _native.RA_OBS_NEW_GOAL
         self._post(frozen=self.frozen)
         self.frozen.copy_(saved)
 
@@ -1390,57 +1392,57 @@ class BatchedBlockRearrangeEnv:
         self.episode_started.zero_()
         st, left = self._stage, self._left
         # ---- envs inside the recipe: this step counted
-        inside = st > 0
+        inside = st != _native.RA_STAGE_LIVE
         left[inside] -= 1
         nxt = np.nonzero(inside & (left <= 0))[0]
         started = []
         was = st[nxt].copy()
-        for stage in (1, 2, 3):
+        for stage in (_native.RA_STAGE_STABILISE, _native.RA_STAGE_RANDOM_ACTION, _native.RA_STAGE_SETTLE):
             rows = nxt[was == stage]
             if len(rows) == 0:
                 continue
             idx = torch.as_tensor(rows, device=dev, dtype=torch.long)
-            if stage == 1:
+            if stage == _native.RA_STAGE_STABILISE:
                 self._set_object_damping(idx, None)                     # stabilize_objects restores the objects' damping
-            if stage == 1 and self.n_random_initial_steps >= 1:         # -> one random action for n_random_initial_steps steps
-                st[rows], left[rows] = 2, self.n_random_initial_steps
+            if stage == _native.RA_STAGE_STABILISE and self.n_random_initial_steps >= 1:         # -> one random action for n_random_initial_steps steps
+                st[rows], left[rows] = _native.RA_STAGE_RANDOM_ACTION, self.n_random_initial_steps
                 self.scripted[idx] = torch.tensor(self._rng.uniform(-1, 1, (len(rows), self.launch_action_dim)).astype(np.float32), device=dev)
                 self.solver_active[idx] = 1; self.hold_ctrl[idx] = 0
-            elif stage == 2:                                            # -> zero action while everything settles
-                st[rows], left[rows] = 3, self.settle_steps
+            elif stage == _native.RA_STAGE_RANDOM_ACTION:                                            # -> zero action while everything settles
+                st[rows], left[rows] = _native.RA_STAGE_SETTLE, self.settle_steps
                 self.scripted[idx] = 0
             else:                                                       # -> the episode starts
                 started.append(rows)
         if started:
             rows = np.concatenate(started)
             idx = torch.as_tensor(rows, device=dev, dtype=torch.long)
-            st[rows], left[rows] = 0, 0
-            self.hold[idx] = 0; self.scripted[idx] = 0; self.frozen[idx] = 0; self.solver_active[idx] = 1; self.hold_ctrl[idx] = 0
+            st[rows], left[rows] = _native.RA_STAGE_LIVE, 0
+            self.hold[idx] = 0; self.scripted[idx] = 0; self.frozen[idx] = _native.RA_OBS_STEP; self.solver_active[idx] = 1; self.hold_ctrl[idx] = 0
             self.resetting[idx] = False; self.episode_started[idx] = True
             self._start_episode(rows, idx, self._yaw[rows])
         # ---- live envs with a reached goal: ObjectStateGoal.next_goal (what reset_goals() does on request)
-        grows = np.nonzero(newgoal.astype(bool) & (st == 0) & ~done.astype(bool))[0]     # (an episode that ends on the same step keeps the reached goal's entries in its terminal observation: ra_recipe_kernel)
+        grows = np.nonzero(newgoal.astype(bool) & (st == _native.RA_STAGE_LIVE) & ~done.astype(bool))[0]     # (an episode that ends on the same step keeps the reached goal's entries in its terminal observation: ra_recipe_kernel)
         if len(grows):
             self._regoal(grows)
         if self.reach:      # (one forward and one re-observation for the rows that start and the rows with a new goal)
             self._forward_rows(np.concatenate(started + [grows]))
         self._reobserve(np.concatenate(started) if started else np.zeros(0, dtype=np.int64), grows)
         # ---- episodes that ended on this step: their recipe begins (the returned observation / reward / done are the terminal ones)
-        rows = np.nonzero(done.astype(bool) & (st == 0))[0]
+        rows = np.nonzero(done.astype(bool) & (st == _native.RA_STAGE_LIVE))[0]
         self.ended_rows = rows                              # (envs/rearrange/ycb.py hands these slots out again, to other envs of the batch)
         if len(rows):
             idx = torch.as_tensor(rows, device=dev, dtype=torch.long)
             self._yaw[rows] = self._begin_episode_state(rows, idx)
             self._set_object_damping(idx, self.stabilize_object_damping)
-            st[rows], left[rows] = 1, self.stabilize_steps
-            self.hold[idx] = 1; self.scripted[idx] = 0; self.frozen[idx] = 4; self.solver_active[idx] = 0; self.hold_ctrl[idx] = 1
+            st[rows], left[rows] = _native.RA_STAGE_STABILISE, self.stabilize_steps
+            self.hold[idx] = 1; self.scripted[idx] = 0; self.frozen[idx] = _native.RA_OBS_IN_RECIPE; self.solver_active[idx] = 0; self.hold_ctrl[idx] = 1
             self.resetting[idx] = True
             if self.stabilize_steps <= 0:        # (degenerate configuration: straight to the next stage on the following step)
                 left[rows] = 1
         # controller ticks of the NEXT step's main-world launch: two for live envs, one inside the recipe, two on the recipe's last step (see _physics)
-        last_stage = 3 if self.n_random_initial_steps >= 1 else 1
+        last_stage = _native.RA_STAGE_SETTLE if self.n_random_initial_steps >= 1 else _native.RA_STAGE_STABILISE
         # (reach: one on the recipe's last step -- its goal moves the object, the forward of _observe_sync comes after that, _forward_rows)
-        want = np.where(st > 0, np.where((st == last_stage) & (left <= 1) & (not self.reach), 2, 1), 2).astype(np.int32)
+        want = np.where(st != _native.RA_STAGE_LIVE, np.where((st == last_stage) & (left <= 1) & (not self.reach), 2, 1), 2).astype(np.int32)
         if not np.array_equal(want, getattr(self, "_nticks_host", None)):
             self._nticks_host = want
             self.nticks.copy_(torch.as_tensor(want, device=dev))
@@ -1463,7 +1465,7 @@ class BatchedBlockRearrangeEnv:
             if self.max_num_objects is not None:      # parking after the restore, the damping changes and the randomizers, on the recipe's masks
                 self._apply_parking(self.ended | self.stabilised | self.episode_started)
         if self.reach:      # the object the goal moved: _observe_sync's forward for the envs with a new goal (no readback: every env, masked by the reobserve codes)
-            self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=(self.reobserve != 2).to(torch.int32))
+            self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=(self.reobserve != _native.RA_OBS_SKIP).to(torch.int32))
         self._post(frozen=self.reobserve)
         self.ended_rows = np.zeros(0, dtype=np.int64)
 
@@ -1542,9 +1544,9 @@ class BatchedBlockRearrangeEnv:
             try:
                 self._recipe_launch()
             finally:
-                r.sync_mode = 0
+                r.sync_mode = _native.RA_SYNC_PIPELINED
             if self.reach:
-                self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=(self.reobserve != 2).to(torch.int32))
+                self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=(self.reobserve != _native.RA_OBS_SKIP).to(torch.int32))
             self._post(frozen=self.reobserve)
             return
         rows = np.nonzero(self.goal_reset.cpu().numpy())[0]

@@ -236,7 +236,7 @@ class GroupedYcbRearrangeEnv:
         return obs, reward, done, info
 
     def _trade_slots_device(self):
-        """`_trade_slots` without the host (device_reset): the pool -- every slot whose recipe stage is > 0 after this step's recipe launch -- is dealt out again among
+        """`_trade_slots` without the host (device_reset): the pool -- every slot that is inside the recipe (its stage is not RA_STAGE_LIVE) after this step's recipe launch -- is dealt out again among
         the envs that hold those slots by a random permutation, if any episode ended on this step; fixed-shape tensor ops, no readback.  Sorting the slots by
         (in the pool ? 0 : 1, index) and by (in the pool ? random key : 2 + index) lists the pool first in both orders -- in index order and in random order -- and the
         other slots identically behind it, so "the k-th env of the first order gets the k-th slot of the second" is the identity outside the pool."""
@@ -246,7 +246,7 @@ class GroupedYcbRearrangeEnv:
             return
         stage = torch.cat([g.stage.reshape(-1) for g in self.groups]).to(torch.int64)
         ended = torch.cat([g.ended.reshape(-1) for g in self.groups])
-        pool = stage > 0
+        pool = stage != _native.RA_STAGE_LIVE
         idx = self._arange.to(torch.float64) / float(self.B)
         by_index = torch.argsort(torch.where(pool, idx, 2.0 + idx))
         by_key = torch.argsort(torch.where(pool, torch.rand(self.B, generator=self._gen, device=self.device, dtype=torch.float64), 2.0 + idx))
@@ -276,7 +276,7 @@ class GroupedYcbRearrangeEnv:
 
         if not (self.resample and self.groups[0].pipelined) or sum(len(g.ended_rows) for g in self.groups) == 0:
             return
-        pool = np.concatenate([i * self.b + np.nonzero(np.asarray(g._stage) > 0)[0] for i, g in enumerate(self.groups)])
+        pool = np.concatenate([i * self.b + np.nonzero(np.asarray(g._stage) != _native.RA_STAGE_LIVE)[0] for i, g in enumerate(self.groups)])
         inv = np.empty(self.B, dtype=np.int64); inv[self._slot] = np.arange(self.B)
         self._reassign(inv[pool])
 
