@@ -603,6 +603,15 @@ typedef struct ra_post_args {
   float area_offset[2], area_size[2], table_pos[3], table_size[3], used_table_portion;   /* as ra_recipe_args */
   unsigned seed, step;
   const float* goal_in_area;                     /* [B][N] 1.0 / 0.0 */
+  /* the relative distance of the holdout goals (appended; rel_dist NULL = none, every path above as it is).  HoldoutObjectStateGoal.goal_distance
+   * (goals/holdout_object_state.py:65-74): the anchor is the FIRST object with the lowest goal z among the env's active objects (np.argmin), and
+   * rel_dist[e][i] = |pos_i - (goal_i - goal_anchor + pos_anchor)| for every active object, 0 for a padded slot; written by the launches that write goal_dist
+   * (RA_OBS_STEP, RA_OBS_EPISODE_START, RA_OBS_IN_RECIPE).  Positions and goals are indexed by object: the reference computes it for distinct objects only, so
+   * rel_dist with obj_group is an error, as it is with a reach goal.  rel_threshold > 0 (needs rel_dist): an object counts as achieved only if its rel_dist is also below it --
+   * in the success count behind the goal-distance reward, in is_goal_achieved and in the tracker's success (_calculate_num_success is an `all` over the
+   * threshold's keys, common/base.py:824-848); rel_threshold <= 0: rel_dist is reported only.  The observation row does not change. */
+  float* rel_dist;                               /* [B][N] */
+  float rel_threshold;
 } ra_post_args;
 int ra_env_post_step(rb_batch* main, rb_batch* solver, const ra_post_args* args, void* stream);
 int ra_post_args_size(void);
@@ -716,6 +725,33 @@ typedef struct ra_recipe_args {
   float* goal_in_area;                           /* [B][N] */
   int soft_mask;
   float mask_margin, area_height;
+  /* recorded scenes (appended; zero-filled = none, every path above as it is): the reference's holdout envs (envs/rearrange/holdout.py:93-106,
+   * goals/holdout_object_state.py) as state tables, rows of (position, quaternion w x y z) per object, the quaternions normalised by the caller.  No goal kind of
+   * their own: a recorded goal is RA_GOAL_OBJECT_STATE with its sampling replaced, so goal_kind must be RA_GOAL_OBJECT_STATE when a table is given.
+   * num_scenes = S >= 1 with scene [B] and scene_next [B]: when an env's episode ends the kernel latches scene[e] = clamp(scene_next[e], 0, S - 1), as
+   * num_active is latched -- a value written mid-episode waits for that.
+   * Everything DERIVED from a state is the caller's too, made once in float64 next to the table (scene_init_half, scene_goal_rot): a launch only copies rows, so a
+   * host route that reads the same tables writes the same bits.
+   * scene_init [S][N][7] with scene_init_half [S][N][3], NULL = drawn placements: the episode starts from row scene[e] -- qpos gets position and the full
+   * quaternion, the static obj_bbox_size is the box turned by that rotation, half extents sum_k |R_ik| obj_half[k] (rotate_bounding_box as
+   * get_block_bounding_box calls it; ra_yawed_half for a yaw): row scene[e] of scene_init_half.  No yaw and no placement is drawn, obj_colors keep what the
+   * static_obs rows hold (HoldoutRearrangeEnv._apply_object_colors does nothing; the random initial action keeps its draws), yaw[e] = 0: the reference sets the
+   * objects only, not the targets, so a goal SAMPLED after a recorded start begins from the target's model orientation.  Stabilisation, random steps and
+   * settling as above.
+   * scene_goal [S][max_scene_goals][N][7] with scene_num_goals [S] (0 <= count <= max_scene_goals; 0 = that scene's goals are sampled as above): every goal the
+   * kernel makes for an env of a scene with goals -- a started episode, a regoal, the sync modes -- is row goal_cursor[e] of the scene: goal[0..6] = the recorded
+   * position and quaternion, goal_rot = the normalised mat2euler of it, qpos_goal carries euler2quat(goal_rot) (ObjectStateGoal.next_goal) -- both from
+   * scene_goal_rot [S][max_scene_goals][N][7], Euler angles 3 | that quaternion 4 --, goal_in_area from the recorded position; no draw, randomize_goal_rot does not turn it (holdout_object_state.py:59-63).  goal_cursor [B]: advance_goals 0 = every goal is
+   * row 0 (what the reference's code does: goal_idx never moves); 1 = the cursor steps at every goal made, wraps at the scene's count and restarts at 0 when an
+   * episode starts (the round robin its docstring promises).  With num_active the rows beyond the env's count are padded as above. */
+  const float *scene_init, *scene_init_half;
+  const float *scene_goal, *scene_goal_rot;
+  const int* scene_num_goals;
+  int num_scenes, max_scene_goals;
+  const int* scene_next;
+  int* scene;
+  int* goal_cursor;
+  int advance_goals;
 } ra_recipe_args;
 /* The launch that follows it on the per-env parameter rows (ra_param_rows_args): declared and described in rgstep_sync_reset.h, which the end of this header includes. */
 int ra_env_recipe_step(rb_batch* main, rb_batch* solver, const ra_recipe_args* args, void* stream);

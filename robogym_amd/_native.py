@@ -99,7 +99,8 @@ def _ra_post_fields():
             + [("num_active", _p), ("max_timesteps_per_goal_per_obj", _i)]
             + [("icp_rel", _p)]
             + [("mask_obs", _i), ("soft_mask", _i), ("mask_margin", _f), ("area_height", _f), ("area_offset", _f * 2), ("area_size", _f * 2), ("table_pos", _f * 3),
-               ("table_size", _f * 3), ("used_table_portion", _f), ("seed", ctypes.c_uint), ("step", ctypes.c_uint), ("goal_in_area", _p)])
+               ("table_size", _f * 3), ("used_table_portion", _f), ("seed", ctypes.c_uint), ("step", ctypes.c_uint), ("goal_in_area", _p)]
+            + [("rel_dist", _p), ("rel_threshold", _f)])
 
 
 class RaPostArgs(ctypes.Structure):
@@ -133,7 +134,9 @@ def _ra_recipe_fields():
             + [("fixed_xy", (_f * 2) * RA_MAXOBJ), ("fixed_yaw", _f * RA_MAXOBJ)]
             + [("num_active", _p), ("num_objects_next", _p), ("used_table_portion", _f), ("park_pose", (_f * 7) * RA_MAXOBJ)]
             + [("active", _p), ("sync_mode", _i)]
-            + [("goal_in_area", _p), ("soft_mask", _i), ("mask_margin", _f), ("area_height", _f)])
+            + [("goal_in_area", _p), ("soft_mask", _i), ("mask_margin", _f), ("area_height", _f)]
+            + [("scene_init", _p), ("scene_init_half", _p), ("scene_goal", _p), ("scene_goal_rot", _p), ("scene_num_goals", _p), ("num_scenes", _i), ("max_scene_goals", _i), ("scene_next", _p), ("scene", _p),
+               ("goal_cursor", _p), ("advance_goals", _i)])
 
 
 class RaRecipeArgs(ctypes.Structure):

@@ -253,6 +253,27 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
       ra_write_object<true>(row, N, nq, lane, v, obj_in, goal_in);
     }
   }
+  if (a.rel_dist) {
+    // HoldoutObjectStateGoal.goal_distance (goals/holdout_object_state.py:65-74): the anchor is the first active object with the lowest goal z (np.argmin); each
+    // object's distance from where the goal puts it relative to the anchor's current position.  By object: no duplicates here (the host refuses obj_group)
+    float gz = INFINITY; int anchor = 0x7fffffff;
+    if (lane < n) { gz = a.goal[((size_t)e * N + lane) * 7 + 2]; anchor = lane; }
+    for (int o = 32; o > 0; o >>= 1) {
+      const float oz = __shfl_xor(gz, o); const int oa = __shfl_xor(anchor, o);
+      if (oz < gz || (oz == gz && oa < anchor)) { gz = oz; anchor = oa; }
+    }
+    if (anchor >= n) anchor = 0;                                       // (no goal z compares: NaN rows; np.argmin would name the first)
+    float rd = 0.f;
+    if (lane < n) {
+      const float* ga = a.goal + ((size_t)e * N + anchor) * 7; const float* gi = a.goal + ((size_t)e * N + lane) * 7;
+      const float* pa = xpos + 3 * a.obj_body[anchor]; const float* pi = xpos + 3 * a.obj_body[lane];
+      const float dx = pi[0] - (gi[0] - ga[0] + pa[0]), dy = pi[1] - (gi[1] - ga[1] + pa[1]), dz = pi[2] - (gi[2] - ga[2] + pa[2]);
+      rd = sqrtf(dx * dx + dy * dy + dz * dz);
+      if (a.rel_threshold > 0.f) ok_obj = ok_obj && rd < a.rel_threshold;
+    }
+    const int code = a.frozen ? a.frozen[e] : RA_OBS_STEP;
+    if (lane < N && (code == RA_OBS_STEP || code == RA_OBS_EPISODE_START || code == RA_OBS_IN_RECIPE)) a.rel_dist[(size_t)e * N + lane] = rd;
+  }
   const unsigned long long okmask = __ballot(ok_obj), offmask = __ballot(off_obj);
   const int nsucc = __popcll(okmask), any_off = offmask != 0;
   // sums of the distances over the objects (goal_info["goal_dist"])
@@ -348,8 +369,14 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
 //   ObjectStateGoal.next_goal                                      envs/rearrange/goals/object_state.py:355-418 (randomize_goal_rot: randomize_quaternion_along_z, :80-85)
 //   DominoStateGoal                                                envs/rearrange/goals/dominos.py:20-150
 //   place_targets_with_fixed_position                              envs/rearrange/common/utils.py:884-919 (ObjectFixedStateGoal, goals/object_state_fixed.py)
-//   AttachedBlockStateGoal                                         envs/rearrange/goals/attached_block_state.py:17-68
-struct RaRecipeLds { int started, ended, regoal, moved; float pos[RA_MAXOBJ][3], gpos[RA_MAXOBJ][3], gyaw[RA_MAXOBJ], opos[3]; int n; };
+//   HoldoutRearrangeEnv._randomize_object_initial_states           envs/rearrange/holdout.py:93-106 (a recorded start: ra_recipe_args.scene_init)
+//   HoldoutObjectStateGoal                                         envs/rearrange/goals/holdout_object_state.py:24-74 (recorded goals: scene_goal; rel_dist: ra_post_step_kernel)
+// (recorded scenes, ra_recipe_args.scene_init / scene_goal: `init_scene` with the start's quaternions `iquat` and turned half extents `ihalf`; `recorded` with the
+//  goal's quaternion `gquat`, its normalised Euler angles `geul` and euler2quat of those, `gqe`)
+struct RaRecipeLds { int started, ended, regoal, moved; float pos[RA_MAXOBJ][3], gpos[RA_MAXOBJ][3], gyaw[RA_MAXOBJ], opos[3]; int n;
+                     int init_scene, recorded; float iquat[RA_MAXOBJ][4], ihalf[RA_MAXOBJ][3], gquat[RA_MAXOBJ][4], geul[RA_MAXOBJ][3], gqe[RA_MAXOBJ][4]; };
+// the env's latched scene, inside the tables whatever the row holds
+__device__ inline int ra_scene_of(const RaRecipeArgs& a, int e) { const int s = a.scene[e]; return s < 0 ? 0 : (s >= a.num_scenes ? a.num_scenes - 1 : s); }
 // rotate_bounding_box: half extents in x and y of object i's box turned about z by `yaw`
 __device__ inline void ra_yawed_half(const RaRecipeArgs& a, int i, float yaw, float& hx, float& hy) {
   const float c = fabsf(cosf(yaw)), s_ = fabsf(sinf(yaw));
@@ -540,9 +567,26 @@ __device__ inline void ra_stage_step(const RaRecipeArgs& a, int e, int& st, int&
 }
 // A new goal for env e into F.gyaw / F.gpos (F.opos, F.moved: the reach goals' moved object), from the yaws gy[i * gstride].  The goal's draws come from a stream of
 // their own, RA_STREAM_GOAL: an env can get a new goal and end its episode on the same step.
-__device__ inline void ra_sample_goal(const RaRecipeArgs& a, RaRecipeLds& F, int e, int n, const float* qrow, const float* gy, int gstride) {
+// A scene with recorded goals (ra_recipe_args.scene_goal; `first`: the episode's first goal) copies row goal_cursor[e] of its table instead: no draw.
+__device__ inline void ra_sample_goal(const RaRecipeArgs& a, RaRecipeLds& F, int e, int n, const float* qrow, const float* gy, int gstride, bool first) {
   const int N = a.num_objects, kind = a.goal_kind;
-  F.moved = 0;
+  F.moved = 0; F.recorded = 0;
+  if (a.scene_goal) {
+    const int s = ra_scene_of(a, e), ng = a.scene_num_goals[s] < a.max_scene_goals ? a.scene_num_goals[s] : a.max_scene_goals;      // (never past the table)
+    if (ng > 0) {                                                     // HoldoutObjectStateGoal._sample_next_goal_positions / _orientations: state goal_idx of the list
+      int c = (a.advance_goals && !first) ? a.goal_cursor[e] : 0;
+      c = (c < 0 || c >= ng) ? 0 : c;
+      a.goal_cursor[e] = a.advance_goals ? (c + 1 >= ng ? 0 : c + 1) : 0;
+      // (get_target_rot + normalize_angles and qpos_goal's euler2quat(target_rot), goals/object_state.py:355-390: the caller's scene_goal_rot rows)
+      const float* row = a.scene_goal + ((size_t)s * a.max_scene_goals + c) * N * 7; const float* rot = a.scene_goal_rot + ((size_t)s * a.max_scene_goals + c) * N * 7;
+      for (int i = 0; i < n; i++) {
+        for (int k = 0; k < 3; k++) { F.gpos[i][k] = row[7 * i + k]; F.geul[i][k] = rot[7 * i + k]; }
+        for (int k = 0; k < 4; k++) { F.gquat[i][k] = row[7 * i + 3 + k]; F.gqe[i][k] = rot[7 * i + 3 + k]; }
+      }
+      F.recorded = 1;
+      return;
+    }
+  }
   RaDraws UG = {a.seed ^ RA_STREAM_GOAL, a.step, (unsigned)e, 0u};
   // the goal's yaws: the ones it has, or -- randomize_quaternion_along_z, drawn before the positions -- those turned by U(0, 2 pi) each; the placements below work
   // with the boxes rotated by THESE
@@ -643,20 +687,35 @@ __device__ inline void ra_begin_recipe(const RaRecipeArgs& a, RaRecipeLds& F, in
   const int N = a.num_objects, AD = a.action_dim;
   if (a.num_active) { n = a.num_objects_next[e]; n = n < 1 ? 1 : (n > N ? N : n); a.num_active[e] = n; }
   if (a.obj_group && a.group_mode == RA_GROUPS_SAMPLE) ra_sample_groups(a, e, n);
-  RaDraws U = {a.seed, a.step, (unsigned)e, RA_DRAW_PLACEMENT};
+  if (a.scene) { const int s = a.scene_next[e]; a.scene[e] = s < 0 ? 0 : (s >= a.num_scenes ? a.num_scenes - 1 : s); }
   float* yw = a.yaw + (size_t)e * N;
-  for (int i = 0; i < N; i++) yw[i] = i < n ? 2.f * RBC_PI * U() : 0.f;
-  if (!ra_place(a, ra_area(a, n), n, false, yw, 1, U, F.pos)) a.placement_failed[e] += 1;
+  F.init_scene = a.scene_init != 0;
+  if (F.init_scene) {
+    // HoldoutRearrangeEnv._randomize_object_initial_states (envs/rearrange/holdout.py:93-106): the recorded state, objects only -- the targets keep their model
+    // orientation, so the yaws a sampled first goal starts from are zero
+    const float* row = a.scene_init + (size_t)a.scene[e] * N * 7; const float* half = a.scene_init_half + (size_t)a.scene[e] * N * 3;
+    for (int i = 0; i < N; i++) {
+      yw[i] = 0.f;
+      if (i >= n) continue;
+      for (int k = 0; k < 3; k++) { F.pos[i][k] = row[7 * i + k]; F.ihalf[i][k] = half[3 * i + k]; }
+      for (int k = 0; k < 4; k++) F.iquat[i][k] = row[7 * i + 3 + k];
+    }
+  } else {
+    RaDraws U = {a.seed, a.step, (unsigned)e, RA_DRAW_PLACEMENT};
+    for (int i = 0; i < N; i++) yw[i] = i < n ? 2.f * RBC_PI * U() : 0.f;
+    if (!ra_place(a, ra_area(a, n), n, false, yw, 1, U, F.pos)) a.placement_failed[e] += 1;
+  }
   st = RA_STAGE_STABILISE; lf = a.stabilize_steps > 0 ? a.stabilize_steps : 1;
   a.hold[e] = 1; a.hold_ctrl[e] = 1; a.frozen[e] = RA_OBS_IN_RECIPE; a.solver_active[e] = 0; a.resetting[e] = 1;
   for (int d = 0; d < AD; d++) a.scripted[(size_t)e * AD + d] = 0.f;
 }
 // Entry i of a qpos row in which the env's n active objects sit at pos[o], turned about z by yaw[o] (`wrap`: normalised first), and the others at their parking
-// poses (ra_recipe_args.park_pose); `v` where no object lives.
-__device__ inline float ra_qpos_with_objects(const RaRecipeArgs& a, int i, int n, float v, const float (*pos)[3], const float* yaw, bool wrap) {
+// poses (ra_recipe_args.park_pose); `v` where no object lives.  `quat` (recorded scenes): the active objects' quaternions, in place of the yaws.
+__device__ inline float ra_qpos_with_objects(const RaRecipeArgs& a, int i, int n, float v, const float (*pos)[3], const float* yaw, bool wrap, const float (*quat)[4] = 0) {
   for (int o = 0; o < a.num_objects; o++) {
     const int d = i - a.obj_qposadr[o];
     if (d < 0 || d >= 7) continue;
+    if (quat) { v = o >= n ? a.park_pose[o][d] : (d < 3 ? pos[o][d] : quat[o][d - 3]); continue; }
     const float ez = wrap ? rbc_wrap(yaw[o]) : yaw[o];
     v = o >= n ? a.park_pose[o][d] : (d < 3 ? pos[o][d] : (d == 3 ? cosf(0.5f * ez) : (d == 6 ? sinf(0.5f * ez) : 0.f)));
   }
@@ -693,7 +752,7 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
       regoal = 1;
       gy = a.goal_rot + (size_t)e * N * 3 + 2; gstride = 3;
     }
-    if (gy) ra_sample_goal(a, F, e, n, bt.qpos + (size_t)e * nq, gy, gstride);
+    if (gy) ra_sample_goal(a, F, e, n, bt.qpos + (size_t)e * nq, gy, gstride, started != 0);
     // ---- an episode that ended on this step: its recipe begins (the returned observation / reward / done are the terminal ones)
     if (!started && st == RA_STAGE_LIVE && (forced || a.done[e]) && !regoal_only) { ended = 1; ra_begin_recipe(a, F, e, n, st, lf); }
     // controller ticks of the NEXT step's main-world launch: two for live envs, one inside the recipe, two on the recipe's last step
@@ -721,13 +780,17 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
       g[3] = act ? cosf(0.5f * ez) : 1.f; g[4] = 0.f; g[5] = 0.f; g[6] = act ? sinf(0.5f * ez) : 0.f;
       float* gr = a.goal_rot + ((size_t)e * N + lane) * 3;
       gr[0] = 0.f; gr[1] = 0.f; gr[2] = ez;
+      if (F.recorded && act) {                        // a recorded goal: its quaternion as recorded, its Euler angles as the observation shows them
+        for (int c = 0; c < 4; c++) g[3 + c] = F.gquat[lane][c];
+        for (int c = 0; c < 3; c++) gr[c] = F.geul[lane][c];
+      }
     }
     // the goal's mask of the placement area (goals/object_state.py:373-378): from the position written above, frozen until the next goal; a padded slot reads 1
     if (a.goal_in_area && lane < N) {
       const float u = a.soft_mask ? env_u01(a.seed ^ RA_STREAM_GOAL_MASK, a.step, (unsigned)e, 0u) : 0.f;
       a.goal_in_area[(size_t)e * N + lane] = lane < n ? ra_in_area(a, ra_area(a, n), F.gpos[lane], a.soft_mask != 0, u) : 1.f;
     }
-    for (int i = lane; i < nq; i += 64) a.qpos_goal[(size_t)e * nq + i] = ra_qpos_with_objects(a, i, n, bt.qpos[(size_t)e * nq + i], F.gpos, F.gyaw, true);
+    for (int i = lane; i < nq; i += 64) a.qpos_goal[(size_t)e * nq + i] = ra_qpos_with_objects(a, i, n, bt.qpos[(size_t)e * nq + i], F.gpos, F.gyaw, true, F.recorded ? F.gqe : 0);
     if (lane == 0) a.prev_valid[e] = 0;
   }
   __syncthreads();
@@ -738,7 +801,7 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
     for (int i = lane; i < nq; i += 64) {
       float v = m.qpos0[i];
       for (int j = 0; j < 6; j++) if (i == a.arm_qposadr[j]) v = a.arm_start[j];
-      bt.qpos[(size_t)e * nq + i] = ra_qpos_with_objects(a, i, n, v, F.pos, yw, false);      // (the parked objects are at rest: qvel is zeroed below)
+      bt.qpos[(size_t)e * nq + i] = ra_qpos_with_objects(a, i, n, v, F.pos, yw, false, F.init_scene ? F.iquat : 0);      // (the parked objects are at rest: qvel is zeroed below)
     }
     for (int i = lane; i < m.nv; i += 64) { bt.qvel[(size_t)e * m.nv + i] = 0.f; bt.qacc_warmstart[(size_t)e * m.nv + i] = 0.f; }
     for (int i = lane; i < m.nu; i += 64) bt.ctrl[(size_t)e * m.nu + i] = i < 6 ? a.arm_start[i] : 0.f;
@@ -758,7 +821,10 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
       if (ms.neq > 0 && lane < 7) sb.eq_data[(size_t)e * 7 * ms.neq + lane] = lane == 3 ? 1.f : 0.f;      // reset_mocap_welds
     }
     if (lane >= n && lane < N) { float* so = a.static_obs + ((size_t)e * N + lane) * 7; for (int q = 0; q < 7; q++) so[q] = 0.f; }
-    if (lane < n) {      // the static observation: bounding box of the yawed object, a random colour
+    if (lane < n && F.init_scene) {      // a recorded start: the box turned by the recorded rotation; the colours stay (HoldoutRearrangeEnv._apply_object_colors does nothing)
+      float* so = a.static_obs + ((size_t)e * N + lane) * 7;
+      for (int q = 0; q < 3; q++) so[q] = F.ihalf[lane][q];
+    } else if (lane < n) {      // the static observation: bounding box of the yawed object, a random colour
       float* so = a.static_obs + ((size_t)e * N + lane) * 7;
       ra_yawed_half(a, lane, yw[lane], so[0], so[1]); so[2] = a.obj_half[lane][2];
       for (int q = 0; q < 3; q++) so[3 + q] = env_u01(a.seed, a.step, (unsigned)e, RA_DRAW_COLOURS + 3u * lane + q);

@@ -1564,6 +1564,8 @@ int ra_env_post_step(rb_batch* b, rb_batch* solver, const ra_post_args* args, vo
   if ((a.rot_dist_type == RA_ROT_MOD90 && !a.parallel_quats) || (a.rot_dist_type == RA_ROT_MOD180 && !a.parallel_quats_180)) return fail("ra_env_post_step: rot_dist_type mod90 / mod180 needs its table of parallel quaternions");
   if (a.num_active && rgb::ra_kind_is_reach(a.goal_kind)) return fail("ra_env_post_step: num_active with a reach goal (one object)");
   if (a.num_active && a.max_timesteps_per_goal_per_obj < 0) return fail("ra_env_post_step: negative max_timesteps_per_goal_per_obj");
+  if (a.rel_dist && (a.obj_group || rgb::ra_kind_is_reach(a.goal_kind))) return fail("ra_env_post_step: rel_dist is computed for distinct objects only (no obj_group, no reach goal)");
+  if (a.rel_threshold > 0.f && !a.rel_dist) return fail("ra_env_post_step: rel_threshold needs rel_dist");
   if (solver) {
     if (solver->dev.B != b->dev.B || solver->device != b->device) return fail("ra_env_post_step: the two batches must have the same size and device");
     const RbModelDev& ds = solver->model->dev;
@@ -1641,6 +1643,18 @@ int ra_env_recipe_step(rb_batch* b, rb_batch* solver, const ra_recipe_args* args
     for (int k = 0; k < a.num_objects; k++)
       for (int c = 0; c < 7; c++)
         if (!(fabsf(a.park_pose[k][c]) < 1.0e4f)) return fail("ra_env_recipe_step: park_pose is not finite (or beyond 1e4: RG_STATUS_BAD_STATE guards 1e10)");
+  }
+  if (a.scene_init || a.scene_init_half || a.scene_goal || a.scene_goal_rot || a.scene_num_goals || a.num_scenes || a.max_scene_goals || a.scene_next || a.scene || a.goal_cursor || a.advance_goals) {      // recorded scenes
+    if (!a.scene_init && !a.scene_goal) return fail("ra_env_recipe_step: recorded scenes need scene_init or scene_goal");
+    if (a.goal_kind != RA_GOAL_OBJECT_STATE) return fail("ra_env_recipe_step: recorded scenes are the object-state goal with its sampling replaced (goal_kind 0)");
+    if (a.num_scenes < 1 || a.num_scenes > 65536) return fail("ra_env_recipe_step: num_scenes out of range (1..65536)");
+    if (!a.scene || !a.scene_next) return fail("ra_env_recipe_step: recorded scenes need scene and scene_next");
+    if (!a.scene_init != !a.scene_init_half) return fail("ra_env_recipe_step: scene_init and scene_init_half come together");
+    if (!a.scene_goal != !a.scene_goal_rot) return fail("ra_env_recipe_step: scene_goal and scene_goal_rot come together");
+    if (a.scene_goal && (!a.scene_num_goals || !a.goal_cursor || a.max_scene_goals < 1 || a.max_scene_goals > 65536))
+      return fail("ra_env_recipe_step: scene_goal needs scene_num_goals, goal_cursor and max_scene_goals in 1..65536");
+    if (!a.scene_goal && (a.scene_num_goals || a.max_scene_goals || a.advance_goals)) return fail("ra_env_recipe_step: scene_num_goals, max_scene_goals and advance_goals belong to scene_goal");
+    if (a.advance_goals < 0 || a.advance_goals > 1) return fail("ra_env_recipe_step: advance_goals is 0 or 1");
   }
   RbBatchDev sb; memset(&sb, 0, sizeof sb);
   const RbModelDev* ms = nullptr;

@@ -42,6 +42,7 @@ Masks of the placement area (`mask_obs_outside_placement_area`; the reference's 
 Not built for this env: vision, `teleport_to_goal`, per-group materials / colours / scales.
 """
 import ctypes
+import os
 from typing import Optional
 
 import numpy as np
@@ -108,6 +109,56 @@ def euler2quat(e):
     hx, hy, hz = 0.5 * e[..., 0], 0.5 * e[..., 1], 0.5 * e[..., 2]
     cx, sx, cy, sy, cz, sz = np.cos(hx), np.sin(hx), np.cos(hy), np.sin(hy), np.cos(hz), np.sin(hz)
     return np.stack([cx * cy * cz - sx * sy * sz, sx * cy * cz + cx * sy * sz, cx * sy * cz - sx * cy * sz, cx * cy * sz + sx * sy * cz], axis=-1)
+
+
+def quat2mat(q):
+    """robogym/utils/rotation.py quat2mat for quaternions (w, x, y, z) [.., 4] -> [.., 3, 3]"""
+    q = np.asarray(q, dtype=np.float64)
+    w, x, y, z = (q[..., k] for k in range(4))
+    s = 2.0 / (q * q).sum(-1)
+    rows = [[1.0 - s * (y * y + z * z), s * (x * y - w * z), s * (x * z + w * y)], [s * (x * y + w * z), 1.0 - s * (x * x + z * z), s * (y * z - w * x)],
+            [s * (x * z - w * y), s * (y * z + w * x), 1.0 - s * (x * x + y * y)]]
+    return np.stack([np.stack(r, -1) for r in rows], -2)
+
+
+def mat2euler(mat):
+    """robogym/utils/rotation.py mat2euler [.., 3, 3] -> [.., 3], with its gimbal branch below cos(pitch) = 4 eps"""
+    mat = np.asarray(mat, dtype=np.float64)
+    cy = np.sqrt(mat[..., 2, 2] ** 2 + mat[..., 1, 2] ** 2)
+    free = cy > 4.0 * np.finfo(np.float64).eps
+    return np.stack([np.where(free, -np.arctan2(mat[..., 1, 2], mat[..., 2, 2]), 0.0), -np.arctan2(-mat[..., 0, 2], cy),
+                     np.where(free, -np.arctan2(mat[..., 0, 1], mat[..., 0, 0]), -np.arctan2(-mat[..., 1, 0], mat[..., 1, 1]))], -1)
+
+
+def rotated_half(half, quat):
+    """`rotate_bounding_box` as `get_block_bounding_box` calls it: half extents `half` [N, 3] of boxes turned by the unit quaternions `quat` [.., N, 4] -> the half
+    extents of the turned boxes' bounding boxes [.., N, 3], sum_k |R_ik| half_k; `yawed_half` is this for rotations about z"""
+    return np.einsum("...ik,...k->...i", np.abs(quat2mat(quat)), np.asarray(half, dtype=np.float64))
+
+
+def load_state(state, num_objects, key="state"):
+    """A recorded object state -- {"obj_pos": [M, 3], "obj_quat": [M, 4] (w, x, y, z)}, the reference's npz format (envs/rearrange/holdouts), or the path of such a
+    file -- as [num_objects, 7] float64: the rows beyond `num_objects` cut off as the reference cuts them (holdout.py:98-103), the quaternions normalised.  `key`
+    names the argument in the errors."""
+    if isinstance(state, (str, os.PathLike)):
+        with np.load(state) as f:
+            state = {k: f[k] for k in ("obj_pos", "obj_quat")}
+    if not (isinstance(state, dict) and "obj_pos" in state and "obj_quat" in state):
+        raise ValueError("%s is not a state {\"obj_pos\": [N, 3], \"obj_quat\": [N, 4]} or the path of one" % key)
+    pos, quat = np.asarray(state["obj_pos"], dtype=np.float64), np.asarray(state["obj_quat"], dtype=np.float64)
+    if pos.ndim != 2 or pos.shape[1] != 3 or quat.shape != (pos.shape[0], 4):
+        raise ValueError("%s: obj_pos %r / obj_quat %r are not [N, 3] / [N, 4]" % (key, pos.shape, quat.shape))
+    if pos.shape[0] < int(num_objects):
+        raise ValueError("%s has %d rows, fewer than num_objects=%d" % (key, pos.shape[0], num_objects))
+    pos, quat = pos[:int(num_objects)], quat[:int(num_objects)]
+    norm = np.linalg.norm(quat, axis=-1, keepdims=True)
+    if not (np.isfinite(pos).all() and np.isfinite(quat).all() and (norm > 1e-9).all()):
+        raise ValueError("%s holds a position that is not finite or a zero quaternion" % key)
+    return np.concatenate([pos, quat / norm], -1)
+
+
+def _is_state(s):
+    return isinstance(s, (str, os.PathLike, dict))
 
 
 def sample_group_counts(random_state, total: int, lam_low: float = SAMPLE_LAM[0], lam_high: float = SAMPLE_LAM[1]):
@@ -373,7 +424,8 @@ class BatchedBlockRearrangeEnv:
                  object_groups="distinct", sample_lam=SAMPLE_LAM, goal_distance_ratio=1.0, goal_distance_min: float = 0.06, pickup_proba: float = 0.0,
                  stacking_proba: float = 0.0, rot_dist_type: str = "full", randomize_goal_rot: bool = False, model=None, domino_distance_mul: float = 4.0,
                  relative_placements=None, init_quats=None, max_num_objects: Optional[int] = None, icp_max_num_vertices: int = 500, icp_error_threshold: float = 0.15,
-                 icp_use_bbox_precheck: bool = False, mask_obs_outside_placement_area: bool = False, soft_mask: bool = False, mask_margin: float = 0.02):
+                 icp_use_bbox_precheck: bool = False, mask_obs_outside_placement_area: bool = False, soft_mask: bool = False, mask_margin: float = 0.02, initial_states=None, goal_states=None,
+                 advance_goals: bool = False):
         """`per_env_parameters`: every env carries its own copy of the randomisable model fields (`self.sim.params`, LargeModelSimulation(env_params=True)) -- what
         the reference's simulation randomizers and `stabilize_objects` write into `sim.model`.  On by default (measured cost: 0.7 % of the step,
         profiles/r05_ab_rb_env_params.txt); off: the model's own arrays, no randomizers, no damping change while the objects stabilise.
@@ -416,8 +468,26 @@ class BatchedBlockRearrangeEnv:
         writes (MASK_OBS_KEYS; `obs_dim` = 74 N + 23 + 2 nq).  Outside: max over x, y, z of the distance to the area's box (`placement_area_boundary`, of the env's own
         object count) >= `mask_margin`; with `soft_mask` inside with probability 1 - clip(distance / margin, 0, 1), one draw per env and step shared by its objects.  The
         goal's mask (`self.goal_in_area` [B, N] floats; `goal_objects_in_placement_area`, `goal_in_placement_area`) is made with the goal -- ra_recipe_kernel or
-        `_write_goal` -- and keeps its value until the next goal; unused slots read 1.  Off (default): no row, no pointer, no draw, the 24 keys."""
+        `_write_goal` -- and keeps its value until the next goal; unused slots read 1.  Off (default): no row, no pointer, no draw, the 24 keys.
+        Recorded scenes (the reference's holdout envs, envs/rearrange/holdout.py and goals/holdout_object_state.py, as arrays).  A state is
+        {"obj_pos": [M, 3], "obj_quat": [M, 4]} or the path of such an npz file (`load_state`: rows beyond `num_objects` cut off, quaternions normalised).
+        `initial_states`: one state or a list of S states -- every episode of env e starts from state `self.scene[e]` instead of a drawn placement: position and full
+        quaternion into qpos, `obj_bbox_size` the box turned by that rotation, no colour drawn (the rows keep (0, 0, 0, 1)); the rest of the recipe as it is.
+        `goal_states`: a list of states (the goals of every scene) or one such list per scene (an empty list: that scene's goals are sampled) -- every goal of an env
+        whose scene has goals is a recorded state: `goal` = its position and quaternion, `goal_rot` = the normalised mat2euler of it, `qpos_goal` carries
+        euler2quat(goal_rot); `randomize_goal_rot` does not turn it.  `advance_goals` False (default): every goal is the scene's state 0, which is what the
+        reference's code does; True: the goals run 0, 1, .. and wrap, from 0 again at every episode start (`self.goal_cursor`).  `self.scene_next` (int32 [B], a device
+        row; `set_scene_next` is the checked host setter; env e starts with scene e mod S) is latched into `self.scene` when that env's episode begins, on the host
+        route and the device route alike, which read the same tables and agree bit for bit.  A goal sampled after a recorded start begins from yaw 0: the
+        reference's holdout reset sets the objects, not the targets.  `success_threshold` may name `rel_dist` (HoldoutObjectStateGoal.goal_distance: each object's
+        distance from where the goal puts it relative to the object with the lowest goal z): `self.rel_dist` [B, N] and `info()["goal_dist"]["rel_dist"]` exist
+        whenever there are no duplicate groups, and with the threshold an object counts as achieved only below it too.  Block worlds, goal_kind object_state, no
+        `max_num_objects`."""
         self.B, self.N = int(batch_size), int(num_objects)
+        if (initial_states is not None or goal_states is not None) and max_num_objects is not None:
+            raise NotImplementedError("max_num_objects (per-env object counts) is not implemented together with initial_states / goal_states (recorded scenes) by the batched rearrange env")
+        if (initial_states is not None or goal_states is not None) and (model is not None or main_model is not None or self.ICP_ROT_DIST):
+            raise NotImplementedError("initial_states / goal_states (recorded scenes) are built for the block worlds of load_blocks_model, not for the ycb or domino worlds")
         self.mask_obs, self.soft_mask, self.mask_margin = bool(mask_obs_outside_placement_area), bool(soft_mask), float(mask_margin)
         if self.soft_mask and not self.mask_margin > 0:
             raise ValueError("soft_mask=True needs mask_margin > 0 (the probability is clip(distance / mask_margin, 0, 1)), got mask_margin=%r" % (mask_margin,))
@@ -574,9 +644,18 @@ class BatchedBlockRearrangeEnv:
         self.resetting, self.episode_started = z(B, dt=torch.bool), z(B, dt=torch.bool)
         self.nticks = torch.full((B,), 2, dtype=torch.int32, device=dev)       # state-less forwards (controller ticks) per env of the main world's launch
         self.wrapped = bool(wrappers)
+        self._fill_scenes(initial_states, goal_states, advance_goals)
         # ---- the arguments of the TCP hook, the env kernel and, for rot_dist_type icp, the launch in front of it
         self._fill_tcp_args(max_position_change, arm_reset_controller_error)
-        self._fill_post_args(dict(success_threshold or {"obj_pos": 0.04, "obj_rot": 0.2}), dict(penalty or dict(table_collision=0.0, objects_off_table=1.0, wrist_collision=0.0)),
+        st = dict(success_threshold or {"obj_pos": 0.04, "obj_rot": 0.2})
+        if "rel_dist" in st and self.group_mode != "distinct":
+            raise ValueError("success_threshold names rel_dist together with object_groups=%r: the relative distance is defined for distinct objects only "
+                             "(goals/holdout_object_state.py:67-69)" % (object_groups,))
+        if "rel_dist" in st and self.reach:
+            raise ValueError("success_threshold names rel_dist with a reach goal (one object, measured at the grip site)")
+        # (HoldoutObjectStateGoal.goal_distance: rel_dist whenever every object is its own group; here: where the threshold or a recorded scene asks for it)
+        self.rel_dist = z(B, N) if ("rel_dist" in st or self.num_scenes) and self.group_mode == "distinct" and not self.reach else None
+        self._fill_post_args(st, dict(penalty or dict(table_collision=0.0, objects_off_table=1.0, wrist_collision=0.0)),
                              goal_reward_per_object, success_reward, max_timesteps_per_goal_per_obj, successes_needed, use_goal_distance_reward, reward_clip, starting_seed)
         self.icp = self.icp_rel = self.icp_clouds = None
         if rot_dist_type == "icp":
@@ -608,6 +687,84 @@ class BatchedBlockRearrangeEnv:
             self.reobserve, self.ended, self.stabilised = torch.full((B,), _native.RA_OBS_SKIP, dtype=torch.uint8, device=dev), z(B, dt=torch.bool), z(B, dt=torch.bool)
             self._fill_recipe_args(starting_seed)
             self._fill_sync_reset_args()
+
+    def _fill_scenes(self, initial_states, goal_states, advance_goals):
+        """Recorded scenes: the state tables of `initial_states` / `goal_states` and what is derived from them once, in float64 -- the turned boxes of the starts
+        (`rotated_half`), the goals' normalised Euler angles and euler2quat of those -- as float32 host arrays (the host route) and device tensors (ra_recipe_args), and
+        the per-env rows `scene_next`, `scene`, `goal_cursor`.  Without tables: no row, no pointer."""
+        self.num_scenes, self.advance_goals = 0, bool(advance_goals)
+        self.scene_init = self.scene_init_half = self.scene_goal = self.scene_goal_rot = self.scene_num_goals = self.scene_next = self.scene = self.goal_cursor = None
+        if initial_states is None and goal_states is None:
+            if self.advance_goals:
+                raise ValueError("advance_goals=True without goal_states: there is no list of recorded goals to step through")
+            return
+        if self.goal_kind_name != "object_state":      # (the constructor's head has refused max_num_objects and the worlds that are no block worlds)
+            raise ValueError("initial_states / goal_states belong to goal_kind \"object_state\" (HoldoutObjectStateGoal is an ObjectStateGoal), not to %r" % (self.goal_kind_name,))
+        N, dev = self.N, self.device
+        init = goals = None
+        if initial_states is not None:
+            given = [initial_states] if _is_state(initial_states) else list(initial_states)
+            if not given:
+                raise ValueError("initial_states is an empty list")
+            init = np.stack([load_state(s, N, "initial_states[%d]" % i) for i, s in enumerate(given)])
+        if goal_states is not None:
+            given = [goal_states] if _is_state(goal_states) else list(goal_states)
+            per_scene = len(given) > 0 and not _is_state(given[0])
+            S = len(init) if init is not None else (len(given) if per_scene else 1)
+            if per_scene and len(given) != S:
+                raise ValueError("goal_states lists the goals of %d scenes, initial_states has %d" % (len(given), S))
+            per = [list(g) for g in given] if per_scene else [given] * S
+            goals = [[load_state(s, N, "goal_states[%d][%d]" % (i, j)) for j, s in enumerate(g)] for i, g in enumerate(per)]
+            if not any(goals):
+                raise ValueError("goal_states holds no state")
+        if self.advance_goals and goals is None:
+            raise ValueError("advance_goals=True without goal_states: there is no list of recorded goals to step through")
+        S = self.num_scenes = len(init) if init is not None else len(goals)
+        f32 = lambda x: np.ascontiguousarray(x, dtype=np.float32)
+        up = lambda x: torch.as_tensor(x, device=dev).contiguous()
+        if init is not None:
+            self._scene_init, self._scene_init_half = f32(init), f32(rotated_half(self.obj_half, init[..., 3:]))
+            self.scene_init, self.scene_init_half = up(self._scene_init), up(self._scene_init_half)
+            self.static_obs[:, :, 6] = 1.0      # (no colour is applied to a recorded start, HoldoutRearrangeEnv._apply_object_colors: the rows keep this)
+        if goals is not None:
+            G = max(len(g) for g in goals)
+            table = np.zeros((S, G, N, 7)); table[..., 3] = 1.0
+            for i, g in enumerate(goals):
+                if g:
+                    table[i, :len(g)] = np.stack(g)
+            eul = mat2euler(quat2mat(table[..., 3:]))
+            eul = np.mod(eul + np.pi, 2 * np.pi) - np.pi                    # get_target_rot + normalize_angles
+            self._scene_goal, self._scene_goal_rot = f32(table), f32(np.concatenate([eul, euler2quat(eul)], -1))
+            self._scene_num_goals = np.array([len(g) for g in goals], dtype=np.int32)
+            self.max_scene_goals = G
+            self.scene_goal, self.scene_goal_rot, self.scene_num_goals = up(self._scene_goal), up(self._scene_goal_rot), up(self._scene_num_goals)
+            self.goal_cursor = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.scene_next = (torch.arange(self.B, dtype=torch.int32, device=dev) % S).contiguous()
+        self.scene = self.scene_next.clone()
+
+    def set_scene_next(self, scenes, rows=None):
+        """The scene of the NEXT episode of the envs `rows` (default: every env), checked: an int or one per env, each in 0..S-1.  (Writing `self.scene_next`
+        directly, as a curriculum on the device does, is clamped to that range where it is latched.)"""
+        if not self.num_scenes:
+            raise ValueError("set_scene_next: the env was built without initial_states / goal_states")
+        c = np.asarray(scenes)
+        if c.size == 0 or not np.all(c == np.round(c)) or c.min() < 0 or c.max() >= self.num_scenes:
+            raise ValueError("scene_next %r: a scene index is outside 0..%d" % (np.asarray(scenes).tolist(), self.num_scenes - 1))
+        t = torch.as_tensor(c.astype(np.int32), device=self.device)
+        if rows is None:
+            self.scene_next.copy_(t.expand(self.B) if t.dim() == 0 else t)
+        else:
+            self.scene_next[torch.as_tensor(rows, device=self.device, dtype=torch.long)] = t
+
+    def record_state(self, rows=None):
+        """The live objects of the envs `rows` (default: every env; an int: that env alone, without the batch axis) as a state dict {"obj_pos", "obj_quat"} of
+        float64 arrays -- what the reference's `create_holdout` tool saves, and what `initial_states` / `goal_states` take."""
+        one = np.isscalar(rows)
+        idx = torch.arange(self.B, device=self.device) if rows is None else torch.as_tensor(np.atleast_1d(rows), device=self.device, dtype=torch.long)
+        q = self.sim.qpos[idx].cpu().numpy().astype(np.float64)
+        pose = np.stack([q[:, qa:qa + 7] for qa in self.obj_q], 1)
+        pose = pose[0] if one else pose
+        return {"obj_pos": pose[..., :3].copy(), "obj_quat": pose[..., 3:].copy()}
 
     def _fill_tcp_args(self, max_position_change, arm_reset_controller_error):
         """`self.tcp`, rb_tcp_args of the TCP hook: on the solver world, or (`ideal_arm`) on the env's own world (rb_tcp_args.self_world: TCP pose + denormalised action ->
@@ -699,6 +856,8 @@ class BatchedBlockRearrangeEnv:
             a.reward_clip = float(reward_clip)
         if self.pipelined:
             a.frozen = self.frozen.data_ptr()
+        if self.rel_dist is not None:
+            a.rel_dist, a.rel_threshold = _ptr(self.rel_dist), float(st.get("rel_dist", 0.0))
         if self.mask_obs:
             a.mask_obs, a.soft_mask, a.mask_margin, a.area_height, a.goal_in_area = 1, int(self.soft_mask), self.mask_margin, PLACEMENT_AREA_HEIGHT, _ptr(self.goal_in_area)
             (off_x, off_y, _), (width, height, _) = self.placement_area(N)
@@ -770,6 +929,13 @@ class BatchedBlockRearrangeEnv:
                     r.park_pose[i][k] = float(self.park_pose[i, k])
         if self.mask_obs:
             r.goal_in_area, r.soft_mask, r.mask_margin, r.area_height = _ptr(self.goal_in_area), int(self.soft_mask), self.mask_margin, PLACEMENT_AREA_HEIGHT
+        if self.num_scenes:
+            r.num_scenes, r.scene_next, r.scene = self.num_scenes, _ptr(self.scene_next), _ptr(self.scene)
+            if self.scene_init is not None:
+                r.scene_init, r.scene_init_half = _ptr(self.scene_init), _ptr(self.scene_init_half)
+            if self.scene_goal is not None:
+                r.scene_goal, r.scene_goal_rot, r.scene_num_goals, r.max_scene_goals = _ptr(self.scene_goal), _ptr(self.scene_goal_rot), _ptr(self.scene_num_goals), self.max_scene_goals
+                r.goal_cursor, r.advance_goals = _ptr(self.goal_cursor), int(self.advance_goals)
 
     def _fill_sync_reset_args(self):
         """What the synchronous episode API on the device adds to the recipe's arguments (`reset(mask, on_device=True)`, `reset_goals(on_device=True)`): the `active` row
@@ -939,6 +1105,8 @@ class BatchedBlockRearrangeEnv:
         out = {"goal_dist_obj_pos": self.goal_dist[:, 0], "goal_dist_obj_rot": self.goal_dist[:, 1], "goal_reset": self.goal_reset, "trial_success": self.trial_success,
                "sub_goal_is_successful": self.sub_goal_ok, "env_crash": self.env_crash, "objects_off_table": self.objects_off_table, "successes_so_far": self.successes,
                "steps_since_last_goal": self.info_ssl, "resetting": self.resetting, "episode_started": self.episode_started}
+        if self.rel_dist is not None:      # HoldoutObjectStateGoal.goal_distance's key, per object as the reference's goal_distance has it
+            out["goal_dist"] = {"rel_dist": self.rel_dist}
         if self.goal_kind_name == "stack":      # ObjectStackGoal.goal_distance's two more keys, summed as goal_info["goal_dist"] sums every key (robot_env.py:611)
             out["goal_dist_gripper_pos"], out["goal_dist_grasped"] = self.goal_dist_extra[:, 0], self.goal_dist_extra[:, 1]
         return out
@@ -1160,14 +1328,49 @@ class BatchedBlockRearrangeEnv:
         g[unused] = np.array([0, 0, 0, 1, 0, 0, 0], dtype=np.float32)
         self.goal[idx] = torch.tensor(g, device=dev)
         self.prev_valid[idx] = 0
+        self._write_goal_mask(rows, idx, g[..., :3], unused)
+
+    def _write_goal_mask(self, rows, idx, goal_pos, unused):
         if self.mask_obs and len(rows):
             # the goal's mask of the placement area (goals/object_state.py:373-378), from the goal rows as written, in the area of each env's count; an unused slot
             # reads 1.  soft_mask: one draw per env, after the positions' draws (the reference's np.random.random() inside check_objects_in_placement_area)
             bounds = [self.placement_area_boundary(int(c)) for c in self._counts(rows)]
             lo, hi = np.array([b[0] for b in bounds])[:, None, :], np.array([b[1] for b in bounds])[:, None, :]
             u = self._rng.random(len(rows))[:, None] if self.soft_mask else None
-            inside = objects_in_placement_area(g[..., :3], lo, hi, self.mask_margin, self.soft_mask, u) | unused
-            self.goal_in_area[idx] = torch.tensor(inside.astype(np.float32), device=dev)
+            inside = objects_in_placement_area(goal_pos, lo, hi, self.mask_margin, self.soft_mask, u) | unused
+            self.goal_in_area[idx] = torch.tensor(inside.astype(np.float32), device=self.device)
+
+    def _make_goal(self, rows, yaw, first):
+        """The next goal of the envs `rows`, whose goals (`first`: objects, at an episode start) have the yaws `yaw`: sampled (`_next_goal`), or for the envs whose
+        scene has recorded goals state `goal_cursor` of the scene's list -- no draw; what ra_sample_goal does on the device, from the same tables."""
+        rows = np.asarray(rows)
+        if self.scene_goal is None or len(rows) == 0:
+            return self._write_goal(rows, *self._next_goal(rows, yaw))
+        dev = self.device
+        idx = torch.as_tensor(rows, device=dev, dtype=torch.long)
+        sc = self.scene[idx].cpu().numpy().clip(0, self.num_scenes - 1)
+        ng = self._scene_num_goals[sc]
+        rec = ng > 0
+        if (~rec).any():
+            self._write_goal(rows[~rec], *self._next_goal(rows[~rec], np.asarray(yaw)[~rec]))
+        if not rec.any():
+            return
+        rows, idx, sc, ng = rows[rec], idx[torch.as_tensor(rec, device=dev)], sc[rec], ng[rec]
+        cur = np.zeros(len(rows), dtype=np.int64)
+        if self.advance_goals and not first:      # (HoldoutObjectStateGoal.goal_idx never moves in the reference: advance_goals False)
+            cur = self.goal_cursor[idx].cpu().numpy().astype(np.int64)
+            cur = np.where((cur < 0) | (cur >= ng), 0, cur)
+        self.goal_cursor[idx] = torch.as_tensor((((cur + 1) % ng) if self.advance_goals else 0 * cur).astype(np.int32), device=dev)
+        g, rot = self._scene_goal[sc, cur], self._scene_goal_rot[sc, cur]      # [R, N, 7]: position | quaternion, Euler angles | euler2quat of them
+        self.goal[idx] = torch.tensor(g, device=dev)
+        self.goal_rot[idx] = torch.tensor(rot[..., :3], device=dev)
+        qg = self.sim.qpos[idx].clone()                                   # qpos_goal: the current qpos with the objects at their goals (object_state.py:381-389)
+        for i, qa in enumerate(self.obj_q):
+            qg[:, qa:qa + 3] = torch.tensor(g[:, i, :3], device=dev)
+            qg[:, qa + 3:qa + 7] = torch.tensor(rot[:, i, 3:], device=dev)
+        self.qpos_goal[idx] = qg
+        self.prev_valid[idx] = 0
+        self._write_goal_mask(rows, idx, g[..., :3].astype(np.float64), np.zeros(g.shape[:2], dtype=bool))
 
     def _begin_episode_state(self, rows, idx):
         """What RearrangeEnv._reset writes before anything is simulated (common/base.py:897-932): both worlds as freshly made, the arm's start pose, object
@@ -1176,6 +1379,8 @@ class BatchedBlockRearrangeEnv:
         A = self.model.arrays
         if self.max_num_objects is not None:      # the count of the episode that begins: _recreate_sim builds the simulation with the current num_objects (common/base.py:850-856, 904)
             self.num_active[idx] = self.num_objects_next[idx].clamp(1, N)
+        if self.scene is not None:                 # ... and its scene (recorded scenes), latched the same way
+            self.scene[idx] = self.scene_next[idx].clamp(0, self.num_scenes - 1)
         counts = self._counts(rows)
         unused = np.arange(N)[None, :] >= counts[:, None]
         if self.group_mode == "sample":      # _randomize_object_groups: the first act of RearrangeEnv._reset (common/base.py:903), over the env's own count; an unused slot belongs to no group: -1
@@ -1203,6 +1408,15 @@ class BatchedBlockRearrangeEnv:
         if self.solver_sim is not None:
             self.solver_sim.qpos[idx[:, None], torch.tensor(self.solver_arm_q, device=dev)] = arm0
             self.solver_sim.eq_data[idx, :7] = torch.tensor([0, 0, 0, 1, 0, 0, 0], dtype=torch.float32, device=dev)     # reset_mocap_welds
+        if self.scene_init is not None:
+            # HoldoutRearrangeEnv._randomize_object_initial_states (holdout.py:93-106): the recorded state -- the objects only, the targets keep the model's
+            # orientation (the yaws a sampled first goal starts from: 0) --, the boxes turned by the recorded rotations, no colours; no draw
+            sc = self.scene[idx].cpu().numpy()
+            pose = self._scene_init[sc]
+            for i, qa in enumerate(self.obj_q):
+                self.sim.qpos[idx, qa:qa + 7] = torch.tensor(pose[:, i], device=dev)
+            self.static_obs[idx, :, :3] = torch.tensor(self._scene_init_half[sc], device=dev)
+            return np.zeros((len(rows), N))
         # object rotations about z and grid placement (common/base.py:613-640, 797-822): the env's first n objects in the placement area of n objects, the others
         # parked (identity orientation: yaw 0)
         yaw = self._rng.uniform(0.0, 2 * np.pi, (len(rows), N))
@@ -1289,7 +1503,12 @@ class BatchedBlockRearrangeEnv:
             for it in range(iterations):
                 # the envs of the mask run the stages in lockstep, so the host knows what the recipe's rows hold: `solver_active` is 0 for all of them while the
                 # objects stabilise (no solver world launch: it would skip every env) and 1 afterwards
-                if self.joint_control:      # every env of these launches is inside its recipe: the stored controls while the objects stabilise, then the scripted action
+                if it < stabilising and self.stabilize_steps <= 0 and self.scene_init is not None:
+                    # a recorded start without stabilisation: the stage of zero steps is counted, not simulated -- the episode starts AT the recorded state, as on the
+                    # host route; where it is the recipe's last launch, the forward of _observe_sync that the last physics launch would have carried
+                    if it == iterations - 1:
+                        self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=act32)
+                elif self.joint_control:      # every env of these launches is inside its recipe: the stored controls while the objects stabilise, then the scripted action
                     self.sim.env_step(action=self.scripted, nforward_ticks=2, flags=FLAG_FULL_FORWARD, active=act32, nticks=self.nticks, hold=self.hold_ctrl)
                 else:
                     if it >= stabilising:
@@ -1363,12 +1582,12 @@ class BatchedBlockRearrangeEnv:
             f[idx] = 0
         self.ema_value[idx] = 0; self.action_ema[idx] = 0          # SmoothActionWrapper.reset: a fresh filter, action_ema = 0
         self._randomize_simulation(idx)                               # simulation_randomizer.randomize AFTER _reset (robot_env.py:779-783)
-        self._write_goal(rows, *self._next_goal(rows, yaw))
+        self._make_goal(rows, yaw, first=True)
 
     def _regoal(self, rows):
         """ObjectStateGoal.next_goal for the live envs `rows`: the next goal, from the yaws of the one they have"""
         yaw = self.goal_rot[torch.as_tensor(rows, device=self.device, dtype=torch.long), :, 2].cpu().numpy().astype(np.float64)
-        self._write_goal(rows, *self._next_goal(rows, yaw))
+        self._make_goal(rows, yaw, first=False)
 
     # ------------------------------------------------------------------ pipelined resets
     def _reobserve(self, started, regoaled):
@@ -1771,4 +1990,5 @@ class SingleEnvView:
         a = np.asarray(action)
         t = torch.as_tensor((a.astype(np.int64) if self.env.wrapped else a.astype(np.float32))[None], device=self.env.device)
         obs, reward, done, info = self.env.step(t.contiguous())
-        return self._obs(obs), [float(x) for x in reward[0]], bool(done[0]), {k: (v[0].item() if v[0].dim() == 0 else self._np(v)) for k, v in info.items()}
+        one = lambda v: {k: one(x) for k, x in v.items()} if isinstance(v, dict) else (v[0].item() if v[0].dim() == 0 else self._np(v))      # (goal_dist: a dict of per-object rows)
+        return self._obs(obs), [float(x) for x in reward[0]], bool(done[0]), {k: one(v) for k, v in info.items()}
