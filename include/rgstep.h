@@ -36,7 +36,7 @@ enum {
   RG_F_TIME = 5,      /* float [B]         sim.data.time                                                   */
   RG_F_STATUS = 6,    /* uint32 [B]        sticky per-env status bits (RG_STATUS_*)                        */
   RG_F_STATS = 7,     /* float [B][4]      accumulated ncon, nefc, Newton iterations, substeps             */
-  RG_F_DEBUG = 8,     /* float [B][rg_debug_size()] stage dump of the first substep (flags & 1)            */
+  RG_F_DEBUG = 8,     /* float [B][rg_debug_size()] stage dump of the first substep (RG_FLAG_STAGE_DUMP)   */
   RG_F_COST = 9,      /* float [B]         shader cycles the last rg_batch_step_ex spent on the env (dispatch ordering) */
   RG_F_PAIRLB = 10,   /* float [B][npair]  collision cache: lower bounds on the pair distances (0 = unknown). Not state. */
   RG_F_ENVPRM = 11    /* float [B][rg_prm_layout()[0]] per-env model parameters, after rg_batch_enable_env_params          */
@@ -141,33 +141,46 @@ int rg_batch_copy_rows(rg_batch* b, int field, const void* src_dev, const int* m
  *                resets, per-env goal resets; the reference simply does not call step on those envs)
  *   nsubsteps    mj_step calls (MjSim.nsubsteps, mujoco_xml.py:249-260 / robot_env.py:132)
  *   nforward_ticks number of state-less mj_forward calls the reference makes afterwards (3 per env.step)
- *   flags        bit0: write the RG_F_DEBUG stage dump of the first substep
- *                bit1: accumulate per-stage cycle counters into the RG_F_DEBUG contact region (profiling)
- *                bit2: ignore the cached pair distance bounds (every pair goes through the sphere/box tests
+ *   flags        bit0 RG_FLAG_STAGE_DUMP: write the RG_F_DEBUG stage dump of the first substep
+ *                bit1 RG_FLAG_PROFILE: accumulate per-stage cycle counters into the RG_F_DEBUG contact region (profiling)
+ *                bit2 RG_FLAG_NO_PAIR_CACHE: ignore the cached pair distance bounds (every pair goes through the sphere/box tests
  *                      each substep; results are bit-identical either way — test hook for that claim)
- *                bit3: hull support points by scanning every vertex instead of the per-direction-cell
+ *                bit3 RG_FLAG_SCAN_HULL_VERTICES: hull support points by scanning every vertex instead of the per-direction-cell
  *                      candidate lists (bit-identical as well; test hook)
- *                bit4: contact depth / normal of convex pairs from the final MPR portal's PLANE instead of libccd's closest
+ *                bit4 RG_FLAG_MPR_PLANE_DEPTH: contact depth / normal of convex pairs from the final MPR portal's PLANE instead of libccd's closest
  *                      point on the final portal TRIANGLE (the default, = MuJoCo 2.0's mjc_Convex).  The two agree whenever
  *                      the origin projects inside the triangle; the plane variant does not depend on the rounding-level
  *                      tie breaks that pick the triangle on flat contacts.  The flag selects round 1's contact generation as a
  *                      whole: pairs of two boxes then go through MPR too (one contact) instead of the multi-point box-box
  *                      routine (the default, = mjc_BoxBox: face clipping, up to 8 contacts per pair).
- *                bit5: evaluate data.sensordata (touch sensors, mj_sensorAcc) into the xdata row: the last of the state-less
+ *                bit5 RG_FLAG_SENSORS: evaluate data.sensordata (touch sensors, mj_sensorAcc) into the xdata row: the last of the state-less
  *                      forwards then runs in full (collision and constraint solve at the final state, as mj_forward does),
  *                      about one more substep of work.  Needs xdata_dev and nforward_ticks >= 1.
- *                bit6: dense Newton step with the forward substitution as its own pass instead of inside the
+ *                bit6 RG_FLAG_SEPARATE_FORWARD_SUBSTITUTION: dense Newton step with the forward substitution as its own pass instead of inside the
  *                      factorisation (same result to rounding; test hook)
- *                bit7: substep-granular dispatch (RG_CFG_ROLLOUT, nsubsteps >= 2, no bit 0 / 1 / 5): the launch is a grid of
+ *                bit7 RG_FLAG_SUBSTEP_ITEMS: substep-granular dispatch (RG_CFG_ROLLOUT, nsubsteps >= 2, no bit 0 / 1 / 5): the launch is a grid of
  *                      persistent workgroups that draw (env, substep) work items in substep-major order instead of one workgroup
  *                      per env.step, so the device stays full to the end of the launch; bit-identical results.  An env that
  *                      exceeds the rollout capacities in substep s gets redo_dev[e] = s + 1.  Ignored where the device probe
  *                      at rg_batch_create found it unavailable (rg_batch_items_info).
- *                bit9: test hook for the hand-over: a rollout-configuration substep with more than 5 contacts counts as exceeding the
+ *                bit9 RG_FLAG_CAPACITY_TEST_HOOK: test hook for the hand-over: a rollout-configuration substep with more than 5 contacts counts as exceeding the
  *                      capacities (the env goes to redo_dev although it would fit)
- *                bit8: active_dev is the redo_dev array of a rollout launch: entry - 1 is the first substep still to do
+ *                bit8 RG_FLAG_RESUME: active_dev is the redo_dev array of a rollout launch: entry - 1 is the first substep still to do
  *                      (the env.step is resumed there; entry 1 = from the start)
+ *                bit10 RG_FLAG_DESERT_QUEUE0: test hook for the substep-granular dispatch: its queue 0 is left unserved, as if that XCD had received no
+ *                      workgroup (the launch behind it must complete those envs)
  *   stream       hipStream_t (NULL = default stream).  Asynchronous. */
+#define RG_FLAG_STAGE_DUMP 1
+#define RG_FLAG_PROFILE 2
+#define RG_FLAG_NO_PAIR_CACHE 4
+#define RG_FLAG_SCAN_HULL_VERTICES 8
+#define RG_FLAG_MPR_PLANE_DEPTH 16
+#define RG_FLAG_SENSORS 32
+#define RG_FLAG_SEPARATE_FORWARD_SUBSTITUTION 64
+#define RG_FLAG_SUBSTEP_ITEMS 128
+#define RG_FLAG_RESUME 256
+#define RG_FLAG_CAPACITY_TEST_HOOK 512
+#define RG_FLAG_DESERT_QUEUE0 1024
 int rg_batch_step(rg_batch* b, const float* action_dev, const float* goal_quat_dev, float* obs_dev, float* goal_dist_dev,
                   const int* active_dev, int nsubsteps, int nforward_ticks, int flags, void* stream);
 /* The same launch with every optional per-env input spelled out.  Arrays are device pointers or NULL.
@@ -439,7 +452,13 @@ enum {
   RB_F_EQ_ACTIVE = 14,  /* int32 [B][neq]       model.eq_active (envs/rearrange/common/base.py:452-455)                                     */
   RB_F_SENSORDATA = 15  /* float [B][nsensordata] data.sensordata of the last full forward (step flags bit 5)                               */
 };
-/* step flags bit 5 (32): the LAST state-less forward of the call runs in full (mj_forward: collision, constraint solve) and the sensors are
+/* The step flags of the large-model stepper are the RG_FLAG_* bits above where the two steppers share a meaning: RG_FLAG_STAGE_DUMP, RG_FLAG_PROFILE,
+ * RG_FLAG_SCAN_HULL_VERTICES, RG_FLAG_MPR_PLANE_DEPTH (box and plane pairs then go through MPR too) and RG_FLAG_SENSORS.  Two bits are its own, both test
+ * hooks with the same results to rounding: RB_FLAG_DENSE_SOLVE (bit 2) solves with the dense factor where the kinematic tree's block elimination would run,
+ * RB_FLAG_NO_OBB_PRUNE (bit 11) prunes collision pairs by their bounding spheres only, without the oriented-box test. */
+#define RB_FLAG_DENSE_SOLVE 4
+#define RB_FLAG_NO_OBB_PRUNE 2048
+/* step flags bit 5 (RG_FLAG_SENSORS): the LAST state-less forward of the call runs in full (mj_forward: collision, constraint solve) and the sensors are
  * evaluated from it (mj_sensorPos / mj_sensorAcc with mj_rnePostConstraint); the stage arrays of the scratch row (body frames, velocities,
  * contact list) then describe the final state, which is what the rearrange observation reads (envs/rearrange/common/base.py:376-421).
  *
@@ -500,7 +519,7 @@ int rb_multi_launch(void* stream);
  * (goals/object_state.py:492-599), MultiGoalTracker.process and the gripper hand-over to the solver world (joint_controlled_tcp_arm.py:114-129).
  * The main batch must have been stepped with flags bit 5 (the row is read from the final forward's stage arrays).  goal_reset[e] = 1 asks the
  * host for a new goal (ObjectStateGoal.next_goal is placement sampling: host work). */
-/* Codes of the rearrange env kernels, each defined here once (robogym_amd/_native.py mirrors them).
+/* Codes of the rearrange env kernels, each defined here once (robogym_amd/_native.py reads them from this file).
  * goal kinds (ra_post_args.goal_kind, ra_recipe_args.goal_kind), in the order of GOAL_KINDS (robogym_amd/envs/rearrange/blocks.py): */
 #define RA_GOAL_OBJECT_STATE 0
 #define RA_GOAL_PICKANDPLACE 1

@@ -1335,8 +1335,8 @@ __device__ __forceinline__ void rb_broadphase(RbM m, RbLds& s, float* S, int fla
   const float *gpos = SC(GPOS), *gquat = SC(GQUAT);
   if (TID == 0) { s.ncand = 0; s.ncand2 = 0; s.ncon = s.neqcon; }
   BSYNC();
-  const bool multipoint = !(flags & 16);   // box - box and plane - box pairs have their own multi-point routines (bit 4: everything through MPR / the support map)
-  const bool obb = !(flags & 2048);        // (bit 11: bounding spheres only, the test switch of the oriented-box prune)
+  const bool multipoint = !(flags & RG_FLAG_MPR_PLANE_DEPTH);   // box - box and plane - box pairs have their own multi-point routines (bit 4: everything through MPR / the support map)
+  const bool obb = !(flags & RB_FLAG_NO_OBB_PRUNE);        // (bit 11: bounding spheres only, the test switch of the oriented-box prune)
   const int halfcand = m.maxcand >> 1;
   // broadphase: the static pair list against bounding spheres (planes: distance of the sphere to the plane), then the geoms' oriented boxes.
   // Two lists: pairs for the support-map routines from the front of the candidate array, box - box / plane - box pairs from its end
@@ -1379,10 +1379,10 @@ __device__ __forceinline__ void rb_broadphase(RbM m, RbLds& s, float* S, int fla
 __device__ __forceinline__ void rb_narrow_convex(RbM m, RbLds& s, float* S, int flags) {
   const int* cand = (const int*)SC(CAND);
   const float *gpos = SC(GPOS), *gquat = SC(GQUAT);
-  const bool multipoint = !(flags & 16);
+  const bool multipoint = !(flags & RG_FLAG_MPR_PLANE_DEPTH);
   (void)multipoint;
   // narrowphase: one quad per candidate, 64 candidates per trip
-  MprEnv E; E.mesh_vert = m.b_mesh_rec; E.cell_adr = m.b_cell_adr; E.cell_blk = (const rgf4*)m.b_cell_blk; E.cell_ovf = (const rgf4*)m.b_cell_ovf; E.prof = 0; E.cells = !(flags & 8); E.plane_depth = (flags & 16) != 0;
+  MprEnv E; E.mesh_vert = m.b_mesh_rec; E.cell_adr = m.b_cell_adr; E.cell_blk = (const rgf4*)m.b_cell_blk; E.cell_ovf = (const rgf4*)m.b_cell_ovf; E.prof = 0; E.cells = !(flags & RG_FLAG_SCAN_HULL_VERTICES); E.plane_depth = (flags & RG_FLAG_MPR_PLANE_DEPTH) != 0;
   const int ncand = s.ncand;
   float* con = SC(CON);
   for (int base = 0; base < ncand; base += RB_T / 4) {
@@ -1441,7 +1441,7 @@ __device__ __forceinline__ void rb_narrow_box(RbM m, RbLds& s, float* S, int fla
   const int* cand = (const int*)SC(CAND);
   const float *gpos = SC(GPOS), *gquat = SC(GQUAT);
   float* con = SC(CON);
-  const bool multipoint = !(flags & 16);
+  const bool multipoint = !(flags & RG_FLAG_MPR_PLANE_DEPTH);
   // box - box (mjc_BoxBox, up to 8 contacts) and plane - box (up to 4 corners): 32 lanes per pair, 8 pairs per trip
   if (multipoint) {
     const int ncand2 = s.ncand2;
@@ -2453,9 +2453,9 @@ RB_STAGE void sv_M_solve(RbCtx c, int mode, int flags) {
   RB_STAGE_ENTER();
   const float* diag = mode ? PRM(dof_damping, RB_P_DOF_DAMPING) : (const float*)0; const float h = mode ? s.timestep : 0.f;
   const float* src = mode ? s.grad : s.qfrc_smooth; float* dst = mode ? s.search : s.qacc_smooth;
-  if (m.b_tree8[0] > 0 && !(flags & 4)) { rb_trees8_solve(m, s, SC(MSP), diag, h, src, dst, 1.f); return; }
+  if (m.b_tree8[0] > 0 && !(flags & RB_FLAG_DENSE_SOLVE)) { rb_trees8_solve(m, s, SC(MSP), diag, h, src, dst, 1.f); return; }
   for (int grp = 0; grp < m.ngroup; grp++) {
-    if (m.b_star_grp[4 * grp + 3] && !(flags & 4)) { rb_star_group_solve(m, s, SC(MSP), grp, diag, h, src, dst, 1.f); continue; }   // (flags bit 2: dense path everywhere, test hook)
+    if (m.b_star_grp[4 * grp + 3] && !(flags & RB_FLAG_DENSE_SOLVE)) { rb_star_group_solve(m, s, SC(MSP), grp, diag, h, src, dst, 1.f); continue; }   // (flags bit 2: dense path everywhere, test hook)
     rb_M_block(m, s, SC(MSP), grp, diag, h);
 #if RB_T == 64 && !defined(RB_LDS_CHOL)
     if (!rb_reg_solve(m, s, grp, src, dst, 1.f) && TID == 0) s.status |= RG_STATUS_BAD_FACTOR;
@@ -2468,7 +2468,7 @@ RB_STAGE void sv_M_solve(RbCtx c, int mode, int flags) {
 }
 __device__ __forceinline__ int rb_solve(RbCtx cx, RbM m, RbLds& s, float* S, int flags) {
   long long tq0 = rg_clock(), tq1;
-#define RB_PROFS(k) do { if (flags & 2) { BSYNC(); tq1 = rg_clock(); if (TID == 0) s.prof[k] += (float)(tq1 - tq0); tq0 = tq1; } } while (0)
+#define RB_PROFS(k) do { if (flags & RG_FLAG_PROFILE) { BSYNC(); tq1 = rg_clock(); if (TID == 0) s.prof[k] += (float)(tq1 - tq0); tq0 = tq1; } } while (0)
   const int nv = m.nv, ne = s.nefc;
   float* row = SC(ROW); const float* Msp = SC(MSP);
   if (ne == 0) { BFOR(i, nv) { s.qa[i] = s.qacc_smooth[i]; s.qfrc_con[i] = 0.f; } BSYNC(); return 0; }
@@ -2515,7 +2515,7 @@ __device__ __forceinline__ int rb_solve(RbCtx cx, RbM m, RbLds& s, float* S, int
     // search = - inv(H) grad, group by group
     bool okf = true;
     for (int grp = 0; grp < m.ngroup; grp++) {
-      if (m.b_star_grp[4 * grp] && !(flags & 4)) {   // H = M + diagonal on this group: block elimination along the tree
+      if (m.b_star_grp[4 * grp] && !(flags & RB_FLAG_DENSE_SOLVE)) {   // H = M + diagonal on this group: block elimination along the tree
         sv_star_direction(cx, grp, 0); RB_PROFS(10);
         sv_star_direction(cx, grp, 1); RB_PROFS(11);
         continue;
@@ -2804,20 +2804,20 @@ __device__ __forceinline__ void rb_step_body(const RbModelDev* mp, RbKlp klp, co
     float bd = 0; BFOR(i, nq) bd += (fabsf(s.qpos[i]) < 1e10f) ? 0.f : 1.f; BFOR(i, nv) bd += (fabsf(s.qvel[i]) < 1e10f) ? 0.f : 1.f;
     if (rb_sum(s, bd) > 0) { if (TID == 0) s.status |= RG_STATUS_BAD_STATE; break; }
     long long tp0 = rg_clock(), tp1;
-#define RB_PROF(k) do { if (flags & 2) { BSYNC(); tp1 = rg_clock(); if (TID == 0) s.prof[k] += (float)(tp1 - tp0); tp0 = tp1; } } while (0)
+#define RB_PROF(k) do { if (flags & RG_FLAG_PROFILE) { BSYNC(); tp1 = rg_clock(); if (TID == 0) s.prof[k] += (float)(tp1 - tp0); tp0 = tp1; } } while (0)
     sb_position(c); RB_PROF(0);
     sb_tendon(c); sb_crb(c); RB_PROF(1);
     sb_velocity(c); RB_PROF(2);
     sb_collision(c, flags); sb_narrow_convex(c, flags); sb_narrow_box(c, flags); RB_PROF(3);
     sb_rows(c); RB_PROF(4);
     sb_smooth(c, flags);
-    if ((flags & 1) && sub == 0) {   // stage dump of the first mj_step: ncon, nefc (the arrays themselves are read from the scratch row)
+    if ((flags & RG_FLAG_STAGE_DUMP) && sub == 0) {   // stage dump of the first mj_step: ncon, nefc (the arrays themselves are read from the scratch row)
       if (TID == 0) { SC(DBG)[0] = (float)s.ncon; SC(DBG)[1] = (float)s.nefc; }
       BFOR(i, nv) { SC(DBG)[8 + i] = s.qfrc_bias[i]; SC(DBG)[8 + nv + i] = s.qfrc_passive[i]; SC(DBG)[8 + 2 * nv + i] = s.qfrc_act[i]; SC(DBG)[8 + 3 * nv + i] = s.qacc_smooth[i]; }
     }
     RB_PROF(5);
     const int iters = sb_solve(c, flags); RB_PROF(6);
-    if ((flags & 1) && sub == 0) { if (TID == 0) SC(DBG)[2] = (float)iters; BFOR(i, nv) SC(DBG)[8 + 4 * nv + i] = s.qa[i]; }
+    if ((flags & RG_FLAG_STAGE_DUMP) && sub == 0) { if (TID == 0) SC(DBG)[2] = (float)iters; BFOR(i, nv) SC(DBG)[8 + 4 * nv + i] = s.qa[i]; }
     st_ncon += s.ncon; st_nefc += s.nefc; st_iter += iters; nsub_done++;
     bd = 0; BFOR(i, nv) bd += (fabsf(s.qa[i]) < 1e10f) ? 0.f : 1.f;
     if (rb_sum(s, bd) > 0) { if (TID == 0) s.status |= RG_STATUS_BAD_STATE; break; }
@@ -2826,10 +2826,10 @@ __device__ __forceinline__ void rb_step_body(const RbModelDev* mp, RbKlp klp, co
     if (TID == 0) s.time += s.timestep;
     BSYNC();
   }
-  if ((flags & 2) && TID < 16) SC(DBG)[8 + 5 * nv + TID] = s.prof[TID];   // stage cycle counters: frames+com, tendon+crb, velocity, collision, rows, smooth, Newton, Euler
+  if ((flags & RG_FLAG_PROFILE) && TID < 16) SC(DBG)[8 + 5 * nv + TID] = s.prof[TID];   // stage cycle counters: frames+com, tendon+crb, velocity, collision, rows, smooth, Newton, Euler
   // ---- the state-less forward() calls of the reference: only their PID side effect touches the state
   const int nticks = L.bt.nticks ? L.bt.nticks[e] : L.nforward_ticks;
-  const bool full_forward = (flags & 32) && nticks > 0;   // bit 5: the last state-less forward runs in full (mj_forward) and the sensors are read from it
+  const bool full_forward = (flags & RG_FLAG_SENSORS) && nticks > 0;   // bit 5: the last state-less forward runs in full (mj_forward) and the sensors are read from it
   if (nticks > 0) {
     sb_position(c); sb_tendon(c);
     for (int k = 0; k < nticks - (full_forward ? 1 : 0); k++) sb_pid(c, 0);

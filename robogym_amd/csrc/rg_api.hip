@@ -823,14 +823,14 @@ int rg_batch_step_ex(rg_batch* b, const rg_step_args* a) {
   bt.action = a->action_dev; bt.goal_quat = a->goal_quat_dev; bt.obs = a->obs_dev; bt.goal_dist = a->goal_dist_dev; bt.active = a->active_dev;
   bt.hold = a->hold_dev; bt.nticks = a->nticks_dev; bt.order = a->order_dev;
   // flags bit 5 (sensordata): the sensor-evaluating instantiation, which has the large capacities (no redo hand-off needed)
-  const bool sens = (a->flags & 32) != 0 && a->xdata_dev && b->model->dev.nsensor > 0;
-  const bool large = a->config == RG_CFG_LARGE || sens, prof = (a->flags & 2) != 0;
+  const bool sens = (a->flags & RG_FLAG_SENSORS) != 0 && a->xdata_dev && b->model->dev.nsensor > 0;
+  const bool large = a->config == RG_CFG_LARGE || sens, prof = (a->flags & RG_FLAG_PROFILE) != 0;
   if (a->config != RG_CFG_LARGE && a->config != RG_CFG_ROLLOUT) return fail("rg_batch_step: unknown kernel configuration");
   bt.redo = large ? nullptr : a->redo_dev;
   bt.preticks = a->preticks_dev;
   bt.xdata = a->xdata_dev;
   // flags bit 7: substep-granular dispatch (rollout configuration, >= 2 substeps, no debug / profiling / sensor pass): see rg_step_items_kernel
-  const bool items = (a->flags & 128) && !large && !(a->flags & (1 | 2 | 256)) && a->nsubsteps >= 2 && b->items_slots > 0;
+  const bool items = (a->flags & RG_FLAG_SUBSTEP_ITEMS) && !large && !(a->flags & (RG_FLAG_STAGE_DUMP | RG_FLAG_PROFILE | RG_FLAG_RESUME)) && a->nsubsteps >= 2 && b->items_slots > 0;
   RgLaunch launch_args{b->model->aux, b->env, bt, a->nsubsteps, a->nforward_ticks, a->flags, items ? b->items_queues : 1};
   if (items) {
     const long long nitems = (long long)bt.B * a->nsubsteps;

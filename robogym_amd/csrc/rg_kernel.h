@@ -1292,12 +1292,12 @@ RG_STAGE void rg_narrow_boxbox(RgCtx c, int ncand) {
 }
 template <int G> RG_STAGE void rg_narrow_phase1(RgCtx c, int ncand) {
   RgM m = RG_M(c); RgLRef L = RG_L(c); RgLds& s = RG_S();
-  bool cells = !(L.flags & 8);
+  bool cells = !(L.flags & RG_FLAG_SCAN_HULL_VERTICES);
   rgf4* sepdir = L.bt.sepdir ? (rgf4*)L.bt.sepdir + (size_t)rg_env(L) * m.npair : (rgf4*)0;
-  float* pairlb = (L.bt.pairlb && !(L.flags & 4)) ? L.bt.pairlb + (size_t)rg_env(L) * m.npair : (float*)0;
+  float* pairlb = (L.bt.pairlb && !(L.flags & RG_FLAG_NO_PAIR_CACHE)) ? L.bt.pairlb + (size_t)rg_env(L) * m.npair : (float*)0;
   const float gscale = rg_prm(m, L)[RG_PRM_GEOM_SCALE];
   MprEnv E = rg_mpr_env(m, (float*)0, cells);
-  const bool boxbox = !(L.flags & 16);   // box-box pairs have their own routine (rg_narrow_boxbox)
+  const bool boxbox = !(L.flags & RG_FLAG_MPR_PLANE_DEPTH);   // box-box pairs have their own routine (rg_narrow_boxbox)
   for (int base = 0; base < ncand; base += RG_WAVE / G) {
     int ci = base + LANE / G;
     bool keep = false; int p = 0;
@@ -1331,12 +1331,12 @@ template <int G> RG_STAGE void rg_narrow_phase1(RgCtx c, int ncand) {
 }
 template <int G> RG_STAGE_BIG void rg_narrow_phase2(RgCtx c, int ncand2) {
   RgM m = RG_M(c); RgLRef L = RG_L(c); RgLds& s = RG_S();
-  bool cells = !(L.flags & 8);
-  float* prof = (L.flags & 2) ? s.prof : (float*)0;
+  bool cells = !(L.flags & RG_FLAG_SCAN_HULL_VERTICES);
+  float* prof = (L.flags & RG_FLAG_PROFILE) ? s.prof : (float*)0;
   rgf4* sepdir = L.bt.sepdir ? (rgf4*)L.bt.sepdir + (size_t)rg_env(L) * m.npair : (rgf4*)0;
   const float gscale = rg_prm(m, L)[RG_PRM_GEOM_SCALE];
   MprEnv E = rg_mpr_env(m, prof, cells);
-  E.plane_depth = (L.flags & 16) != 0;
+  E.plane_depth = (L.flags & RG_FLAG_MPR_PLANE_DEPTH) != 0;
   for (int base = 0; base < ncand2; base += RG_WAVE / G) {
     int ci = base + LANE / G;
     bool hit = false;
@@ -1475,7 +1475,7 @@ __device__ __forceinline__ void rg_collision(RgCtx c, RgM m, RgLds& s, const flo
   if (prof && LANE == 0) { prof[16] += (float)(rg_clock() - tb0); prof[17] += ncand; prof[18] += ncand2; }
   rg_narrow_phase2<4>(c, ncand2);   // quads whatever the queue length: a support's first four candidates are one load round, 16 queries per trip (measured against 8- and 16-lane groups for short queues: quads win everywhere, profiles/r02_ab.txt)   // (quads: a support's first four candidates are one load round, and a crowded queue gets through in half the trips)
   if (prof && LANE == 0) prof[19] += (float)(rg_clock() - tb0);
-  if (!(RG_L(c).flags & 16) && __ballot(bbany) != 0) rg_narrow_boxbox(c, ncand);
+  if (!(RG_L(c).flags & RG_FLAG_MPR_PLANE_DEPTH) && __ballot(bbany) != 0) rg_narrow_boxbox(c, ncand);
   // plane pairs (rare: something near the floor), whole wave cooperating, one pair at a time.  Which candidates are plane
   // pairs is found lane-parallel from the pair headers (a serial scan of ~25 candidates cost two dependent loads each).
   if (__ballot(plany) != 0)   // (no plane pair among the candidates: nothing to look for)
@@ -2611,10 +2611,10 @@ __device__ __forceinline__ LsPt rg_ls_eval(const LsRows& L, float alpha, float q
 // (trees no constraint row can touch keep qacc = qacc_smooth).  Result: s.qacc, s.qfrc_con (full space).
 template <bool SENSORS> __device__ __forceinline__ int rg_solve(RgM m, RgLds& s, const float* P, int& nefc_out, int flags, float warm /* qacc_warmstart[LANE] */) {
   long long t0 = rg_clock(), t1;
-#define PROFS(k) do { if (flags & 2) { t1 = rg_clock(); if (LANE == 0) s.prof[k] += (float)(t1 - t0); t0 = t1; } } while (0)
+#define PROFS(k) do { if (flags & RG_FLAG_PROFILE) { t1 = rg_clock(); if (LANE == 0) s.prof[k] += (float)(t1 - t0); t0 = t1; } } while (0)
 #ifdef RG_FINE_PROF
   long long tf0 = rg_clock(), tf1;
-#define PROFF(k) do { if (flags & 2) { tf1 = rg_clock(); if (LANE == 0) s.prof[k] += (float)(tf1 - tf0); tf0 = tf1; } } while (0)
+#define PROFF(k) do { if (flags & RG_FLAG_PROFILE) { tf1 = rg_clock(); if (LANE == 0) s.prof[k] += (float)(tf1 - tf0); tf0 = tf1; } } while (0)
 #else
 #define PROFF(k) do { } while (0)
 #endif
@@ -2685,7 +2685,7 @@ template <bool SENSORS> __device__ __forceinline__ int rg_solve(RgM m, RgLds& s,
   // The factor of H is kept while the set of quadratic rows stays the same (H depends on nothing else).
   PROFF(24);
   float cost = 0, oldcost = 0; int iters = 0; bool have_factor = false;
-  bool fresh_rhs = false; const bool rhs_row = (nvc + 1) * hs <= RG_HWORDS && !(flags & 64);   // (room for the right-hand-side row under the work matrix; flag bit 6: test hook, the separate forward substitution)
+  bool fresh_rhs = false; const bool rhs_row = (nvc + 1) * hs <= RG_HWORDS && !(flags & RG_FLAG_SEPARATE_FORWARD_SUBSTITUTION);   // (room for the right-hand-side row under the work matrix; flag bit 6: test hook, the separate forward substitution)
   const bool regchol = rhs_row && rg_cholreg_ok(nvc);   // the dense step in registers (rg_chol_inv_solve); flag bit 6 therefore also selects the LDS factorisation
   for (int iter = 0;; iter++) {
     float gauss = 0; PFOR(i, nvc) gauss += 0.5f * (s.Ma[i] - s.fs[i]) * (s.a[i] - s.as[i]);
@@ -2693,8 +2693,8 @@ template <bool SENSORS> __device__ __forceinline__ int rg_solve(RgM m, RgLds& s,
     bool flags_changed; int nset; float cc = rg_constraint_update(m, s, RR, flags_changed, nset);
     oldcost = cost; cost = gauss + cc;
 #ifdef RG_FINE_PROF
-    if ((flags & 2) && iter > 0 && flags_changed && LANE == 0) { const float k = s.prof[47]; s.prof[36] += 1.f; s.prof[37] += k; s.prof[38] += k <= 2.f ? 1.f : 0.f; s.prof[39] += k <= 4.f ? 1.f : 0.f; s.prof[40] += k <= 8.f ? 1.f : 0.f; }
-    if ((flags & 2) && iter > 0 && !flags_changed && LANE == 0) s.prof[41] += 1.f;
+    if ((flags & RG_FLAG_PROFILE) && iter > 0 && flags_changed && LANE == 0) { const float k = s.prof[47]; s.prof[36] += 1.f; s.prof[37] += k; s.prof[38] += k <= 2.f ? 1.f : 0.f; s.prof[39] += k <= 4.f ? 1.f : 0.f; s.prof[40] += k <= 8.f ? 1.f : 0.f; }
+    if ((flags & RG_FLAG_PROFILE) && iter > 0 && !flags_changed && LANE == 0) s.prof[41] += 1.f;
 #endif
     PROFF(25);
     rg_JT_force(m, s, RR, s.jtf);
@@ -2720,8 +2720,8 @@ template <bool SENSORS> __device__ __forceinline__ int rg_solve(RgM m, RgLds& s,
 #endif
     if (!refactor && invfac && nset > 0) { corrected = rg_cholinv_woodbury(m, s, RR, s.search); if (!corrected) refactor = true; }
 #ifdef RG_FINE_PROF
-    if ((flags & 2) && LANE == 0 && !(!have_factor) && invfac && nset > 0 && nset <= RG_WOODBURY) { s.prof[45] += 1.f; s.prof[46] += (float)(rg_clock() - twb0); if (!corrected) s.prof[49] += 1.f; }
-    if ((flags & 2) && LANE == 0 && refactor) s.prof[48] += 1.f;
+    if ((flags & RG_FLAG_PROFILE) && LANE == 0 && !(!have_factor) && invfac && nset > 0 && nset <= RG_WOODBURY) { s.prof[45] += 1.f; s.prof[46] += (float)(rg_clock() - twb0); if (!corrected) s.prof[49] += 1.f; }
+    if ((flags & RG_FLAG_PROFILE) && LANE == 0 && refactor) s.prof[48] += 1.f;
 #endif
 #ifdef RG_WOODBURY_CHECK
     if (corrected) { dbg_xw = LANE < nvc ? s.search[LANE] : 0.f; SYNC(); if (LANE < nvc) s.search[LANE] = dbg_g; SYNC(); corrected = false; refactor = true; dbg_chk = true; }
@@ -3003,8 +3003,8 @@ RG_STAGE void st_velocity(RgCtx c) { RgM m = RG_M(c); RgLRef L = RG_L(c); rg_vel
 RG_STAGE_BIG void st_collision(RgCtx c) {
   RgM m = RG_M(c); RgLRef L = RG_L(c); RgLds& s = RG_S();
   int e = rg_env(L), flags = L.flags;
-  rg_collision(c, m, s, rg_prm(m, L), (flags & 2) ? s.prof : (float*)0, L.bt.sepdir ? (rgf4*)L.bt.sepdir + (size_t)e * m.npair : (rgf4*)0,
-               (L.bt.pairlb && !(flags & 4)) ? L.bt.pairlb + (size_t)e * m.npair : (float*)0, !(flags & 8));
+  rg_collision(c, m, s, rg_prm(m, L), (flags & RG_FLAG_PROFILE) ? s.prof : (float*)0, L.bt.sepdir ? (rgf4*)L.bt.sepdir + (size_t)e * m.npair : (rgf4*)0,
+               (L.bt.pairlb && !(flags & RG_FLAG_NO_PAIR_CACHE)) ? L.bt.pairlb + (size_t)e * m.npair : (float*)0, !(flags & RG_FLAG_SCAN_HULL_VERTICES));
 }
 RG_STAGE void st_make_constraint(RgCtx c) { RgM m = RG_M(c); rg_make_constraint(m, RG_S(), rg_prm(m, RG_L(c))); }
 RG_STAGE void st_pid(RgCtx c, float* pid) { RgM m = RG_M(c); rg_pid(m, RG_S(), rg_prm(m, RG_L(c)), pid); }
@@ -3058,7 +3058,7 @@ __global__ void __launch_bounds__(RG_WAVE, RG_WAVES_PER_SIMD) rg_step_kernel(con
   if (L.bt.active && !L.bt.active[e]) return;
   // flags bit 8: `active` is the redo array of a rollout launch, whose entries say where to resume: entry - 1 = the first substep
   // that is still to do (the substep-granular rollout kernel hands an env over in the middle of its env.step)
-  const int sub0 = ((flags & 256) && L.bt.active) ? L.bt.active[e] - 1 : 0;
+  const int sub0 = ((flags & RG_FLAG_RESUME) && L.bt.active) ? L.bt.active[e] - 1 : 0;
   long long tk0 = rg_clock();
   // ---- load the env's state row
   PFOR(i, m.nq) s.qpos[i] = L.bt.qpos[(size_t)e * m.nq + i];
@@ -3069,7 +3069,7 @@ __global__ void __launch_bounds__(RG_WAVE, RG_WAVES_PER_SIMD) rg_step_kernel(con
   { float nz = 0; PFOR(i, 6 * m.nbody) nz += P[RG_PRM_XFRC + i] != 0.f ? 1.f : 0.f; nz = wave_sum(nz); if (LANE == 0) s.has_xfrc = nz > 0; }
   const unsigned status0 = L.bt.status[e];
   if (LANE == 0) s.status = status0;
-  if ((L.flags & 2) && LANE < RG_NPROF) s.prof[LANE] = 0;
+  if ((L.flags & RG_FLAG_PROFILE) && LANE < RG_NPROF) s.prof[LANE] = 0;
   st_build_row_desc(c);
   // ---- action -> ctrl (robot_interface.py:247-278 with the hand's position->control matrix)
   if (L.bt.preticks && sub0 == 0) {
@@ -3108,18 +3108,18 @@ __global__ void __launch_bounds__(RG_WAVE, RG_WAVES_PER_SIMD) rg_step_kernel(con
     float bd = 0; PFOR(i, m.nq) bd += (fabsf(s.qpos[i]) < 1e10f) ? 0.f : 1.f; PFOR(i, m.nv) bd += (fabsf(s.qvel[i]) < 1e10f) ? 0.f : 1.f;
     if (wave_sum(bd) > 0) { bad = true; break; }
     long long t0 = rg_clock(), t1;
-#define PROF(k) do { if (flags & 2) { t1 = rg_clock(); if (LANE == 0) s.prof[k] += (float)(t1 - t0); t0 = t1; } } while (0)
+#define PROF(k) do { if (flags & RG_FLAG_PROFILE) { t1 = rg_clock(); if (LANE == 0) s.prof[k] += (float)(t1 - t0); t0 = t1; } } while (0)
 #ifdef RG_EMUL_POISON
     { unsigned int* u = (unsigned int*)s.H; int nw = (int)((sizeof(RgLds) - ((char*)s.H - (char*)&s)) / 4); for (int w = LANE; w < nw; w += RG_WAVE) u[w] = 0x7fc00000u; SYNC(); }
 #endif
     st_kinematics(c); PROF(0);
     st_com_pos(c); PROF(1);
     st_tendon(c); PROF(2);
-    if (sub == 0 && (flags & 1) && L.bt.dbg) st_dump(c, 0, 0, 0);
+    if (sub == 0 && (flags & RG_FLAG_STAGE_DUMP) && L.bt.dbg) st_dump(c, 0, 0, 0);
     st_crb(c); PROF(3);
     st_velocity(c); PROF(7);
     st_collision(c); PROF(6);
-    if ((flags & 2) && LANE == 0 && (float)s.ncon > s.prof[23]) s.prof[23] = (float)s.ncon;
+    if ((flags & RG_FLAG_PROFILE) && LANE == 0 && (float)s.ncon > s.prof[23]) s.prof[23] = (float)s.ncon;
     st_make_constraint(c); PROF(8);
     if (L.bt.xdata && sub == nsubsteps - 1) {   // data.ncon / data.contact[i].{geom1, geom2, dist} of the last mj_step
       float* xd = L.bt.xdata + (size_t)e * RG_XDATA;
@@ -3127,7 +3127,7 @@ __global__ void __launch_bounds__(RG_WAVE, RG_WAVES_PER_SIMD) rg_step_kernel(con
       if (LANE == 0) xd[RG_XD_NCON] = (float)s.ncon;
       PFOR(ci, nc) { int gg = m.pair_gg[s.c_pair[ci]]; float* o = xd + RG_XD_CONTACT + 3 * ci; o[0] = (float)(gg & 255); o[1] = (float)(gg >> 8); o[2] = s.c_dist[ci]; }
     }
-    if (L.bt.redo && ((s.status & ~status0 & (RG_STATUS_CON_FULL | RG_STATUS_CAND_FULL)) || ((RG_L(c).flags & 512) && s.ncon > 5))) {   // (flags bit 9: test hook, "more than 5 contacts do not fit")
+    if (L.bt.redo && ((s.status & ~status0 & (RG_STATUS_CON_FULL | RG_STATUS_CAND_FULL)) || ((RG_L(c).flags & RG_FLAG_CAPACITY_TEST_HOOK) && s.ncon > 5))) {   // (flags bit 9: test hook, "more than 5 contacts do not fit")
       // more contacts / candidates than this configuration holds: leave the env exactly as it was (state rows are
       // written at the end; the distance-bound cache was advanced by the substeps done so far, so it is voided) and
       // hand it to the large configuration
@@ -3137,7 +3137,7 @@ __global__ void __launch_bounds__(RG_WAVE, RG_WAVES_PER_SIMD) rg_step_kernel(con
     }
     st_pid(c, pidr);
     st_smooth(c); PROF(9);
-    if (sub == 0 && (flags & 1) && L.bt.dbg) st_dump(c, 1, 0, 0);
+    if (sub == 0 && (flags & RG_FLAG_STAGE_DUMP) && L.bt.dbg) st_dump(c, 1, 0, 0);
     // ---- the position-stage scratch is dead from here on; the solver scratch takes its place
 #ifdef RG_EMUL_POISON
     { unsigned int* u = (unsigned int*)s.H; int nw = (int)((sizeof(RgLds) - ((char*)s.H - (char*)&s)) / 4); for (int w = LANE; w < nw; w += RG_WAVE) u[w] = 0x7fc00000u; SYNC(); }
@@ -3145,7 +3145,7 @@ __global__ void __launch_bounds__(RG_WAVE, RG_WAVES_PER_SIMD) rg_step_kernel(con
     st_factor_smooth(c); PROF(4);
     int packed = st_solve(c, warmr), iters = packed & 255, nefc = packed >> 8; t0 = rg_clock();
     st_ncon += s.ncon; st_nefc += nefc; st_iter += iters;
-    if (sub == 0 && (flags & 1) && L.bt.dbg) st_dump(c, 2, nefc, iters);
+    if (sub == 0 && (flags & RG_FLAG_STAGE_DUMP) && L.bt.dbg) st_dump(c, 2, nefc, iters);
     bd = 0; PFOR(i, m.nv) bd += (fabsf(s.qacc[i]) < 1e10f) ? 0.f : 1.f;
     if (wave_sum(bd) > 0) { bad = true; break; }
     warmr = st_euler(c, warmr); PROF(11);
@@ -3165,7 +3165,7 @@ __global__ void __launch_bounds__(RG_WAVE, RG_WAVES_PER_SIMD) rg_step_kernel(con
     }
     st_com_pos(c); st_tendon(c);
 #if RG_SENSORS
-    const bool sensors = (flags & 32) && L.bt.xdata && m.nsensor > 0 && nticks > 0;
+    const bool sensors = (flags & RG_FLAG_SENSORS) && L.bt.xdata && m.nsensor > 0 && nticks > 0;
 #else
     const bool sensors = false;
 #endif
@@ -3175,7 +3175,7 @@ __global__ void __launch_bounds__(RG_WAVE, RG_WAVES_PER_SIMD) rg_step_kernel(con
       // data.sensordata: the LAST state-less forward of the reference in full — contacts and their forces at the final state
       // (mj_sensorAcc reads efc_force); its actuation stage is the last controller tick
       st_crb(c); st_velocity(c); st_collision(c); st_make_constraint(c);
-      if (L.bt.redo && ((s.status & ~status0 & (RG_STATUS_CON_FULL | RG_STATUS_CAND_FULL)) || ((RG_L(c).flags & 512) && s.ncon > 5))) {   // (flags bit 9: test hook, "more than 5 contacts do not fit")
+      if (L.bt.redo && ((s.status & ~status0 & (RG_STATUS_CON_FULL | RG_STATUS_CAND_FULL)) || ((RG_L(c).flags & RG_FLAG_CAPACITY_TEST_HOOK) && s.ncon > 5))) {   // (flags bit 9: test hook, "more than 5 contacts do not fit")
         if (L.bt.pairlb) { float* lb = L.bt.pairlb + (size_t)e * m.npair; PFOR(i, m.npair) lb[i] = 0.f; }
         if (LANE == 0) L.bt.redo[e] = 1;
         return;
@@ -3203,7 +3203,7 @@ __global__ void __launch_bounds__(RG_WAVE, RG_WAVES_PER_SIMD) rg_step_kernel(con
     if (L.bt.cost) L.bt.cost[e] = (float)(rg_clock() - tk0);
     if (L.bt.stats) { float* st = L.bt.stats + 4 * (size_t)e; st[0] += st_ncon; st[1] += st_nefc; st[2] += st_iter; st[3] += nsubsteps - sub0; }
   }
-  if ((flags & 2) && L.bt.dbg && LANE < RG_NPROF) L.bt.dbg[(size_t)e * RG_DBG_SIZE + RG_DBG_CON + LANE] = s.prof[LANE];  // stage cycle counters (overlays the contact dump)
+  if ((flags & RG_FLAG_PROFILE) && L.bt.dbg && LANE < RG_NPROF) L.bt.dbg[(size_t)e * RG_DBG_SIZE + RG_DBG_CON + LANE] = s.prof[LANE];  // stage cycle counters (overlays the contact dump)
   // ---- observation row (robot_env.py:714-743; keys/order: DESIGN.md "observation layout")
   if (L.bt.obs) {
     int od = 3 + 4 + m.nq + m.nv + L.env.n_hand_jnt + 15;
@@ -3273,7 +3273,7 @@ __global__ void __launch_bounds__(RG_WAVE, RG_WAVES_PER_SIMD) rg_step_items_kern
   st_build_row_desc(c);   // (static index tables in the persistent part of the LDS image: once per workgroup, not per item)
   int xfrc_default = -1;  // batches without per-env parameter rows: "any external wrench?" is a property of the model's default row
   if (!L.bt.envprm) { const float* P0 = m.prm_default; float nz = 0; PFOR(i, 6 * m.nbody) nz += P0[RG_PRM_XFRC + i] != 0.f ? 1.f : 0.f; xfrc_default = wave_sum(nz) > 0 ? 1 : 0; }
-  const bool desert = (L.flags & 1024) && xq == 0;   // TEST HOOK (flags bit 10): queue 0 is left unserved, as if its XCD had received no workgroup
+  const bool desert = (L.flags & RG_FLAG_DESERT_QUEUE0) && xq == 0;   // TEST HOOK (flags bit 10): queue 0 is left unserved, as if its XCD had received no workgroup
   for (;;) {
     SYNC();   // (the previous item's LDS image is dead only when every lane is here)
     if (desert) break;
@@ -3351,7 +3351,7 @@ __global__ void __launch_bounds__(RG_WAVE, RG_WAVES_PER_SIMD) rg_step_items_kern
         if (LANE == 0) xd[RG_XD_NCON] = (float)s.ncon;
         PFOR(ci, nc) { int gg = m.pair_gg[s.c_pair[ci]]; float* o = xd + RG_XD_CONTACT + 3 * ci; o[0] = (float)(gg & 255); o[1] = (float)(gg >> 8); o[2] = s.c_dist[ci]; }
       }
-      if (L.bt.redo && ((s.status & ~status0 & (RG_STATUS_CON_FULL | RG_STATUS_CAND_FULL)) || ((RG_L(c).flags & 512) && s.ncon > 5))) {   // (flags bit 9: test hook, "more than 5 contacts do not fit")
+      if (L.bt.redo && ((s.status & ~status0 & (RG_STATUS_CON_FULL | RG_STATUS_CAND_FULL)) || ((RG_L(c).flags & RG_FLAG_CAPACITY_TEST_HOOK) && s.ncon > 5))) {   // (flags bit 9: test hook, "more than 5 contacts do not fit")
         // more contacts / candidates than this configuration holds: the env's rows stay as this item found them (in substep 0:
         // as the launch found them, owed ticks and action included) and the large configuration takes over at this substep
         if (L.bt.pairlb) { float* lb = L.bt.pairlb + (size_t)e * m.npair; PFOR(i, m.npair) lb[i] = 0.f; }

@@ -55,7 +55,7 @@ from robogym_amd.mujoco.large_simulation import LargeModelSimulation
 TABLETOP_EXPERIMENT_INITIAL_POS = np.deg2rad(np.array([135.0, -90, 135, -100, -240, 135]))   # robot/ur16e/arm_interface.py:27
 SPEED_ROLL, SPEED_PITCH = float(np.deg2rad(200)), float(np.deg2rad(600))                      # free_dof_tcp_arm.py:13-17
 JOINT_DRIFT_THRESHOLD = float(np.deg2rad(1))
-FLAG_FULL_FORWARD = 32
+FLAG_FULL_FORWARD = _native.RG_FLAG_SENSORS      # on the large-model stepper: the last state-less forward in full, sensors read from it
 #: the goal generators of the rearrange block tasks (ra_post_args.goal_kind): ObjectStateGoal (goals/object_state.py), PickAndPlaceGoal (goals/pickandplace.py),
 #: ObjectStackGoal (goals/object_stack_goal.py), ObjectReachGoal / DeterministicReachGoal (goals/object_reach_goal.py)
 #: (train: TrainStateGoal, goals/train_state.py; dominos: DominoStateGoal, goals/dominos.py; attached: AttachedBlockStateGoal, goals/attached_block_state.py; fixed:
