@@ -833,8 +833,9 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
   }
 }
 
-// The per-env parameter rows after a recipe launch, on the rows of its masks only (ra_param_rows_args, include/rgstep_sync_reset.h): what
-// BatchedBlockRearrangeEnv._advance_recipes_device does with whole-batch tensor ops.  One wave per env; an env outside `active`, or with none of its three mask
+// The per-env parameter rows after a recipe launch, on the rows of its masks only (ra_param_rows_args, include/rgstep_sync_reset.h): the device route's only
+// implementation, pipelined and synchronous alike.  Its twin on the host route: BatchedBlockRearrangeEnv's `_param_defaults` restore (_begin_episode_state),
+// _set_object_damping and _apply_parking, in that order (tests/test_rearrange_sync_reset.py compares the two).  One wave per env; an env outside `active`, or with none of its three mask
 // bytes set, is left after three byte loads.  `blk`: word offset of the parameter block in the scratch row, `words` its length; `damp` / `xfrc` / `mass` / `grav`: the
 // fields' word offsets in the row (RbModelDev.prm_off).  Plain vector stores; every store of a phase goes to a word no other lane writes in that phase.
 __global__ void __launch_bounds__(64) ra_param_rows_kernel(RbBatchDev bt, int scratch_words, int blk, int words, int damp, int xfrc, int mass, int grav, RaParamRowsArgs a) {

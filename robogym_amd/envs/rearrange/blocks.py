@@ -772,8 +772,7 @@ class BatchedBlockRearrangeEnv:
         main, solver = self.model, self.solver_model
         A, jn = main.arrays, main.names["joint"]
         t = self.tcp = _native.RbTcpArgs()
-        if self.pipelined:
-            t.hold, t.scripted = self.hold.data_ptr(), self.scripted.data_ptr()
+        t.hold, t.scripted = self.hold.data_ptr(), self.scripted.data_ptr()      # (the recipe's rows; zero unless a pipelined or a device reset is under way)
         self.solver_arm_q, self.solver_grip_q, self.solver_grip_act = [], -1, -1
         if self.joint_control:
             # JointControlledArm drives ctrl[:6] from the six arm joints (joint_controlled_arm.py:186-190), MujocoRobotiqGripper its own actuator; relative actions:
@@ -859,12 +858,19 @@ class BatchedBlockRearrangeEnv:
         if self.rel_dist is not None:
             a.rel_dist, a.rel_threshold = _ptr(self.rel_dist), float(st.get("rel_dist", 0.0))
         if self.mask_obs:
-            a.mask_obs, a.soft_mask, a.mask_margin, a.area_height, a.goal_in_area = 1, int(self.soft_mask), self.mask_margin, PLACEMENT_AREA_HEIGHT, _ptr(self.goal_in_area)
-            (off_x, off_y, _), (width, height, _) = self.placement_area(N)
-            a.area_offset[0], a.area_offset[1], a.area_size[0], a.area_size[1], a.used_table_portion = float(off_x), float(off_y), float(width), float(height), float(self.used_table_portion)
-            for k in range(3):
-                a.table_pos[k], a.table_size[k] = float(self.table_pos[k]), float(self.table_size[k])
+            a.mask_obs = 1
+            self._fill_area_args(a)
             a.seed, a.step = (int(starting_seed) * 2654435761 + 40503) & 0xFFFFFFFF, 0
+
+    def _fill_area_args(self, a):
+        """The fields ra_post_args (mask_obs) and ra_recipe_args share, into either: the placement area of an env that uses all N objects, the table,
+        `used_table_portion` (read with per-env object counts only: ra_area, csrc/ra_env_kernel.h) and, with the masks, the goal's mask row and its rule"""
+        (off_x, off_y, _), (width, height, _) = self.placement_area(self.N)
+        a.area_offset[0], a.area_offset[1], a.area_size[0], a.area_size[1], a.used_table_portion = float(off_x), float(off_y), float(width), float(height), float(self.used_table_portion)
+        for k in range(3):
+            a.table_pos[k], a.table_size[k] = float(self.table_pos[k]), float(self.table_size[k])
+        if self.mask_obs:
+            a.goal_in_area, a.soft_mask, a.mask_margin, a.area_height = _ptr(self.goal_in_area), int(self.soft_mask), self.mask_margin, PLACEMENT_AREA_HEIGHT
 
     def _fill_icp_args(self):
         """rot_dist_type icp: the clouds (constant, per object), the angles ra_env_icp leaves for the env kernel, and `self.icp`, its arguments"""
@@ -903,10 +909,7 @@ class BatchedBlockRearrangeEnv:
         for k in range(6):
             r.arm_qposadr[k], r.arm_start[k] = self.arm_q[k], float(TABLETOP_EXPERIMENT_INITIAL_POS[k])
             r.solver_arm_qposadr[k] = self.solver_arm_q[k] if self.solver_arm_q else 0
-        (off_x, off_y, _), (width, height, _) = self.placement_area(N)
-        r.area_offset[0], r.area_offset[1], r.area_size[0], r.area_size[1] = float(off_x), float(off_y), float(width), float(height)
-        for k in range(3):
-            r.table_pos[k], r.table_size[k] = float(self.table_pos[k]), float(self.table_size[k])
+        self._fill_area_args(r)
         r.stabilize_steps, r.n_random_initial_steps, r.settle_steps = int(self.stabilize_steps), int(self.n_random_initial_steps), int(self.settle_steps)
         r.seed, r.step = (int(starting_seed) * 2654435761 + 40503) & 0xFFFFFFFF, 0
         r.goal_kind, r.height_range[0], r.height_range[1], r.object_size = self.goal_kind, self.height_range[0], self.height_range[1], self.object_size
@@ -922,13 +925,11 @@ class BatchedBlockRearrangeEnv:
         if self.goal_kind_name == "fixed":
             for i in range(N):
                 r.fixed_xy[i][0], r.fixed_xy[i][1], r.fixed_yaw[i] = float(self.relative_placements[i, 0]), float(self.relative_placements[i, 1]), float(self.init_yaw[i])
-        if self.max_num_objects is not None:      # (area_offset / area_size above: the area of an env that uses all N objects)
-            r.num_active, r.num_objects_next, r.used_table_portion = _ptr(self.num_active), _ptr(self.num_objects_next), float(self.used_table_portion)
+        if self.max_num_objects is not None:
+            r.num_active, r.num_objects_next = _ptr(self.num_active), _ptr(self.num_objects_next)
             for i in range(N):
                 for k in range(7):
                     r.park_pose[i][k] = float(self.park_pose[i, k])
-        if self.mask_obs:
-            r.goal_in_area, r.soft_mask, r.mask_margin, r.area_height = _ptr(self.goal_in_area), int(self.soft_mask), self.mask_margin, PLACEMENT_AREA_HEIGHT
         if self.num_scenes:
             r.num_scenes, r.scene_next, r.scene = self.num_scenes, _ptr(self.scene_next), _ptr(self.scene)
             if self.scene_init is not None:
@@ -938,15 +939,13 @@ class BatchedBlockRearrangeEnv:
                 r.goal_cursor, r.advance_goals = _ptr(self.goal_cursor), int(self.advance_goals)
 
     def _fill_sync_reset_args(self):
-        """What the synchronous episode API on the device adds to the recipe's arguments (`reset(mask, on_device=True)`, `reset_goals(on_device=True)`): the `active` row
-        of its launches, `self.param_rows` (ra_param_rows_args, include/rgstep_sync_reset.h: the per-env parameter rows on the recipe's masks) and `self.tcp_sync`, the
-        TCP hook's arguments with the recipe's `hold` / `scripted` rows, which a pipelined env's hook has anyway."""
-        dev, B = self.device, self.B
-        self.active_row = torch.zeros(B, dtype=torch.uint8, device=dev)
+        """What the device route has beside the recipe's arguments: the `active` row of the synchronous launches (`reset(mask, on_device=True)`) and
+        `self.param_rows` (ra_param_rows_args, include/rgstep_sync_reset.h: the per-env parameter rows on the recipe's masks; its `active`: `_param_rows_launch`)."""
+        self.active_row = torch.zeros(self.B, dtype=torch.uint8, device=self.device)
         self.param_rows = None
         if self.per_env_parameters:
             a = self.param_rows = _native.RaParamRowsArgs()
-            a.ended, a.stabilised, a.episode_started, a.active = _ptr(self.ended), _ptr(self.stabilised), _ptr(self.episode_started), _ptr(self.active_row)
+            a.ended, a.stabilised, a.episode_started = _ptr(self.ended), _ptr(self.stabilised), _ptr(self.episode_started)
             self._param_block_default = self._param_block_default.contiguous()
             a.block_default, a.num_objects = _ptr(self._param_block_default), self.N
             for i in range(self.N):
@@ -956,14 +955,6 @@ class BatchedBlockRearrangeEnv:
                 a.num_active = _ptr(self.num_active)
         for rz in self.randomizers:      # (their index tables: uploaded here, not inside a reset that must not wait for the device)
             rz.prepare(self.sim)
-        self.tcp_sync = None
-        if not self.joint_control:      # (tcp_solver_mode mocap refuses device_reset above: a solver world exists)
-            t = self.tcp_sync = _native.RbTcpArgs()
-            ctypes.memmove(ctypes.byref(t), ctypes.byref(self.tcp_wrapped if self.wrapped else self.tcp), ctypes.sizeof(t))
-            t.hold, t.scripted = self.hold.data_ptr(), self.scripted.data_ptr()
-            self._zero_index = torch.zeros(B, 6, dtype=torch.int32, device=dev)      # (wrapped: the hook wants bin indices; every env of these launches takes its scripted action)
-            if self.wrapped:
-                t.action_index = self._zero_index.data_ptr()
 
     # ------------------------------------------------------------------ launches
     def _stream(self):
@@ -980,13 +971,14 @@ class BatchedBlockRearrangeEnv:
         if frozen is not None:
             self.post.frozen = had
 
-    def _joint_action(self, actions, wrapped):
+    def _joint_action(self, actions, wrapped, recipe_rows=None):
         """Joint control: the [B, 7] action that reaches `RobotEnv._set_action`.  With the wrapper stack: bin index -> value (DiscretizeActionWrapper.action,
         wrappers/util.py:66-70) -> exponential moving average with bias correction (SmoothActionWrapper.step / IncrementalExpAvg, util.py:142-160, 213-218) -- a few
-        elementwise device ops here (in TCP mode the solver world's launch does them).  Pipelined resets: envs inside their recipe take its scripted action."""
+        elementwise device ops here (in TCP mode the solver world's launch does them).  `recipe_rows` (`_physics`): envs inside their recipe take its scripted action."""
+        recipe_rows = self.pipelined if recipe_rows is None else recipe_rows
         if wrapped:
             x = self.bins[torch.arange(self.action_dim, device=self.device)[None, :], actions.long()]
-            live = (self.hold == 0) if self.pipelined else torch.ones(self.B, dtype=torch.bool, device=self.device)
+            live = (self.hold == 0) if recipe_rows else torch.ones(self.B, dtype=torch.bool, device=self.device)
             al = self.ema_alpha
             v = torch.where(live[:, None], self.ema_value * al + (1.0 - al) * x, self.ema_value)
             self.ema_value.copy_(v)
@@ -994,19 +986,22 @@ class BatchedBlockRearrangeEnv:
             out = v / (1.0 - torch.pow(torch.full_like(v[:, :1], al), self.ema_t[:, None].to(torch.float32))).clamp_min(1.0e-30)
             self.action_ema.copy_(torch.where(live[:, None], out, self.action_ema))
             actions = self.action_ema
-        if self.pipelined:
+        if recipe_rows:
             actions = torch.where(self.hold[:, None] != 0, self.scripted, actions)
         return actions.contiguous()
 
-    def _physics(self, actions, active=None, wrapped=False, solver_active=None, phase=None):
+    def _physics(self, actions, active=None, wrapped=False, solver_active=None, phase=None, recipe_rows=None):
         """`phase`: None = both physics launches; "solver" / "main" = one of them (envs/rearrange/ycb.py GroupedYcbRearrangeEnv records the same phase of every group and
-        issues it as ONE launch, rb_multi_begin / rb_multi_launch)."""
+        issues it as ONE launch, rb_multi_begin / rb_multi_launch).  `recipe_rows`: the launches go by the rows the reset recipe maintains -- `nticks`, joint control's
+        `hold_ctrl` and scripted actions (the TCP hook reads `hold` / `scripted` anyway: zero rows outside a recipe) -- as every step of a pipelined env (the
+        default, None: `self.pipelined`; bench.py wraps this method with the step's five arguments) and every iteration of `_reset_device` (True) does."""
+        recipe_rows = self.pipelined if recipe_rows is None else recipe_rows
         if phase == "solver" and (self.joint_control or self.ideal_arm):
             return                        # one-world robots have no solver phase
+        nticks = self.nticks if recipe_rows else None
         if self.joint_control:     # CompositeRobot.set_position_control at the head of the main world's launch; no solver world
-            self._keep_act = self._joint_action(actions, wrapped)
-            self.sim.env_step(action=self._keep_act, nforward_ticks=2, flags=FLAG_FULL_FORWARD, active=active, nticks=self.nticks if self.pipelined else None,
-                              hold=self.hold_ctrl if self.pipelined else None)
+            self._keep_act = self._joint_action(actions, wrapped, recipe_rows)
+            self.sim.env_step(action=self._keep_act, nforward_ticks=2, flags=FLAG_FULL_FORWARD, active=active, nticks=nticks, hold=self.hold_ctrl if recipe_rows else None)
             return
         if self.ideal_arm:         # one launch: the hook on this world, its mj_steps, the two state-less forwards (the last in full)
             args = self.tcp_wrapped if wrapped else self.tcp
@@ -1029,7 +1024,7 @@ class BatchedBlockRearrangeEnv:
             return
         # live envs: sim.step's forward + _observe_sync's forward = two controller ticks, the last forward in full; envs inside their reset recipe (pipelined
         # resets): `mujoco_simulation.step()` only = one tick, `self.nticks` (the recipe's last step gets the second tick: the _observe_sync that ends a reset)
-        self.sim.env_step(nforward_ticks=2, flags=FLAG_FULL_FORWARD, active=active, nticks=self.nticks if self.pipelined else None)
+        self.sim.env_step(nforward_ticks=2, flags=FLAG_FULL_FORWARD, active=active, nticks=nticks)
 
     def _recipe_physics(self, actions, active):
         """One step of the reset recipe's robot moves, `self._set_action(action); self.mujoco_simulation.step()` (common/base.py:484-496): the TCP solver world's
@@ -1201,15 +1196,20 @@ class BatchedBlockRearrangeEnv:
     def _next_goal(self, rows, yaw):
         """`_update_simulation_for_next_goal` (goals/object_state.py:333-358) for the envs `rows`, whose goals have the yaws `yaw` [len(rows), N]: with
         `randomize_goal_rot` new yaws first (per env, over its active objects, in the reference's draw order; an unused slot keeps yaw 0), then the positions for boxes
-        turned by them; the kinds of OWN_YAW_KINDS set yaws of their own.  -> (positions, yaws): `_write_goal`'s arguments."""
+        turned by them; the kinds of OWN_YAW_KINDS set yaws of their own.  -> `_write_goal`'s arguments: positions, and from the yaws the Euler angles (mat2euler of a
+        z-rotation, normalised as get_target_rot + normalize_angles give it) and euler2quat of them, the quaternion of the goal rows and of qpos_goal alike."""
         counts = self._counts(rows)
         if self.randomize_goal_rot and len(rows):
             yaw = np.array(yaw, dtype=np.float64)
             for r, c in enumerate(counts):
                 yaw[r, :c] = randomize_yaw_along_z(self._rng, yaw[r, :c])
         if self.goal_kind_name in OWN_YAW_KINDS:
-            return self._own_yaw_goals(len(rows))
-        return self._by_count(rows, yaw, counts, self._goal_positions), yaw
+            pos, yaw = self._own_yaw_goals(len(rows))
+        else:
+            pos = self._by_count(rows, yaw, counts, self._goal_positions)
+        eul =np.zeros(pos.shape); eul[..., 2] = np.mod(yaw + np.pi, 2 * np.pi) - np.pi
+        quat = euler2quat(eul)
+        return pos, eul, quat, quat
 
     def _own_yaw_goals(self, R):
         """The goals of `R` envs for the kinds that turn the goals themselves, AFTER the randomisation (host numpy; ra_recipe_kernel does the same on the device):
@@ -1311,21 +1311,22 @@ class BatchedBlockRearrangeEnv:
             return
         self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=self._mask_of(rows, torch.int32))
 
-    def _write_goal(self, rows, goal_pos, yaw):
+    def _write_goal(self, rows, goal_pos, eul, quat, qpos_quat):
+        """The goal of the envs `rows`, sampled or recorded: positions [R, N, 3], Euler angles -> `goal_rot`, `quat` -> the goal rows, `qpos_quat` -> `qpos_goal`
+        (a recorded goal keeps its own quaternion in the goal row and carries euler2quat of its angles in qpos_goal); the tracker's `prev_valid`, the goal's mask."""
         dev = self.device
         idx = torch.as_tensor(rows, device=dev, dtype=torch.long)
-        eul = np.zeros(goal_pos.shape); eul[..., 2] = np.mod(yaw + np.pi, 2 * np.pi) - np.pi        # mat2euler of a z-rotation, normalised as get_target_rot + normalize_angles give it
-        quat = euler2quat(eul)
-        g = np.concatenate([goal_pos, quat], -1).astype(np.float32)
+        eul = np.array(eul, dtype=np.float32)
+        g, q = (np.concatenate([goal_pos, x], -1).astype(np.float32) for x in (quat, qpos_quat))
         unused = np.arange(self.N)[None, :] >= self._counts(rows)[:, None]      # an unused slot: its parked pose in qpos_goal, a zero goal row (identity orientation)
-        g[unused] = np.broadcast_to(self._parked().astype(np.float32)[None], g.shape)[unused]
+        q[unused] = np.broadcast_to(self._parked().astype(np.float32)[None], q.shape)[unused]
+        g[unused] = np.array([0, 0, 0, 1, 0, 0, 0], dtype=np.float32)
         eul[unused] = 0.0
-        self.goal_rot[idx] = torch.tensor(eul.astype(np.float32), device=dev)
+        self.goal_rot[idx] = torch.tensor(eul, device=dev)
         qg = self.sim.qpos[idx].clone()                                   # qpos_goal: the current qpos with the objects at their goals (object_state.py:381-389)
         for i, qa in enumerate(self.obj_q):
-            qg[:, qa:qa + 7] = torch.tensor(g[:, i], device=dev)
+            qg[:, qa:qa + 7] = torch.tensor(q[:, i], device=dev)
         self.qpos_goal[idx] = qg
-        g[unused] = np.array([0, 0, 0, 1, 0, 0, 0], dtype=np.float32)
         self.goal[idx] = torch.tensor(g, device=dev)
         self.prev_valid[idx] = 0
         self._write_goal_mask(rows, idx, g[..., :3], unused)
@@ -1362,15 +1363,7 @@ class BatchedBlockRearrangeEnv:
             cur = np.where((cur < 0) | (cur >= ng), 0, cur)
         self.goal_cursor[idx] = torch.as_tensor((((cur + 1) % ng) if self.advance_goals else 0 * cur).astype(np.int32), device=dev)
         g, rot = self._scene_goal[sc, cur], self._scene_goal_rot[sc, cur]      # [R, N, 7]: position | quaternion, Euler angles | euler2quat of them
-        self.goal[idx] = torch.tensor(g, device=dev)
-        self.goal_rot[idx] = torch.tensor(rot[..., :3], device=dev)
-        qg = self.sim.qpos[idx].clone()                                   # qpos_goal: the current qpos with the objects at their goals (object_state.py:381-389)
-        for i, qa in enumerate(self.obj_q):
-            qg[:, qa:qa + 3] = torch.tensor(g[:, i, :3], device=dev)
-            qg[:, qa + 3:qa + 7] = torch.tensor(rot[:, i, 3:], device=dev)
-        self.qpos_goal[idx] = qg
-        self.prev_valid[idx] = 0
-        self._write_goal_mask(rows, idx, g[..., :3].astype(np.float64), np.zeros(g.shape[:2], dtype=bool))
+        self._write_goal(rows, g[..., :3], rot[..., :3], g[..., 3:], rot[..., 3:])
 
     def _begin_episode_state(self, rows, idx):
         """What RearrangeEnv._reset writes before anything is simulated (common/base.py:897-932): both worlds as freshly made, the arm's start pose, object
@@ -1471,9 +1464,29 @@ class BatchedBlockRearrangeEnv:
         r.step = (int(r.step) + 1) & 0xFFFFFFFF
         _native.check(self._L, self._L.ra_env_recipe_step(self.sim._bh, None if self.solver_sim is None else self.solver_sim._bh, ctypes.byref(r), self._stream()), "ra_env_recipe_step")
 
-    def _param_rows_launch(self, stages):
-        self.param_rows.stages = stages
+    def _param_rows_launch(self, stages, active=None):
+        """The per-env parameter rows of the device route on the masks the last recipe launch left (ra_param_rows_kernel, csrc/ra_env_kernel.h; the host route's twin:
+        the `_param_defaults` restore, `_set_object_damping`, `_apply_parking`).  `active`: the [B] uint8 row of a synchronous reset; None = every env."""
+        self.param_rows.stages, self.param_rows.active = stages, None if active is None else _ptr(active)
         _native.check(self._L, self._L.ra_env_param_rows(self.sim._bh, ctypes.byref(self.param_rows), self._stream()), "ra_env_param_rows")
+
+    def _finish_recipe_launch(self, active=None, started=True):
+        """What follows the last recipe launch of a step, of a synchronous reset (`active`: its [B] uint8 row, the envs outside it are left alone) or of a regoal-only
+        launch (`started` False: that mode leaves the masks as they were, so nothing may go by them and no randomizer draws): the simulation randomizers for the envs
+        whose episode starts, and the park stage after them (gravity and body masses may have changed: the cancelling force follows them); the reach goals' forward
+        (the object the goal moved: _observe_sync's forward) and the env kernel, both over the `reobserve` codes -- first observation of a new episode / the new
+        goal's entries / skip.  No readback."""
+        act = None if active is None else active != 0
+        if started and self.randomizers:
+            mask = self.episode_started if act is None else self.episode_started & act
+            for rz in self.randomizers:
+                rz.randomize(self.sim, self._rand_gen, mask)
+            if self.max_num_objects is not None:
+                self._param_rows_launch(_native.RA_ROWS_PARK, active)
+        codes = self.reobserve if act is None else torch.where(act, self.reobserve, torch.full_like(self.reobserve, _native.RA_OBS_SKIP))
+        if self.reach:
+            self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=(codes != _native.RA_OBS_SKIP).to(torch.int32))
+        self._post(frozen=codes)
 
     def _reset_device(self, mask):
         """`reset(mask)` without the host: one forced-end launch of the recipe kernel for the envs of the mask (ra_recipe_args.sync_mode; whatever recipe they were in
@@ -1498,37 +1511,25 @@ class BatchedBlockRearrangeEnv:
             self._recipe_launch()
             r.sync_mode = _native.RA_SYNC_PIPELINED
             if self.param_rows is not None:
-                self._param_rows_launch(both)
+                self._param_rows_launch(both, self.active_row)
             iterations, stabilising = self.sync_reset_iterations(), max(int(self.stabilize_steps), 1)
             for it in range(iterations):
                 # the envs of the mask run the stages in lockstep, so the host knows what the recipe's rows hold: `solver_active` is 0 for all of them while the
-                # objects stabilise (no solver world launch: it would skip every env) and 1 afterwards
+                # objects stabilise (no solver world launch: it would skip every env) and 1 afterwards, where the mask restricts that launch too (the row is 1 for
+                # the live envs outside it)
                 if it < stabilising and self.stabilize_steps <= 0 and self.scene_init is not None:
                     # a recorded start without stabilisation: the stage of zero steps is counted, not simulated -- the episode starts AT the recorded state, as on the
                     # host route; where it is the recipe's last launch, the forward of _observe_sync that the last physics launch would have carried
                     if it == iterations - 1:
                         self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=act32)
-                elif self.joint_control:      # every env of these launches is inside its recipe: the stored controls while the objects stabilise, then the scripted action
-                    self.sim.env_step(action=self.scripted, nforward_ticks=2, flags=FLAG_FULL_FORWARD, active=act32, nticks=self.nticks, hold=self.hold_ctrl)
-                else:
-                    if it >= stabilising:
-                        self.solver_sim.step_tcp(self.sim, None if self.wrapped else self._zero_action, self.tcp_sync, active=act32)
-                    self.sim.env_step(nforward_ticks=2, flags=FLAG_FULL_FORWARD, active=act32, nticks=self.nticks)
+                else:      # every env of these launches is inside its recipe (`hold`): none takes the zero action handed over, unwrapped so that no live env's filter moves
+                    self._physics(self._zero_action, active=act32, phase="main" if it < stabilising else None, recipe_rows=True)
                 self._recipe_launch()
                 if self.param_rows is not None:
-                    self._param_rows_launch(both)
+                    self._param_rows_launch(both, self.active_row)
         finally:
             r.active, r.sync_mode = None, _native.RA_SYNC_PIPELINED
-        # the last launch started the episodes (the envs of the mask run the stages in lockstep)
-        if self.randomizers:
-            started = self.episode_started & act
-            for rz in self.randomizers:
-                rz.randomize(self.sim, self._rand_gen, started)
-            if self.max_num_objects is not None:      # (gravity and body masses may have changed: the cancelling force follows them)
-                self._param_rows_launch(_native.RA_ROWS_PARK)
-        if self.reach:
-            self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=act32)
-        self._post(frozen=torch.where(act, self.reobserve, torch.full_like(self.reobserve, _native.RA_OBS_SKIP)))
+        self._finish_recipe_launch(self.active_row)      # the last launch started the episodes (the envs of the mask run the stages in lockstep)
         self.episode_started.masked_fill_(act, False)      # (as after the host recipe: the flag belongs to the step calls of a pipelined env)
         self.ended_rows = np.zeros(0, dtype=np.int64)
         return self.observe()
@@ -1667,25 +1668,14 @@ class BatchedBlockRearrangeEnv:
             self.nticks.copy_(torch.as_tensor(want, device=dev))
 
     def _advance_recipes_device(self):
-        """`_advance_recipes` without the host: the recipe kernel (stage machine, begin-of-episode state, placement and goal sampling), tensor ops on its masks for the
-        per-env parameter rows (the block restored for an episode that ended = `_recreate_sim`'s fresh model; stabilize_objects' damping change; the simulation randomizers
-        for the envs whose episode starts), and the env kernel once more over the `reobserve` codes (first observation of a new episode / the new goal's entries)."""
+        """`_advance_recipes` without the host: the recipe kernel (stage machine, begin-of-episode state, placement and goal sampling), one launch on its masks for the
+        per-env parameter rows (the block restored for an episode that ended = `_recreate_sim`'s fresh model, mjData.xfrc_applied at zero among it; stabilize_objects'
+        damping change; the unused objects' parking rows), and `_finish_recipe_launch`: the simulation randomizers for the envs whose episode starts, the env kernel
+        once more over the `reobserve` codes."""
         self._recipe_launch()
-        if self.per_env_parameters:
-            P = self.sim.params
-            # (the block also holds mjData.xfrc_applied, whose default is zero: a re-created simulation starts without applied wrenches, as after mj_resetData)
-            P.block.copy_(torch.where(self.ended[:, None], self._param_block_default[None, :], P.block))
-            d, cols = P["dof_damping"], self.obj_dofs
-            cur = d[:, cols]
-            d[:, cols] = torch.where(self.ended[:, None], torch.full_like(cur, self.stabilize_object_damping),
-                                     torch.where(self.stabilised[:, None], self._param_defaults["dof_damping"][cols][None, :].expand_as(cur), cur))
-            for rz in self.randomizers:
-                rz.randomize(self.sim, self._rand_gen, self.episode_started)
-            if self.max_num_objects is not None:      # parking after the restore, the damping changes and the randomizers, on the recipe's masks
-                self._apply_parking(self.ended | self.stabilised | self.episode_started)
-        if self.reach:      # the object the goal moved: _observe_sync's forward for the envs with a new goal (no readback: every env, masked by the reobserve codes)
-            self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=(self.reobserve != _native.RA_OBS_SKIP).to(torch.int32))
-        self._post(frozen=self.reobserve)
+        if self.param_rows is not None:
+            self._param_rows_launch(_native.RA_ROWS_RESTORE | _native.RA_ROWS_PARK)
+        self._finish_recipe_launch()
         self.ended_rows = np.zeros(0, dtype=np.int64)
 
     def _set_object_damping(self, idx, value):
@@ -1764,9 +1754,7 @@ class BatchedBlockRearrangeEnv:
                 self._recipe_launch()
             finally:
                 r.sync_mode = _native.RA_SYNC_PIPELINED
-            if self.reach:
-                self.sim.env_step(nsubsteps=0, nforward_ticks=1, flags=FLAG_FULL_FORWARD, active=(self.reobserve != _native.RA_OBS_SKIP).to(torch.int32))
-            self._post(frozen=self.reobserve)
+            self._finish_recipe_launch(started=False)
             return
         rows = np.nonzero(self.goal_reset.cpu().numpy())[0]
         if len(rows) == 0:
@@ -1917,16 +1905,15 @@ def group_args(sp, constants):
     return out
 
 
-def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants=None, starting_seed: int = 0, apply_wrappers: bool = True, **kw):
-    """`BlockRearrangeEnv.build` surface (robot_env.py:1081-1089) for the batched env; `apply_wrappers` (default True, as in the reference) = the rearrange
-    wrapper stack of common/base.py:986-996 (MultiDiscrete actions of `constants.n_action_bins` = 11 bins, action smoothing, reward clipping).  `parameters` / `constants` accept the subset this env
-    implements (`SUPPORTED_*` below, and `constants.goal_args` {rot_dist_type, randomize_goal_rot, rot_randomize_type, soft_mask, mask_margin}: `goal_rot_args`); any other
-    name raises NotImplementedError.  `constants.mask_obs_outside_placement_area`: the masks of the placement area and the masked observation keys (MASK_OBS_KEYS)."""
+def make_env_args(parameters, constants, starting_seed, apply_wrappers, num_objects, icp=False):
+    """The constructor's keywords from the reference's `parameters` / `constants` -- what `make_env` here and in envs/rearrange/ycb.py share.  `num_objects`: the
+    env's default count; `icp`: `goal_rot_args`.  A name outside the supported subset raises (`_check_supported`).  -> (keywords, simulation_params, constants): the
+    two dicts as copies, `goal_args` taken out, for what a caller maps itself."""
     parameters, constants = dict(parameters or {}), dict(constants or {})
     sp, rc = dict(parameters.get("simulation_params", {})), dict(parameters.get("robot_control_params", {}))
-    rot_args = goal_rot_args(constants.pop("goal_args", None))      # constants.goal_args: rot_dist_type, randomize_goal_rot (the task modules take their own keys out first)
+    rot_args = goal_rot_args(constants.pop("goal_args", None), icp=icp)      # constants.goal_args: rot_dist_type, randomize_goal_rot (the task modules take their own keys out first)
     _check_supported(parameters, sp, rc, constants)
-    args = dict(num_objects=sp.get("num_objects", 5), max_position_change=rc.get("max_position_change", 0.1), arm_reset_controller_error=rc.get("arm_reset_controller_error", True),
+    args = dict(num_objects=sp.get("num_objects", num_objects), max_position_change=rc.get("max_position_change", 0.1), arm_reset_controller_error=rc.get("arm_reset_controller_error", True),
                 n_random_initial_steps=parameters.get("n_random_initial_steps", 10), starting_seed=starting_seed, wrappers=bool(apply_wrappers),
                 n_action_bins=constants.get("n_action_bins", 11), control_mode=rc.get("control_mode", "tcp+roll+yaw"), tcp_solver_mode=rc.get("tcp_solver_mode", "mocap_ik"))      # (+ pipelined_reset=True through **kw: episodes restart inside the step calls)
     if "action_spacing" in constants:
@@ -1934,13 +1921,22 @@ def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants
     for k in ("success_threshold", "successes_needed", "success_reward", "max_timesteps_per_goal_per_obj", "use_goal_distance_reward", "goal_reward_per_object"):
         if k in constants:
             args[k] = constants[k]
-    if "mask_obs_outside_placement_area" in constants:
+    if "mask_obs_outside_placement_area" in constants:      # the placement-area masks (goal_args.soft_mask / mask_margin come through goal_rot_args)
         args["mask_obs_outside_placement_area"] = bool(constants["mask_obs_outside_placement_area"])
     for k in ("penalty", "used_table_portion"):      # (a given penalty dict replaces the default one as a whole, as the reference's attrs field does)
         if k in sp:
             args[k] = sp[k]
     args.update(group_args(sp, constants))
     args.update(rot_args)
+    return args, sp, constants
+
+
+def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants=None, starting_seed: int = 0, apply_wrappers: bool = True, **kw):
+    """`BlockRearrangeEnv.build` surface (robot_env.py:1081-1089) for the batched env; `apply_wrappers` (default True, as in the reference) = the rearrange
+    wrapper stack of common/base.py:986-996 (MultiDiscrete actions of `constants.n_action_bins` = 11 bins, action smoothing, reward clipping).  `parameters` / `constants` accept the subset this env
+    implements (`SUPPORTED_*` below, and `constants.goal_args` {rot_dist_type, randomize_goal_rot, rot_randomize_type, soft_mask, mask_margin}: `goal_rot_args`); any other
+    name raises NotImplementedError.  `constants.mask_obs_outside_placement_area`: the masks of the placement area and the masked observation keys (MASK_OBS_KEYS)."""
+    args, sp, constants = make_env_args(parameters, constants, starting_seed, apply_wrappers, num_objects=5)
     for k in ("goal_distance_ratio", "goal_distance_min", "max_num_objects"):      # (max_num_objects: per-env object counts, num_objects the first count of every env)
         if k in sp:
             args[k] = sp[k]

@@ -295,32 +295,15 @@ class GroupedYcbRearrangeEnv:
 
 def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants=None, starting_seed: int = 0, apply_wrappers: bool = True, **kw):
     """`YcbRearrangeEnv.build` surface (ycb.py:96) for the batched env; accepts what envs/rearrange/blocks.py `make_env` accepts."""
-    from robogym_amd.envs.rearrange.blocks import _check_supported, goal_rot_args, group_args
+    from robogym_amd.envs.rearrange.blocks import make_env_args
 
     parameters, constants = dict(parameters or {}), dict(constants or {})
-    sp, rc = dict(parameters.get("simulation_params", {})), dict(parameters.get("robot_control_params", {}))
-    rot_args = goal_rot_args(constants.pop("goal_args", None), icp=True)      # constants.goal_args as blocks.make_env takes it, and rot_dist_type icp with its icp_* keys
-    if parameters.get("mesh_names") is not None or constants.get("normalize_mesh"):
+    if parameters.pop("mesh_names", None) is not None or constants.get("normalize_mesh"):
         raise NotImplementedError("mesh_names / normalize_mesh: the shipped models hold fixed object sets")
-    if "max_num_objects" in sp:
+    if "max_num_objects" in parameters.get("simulation_params", {}):
         raise NotImplementedError("parameters.simulation_params.max_num_objects (per-env object counts) is not implemented for the ycb worlds (their objects differ: "
                                   "a prefix of a set is no set of its own); rearrange/blocks and its tasks take it")
-    _check_supported({k: v for k, v in parameters.items() if k != "mesh_names"}, sp, rc, constants)
-    args = dict(num_objects=sp.get("num_objects", 8), max_position_change=rc.get("max_position_change", 0.1), arm_reset_controller_error=rc.get("arm_reset_controller_error", True),
-                n_random_initial_steps=parameters.get("n_random_initial_steps", 10), starting_seed=starting_seed, wrappers=bool(apply_wrappers),
-                n_action_bins=constants.get("n_action_bins", 11), control_mode=rc.get("control_mode", "tcp+roll+yaw"), tcp_solver_mode=rc.get("tcp_solver_mode", "mocap_ik"))
-    if "action_spacing" in constants:
-        args["action_spacing"] = constants["action_spacing"]
-    for k in ("success_threshold", "successes_needed", "success_reward", "max_timesteps_per_goal_per_obj", "use_goal_distance_reward", "goal_reward_per_object"):
-        if k in constants:
-            args[k] = constants[k]
-    if "mask_obs_outside_placement_area" in constants:      # the placement-area masks (goal_args.soft_mask / mask_margin come through goal_rot_args)
-        args["mask_obs_outside_placement_area"] = bool(constants["mask_obs_outside_placement_area"])
-    for k in ("penalty", "used_table_portion"):
-        if k in sp:
-            args[k] = sp[k]
-    args.update(group_args(sp, constants))
-    args.update(rot_args)
+    args = make_env_args(parameters, constants, starting_seed, apply_wrappers, num_objects=8, icp=True)[0]      # (icp: rot_dist_type icp with its icp_* keys)
     args.update(kw)
     object_sets = args.pop("object_sets", None)      # e.g. (0, 1, 2, 3): different object sets across the batch (GroupedYcbRearrangeEnv)
     if object_sets is not None and len(object_sets) > 1:

@@ -528,6 +528,73 @@ def test_grouped_ycb_refuses_on_device_gpu():
     _grouped_refusal(GPU, None)
 
 
+# ------------------------------------------------------------------------------------------------ 7. the parameter rows' launch against the host route's methods
+# (ended, stabilised, episode_started) per env; an env of the last pattern has its masks set and `active` = 0
+ROW_PATTERNS = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 0, 1), (0, 0, 0), (1, 1, 1))
+
+
+def _param_rows_against_host_route(tier, lib, counted):
+    """ra_param_rows_kernel, the device route's only implementation of the per-env parameter rows, against the host route's: the `_param_defaults` restore for
+    `ended`, then `_set_object_damping`, then `_apply_parking`, run on the env's own block and swapped out again.  Env e has pattern (e + shift) mod 6 of
+    ROW_PATTERNS and, `counted` (max_num_objects = 5), (e + shift) mod 5 + 1 objects; three shifts, so that B = 4 meets every pattern too.  Every word of the block
+    is perturbed per env, `body_mass` and `gravity` once more with the env's index.  One launch with both stages: the whole block bit-equal on every env, the
+    skipped envs (no mask byte, or outside `active`) as they were to the byte.  52 of the 874 words of a block lie between the named fields (alignment); no
+    host method addresses them, the kernel's restore of an ended env returns them to the model's values with the rest, which is what is expected of them here.
+    Not `counted`: `num_active` = NULL, nothing is parked."""
+    env = _make(tier, lib, device_reset=True, starting_seed=6, **(dict(num_objects=3, max_num_objects=5) if counted else {}))
+    B, P, dev = env.B, env.sim.params, env.device
+    assert bool(env.param_rows.num_active) == counted
+    default = env._param_block_default.clone()
+    P.block.zero_()
+    for k in P.keys():
+        P[k].fill_(1.0)
+    between = torch.nonzero(P.block[0] == 0).flatten()
+    bits = lambda t: t.contiguous().view(torch.int32)
+    e = torch.arange(B, device=dev)
+    for shift in (0, 2, 4):
+        pattern = torch.tensor(ROW_PATTERNS, device=dev)[(e + shift) % 6].bool()
+        active = (e + shift) % 6 != 5
+        env.ended.copy_(pattern[:, 0]); env.stabilised.copy_(pattern[:, 1]); env.episode_started.copy_(pattern[:, 2]); env.active_row.copy_(active)
+        touched = pattern.any(1) & active
+        if counted:
+            env.num_active.copy_(((e + shift) % 5 + 1).to(torch.int32))
+        noise = torch.rand(P.block.shape, generator=torch.Generator().manual_seed(100 + shift)).to(dev)
+        P.block.copy_(default[None, :] * (1.0 + noise) + 0.25 * noise + 0.01)
+        P["body_mass"].mul_(1.0 + 0.1 * e[:, None]); P["gravity"].add_(0.01 * e[:, None])
+        start = P.block.clone()
+        assert bool((bits(start) != bits(default)[None, :]).all()), "a word of the block was left at the model's value"
+        # the host route's methods, in its order
+        ended = torch.nonzero(env.ended & active).flatten()
+        for k, v in env._param_defaults.items():
+            P[k][ended] = v
+        env._set_object_damping(ended, env.stabilize_object_damping)
+        env._set_object_damping(torch.nonzero(env.stabilised & ~env.ended & active).flatten(), None)
+        if counted:
+            env._apply_parking(touched)
+        want = P.block.clone()
+        want[ended[:, None], between[None, :]] = default[between]
+        P.block.copy_(start)
+        env._param_rows_launch(_native.RA_ROWS_RESTORE | _native.RA_ROWS_PARK, env.active_row)
+        env.sync()
+        got = P.block.clone()
+        assert torch.equal(bits(got), bits(want)), "shift %d: envs %s differ from the host route's rows" % (shift, torch.nonzero((bits(got) != bits(want)).any(1)).flatten().tolist())
+        assert torch.equal(bits(got[~touched]), bits(start[~touched])) and bool((bits(got[ended]) != bits(start[ended])).any(1).all())
+        if counted:      # (the case is live: unused objects exist and hold their parking rows)
+            unused = touched[:, None] & (env._slot[None, :] >= env.num_active[:, None])
+            assert bool(unused.any()) and bool((P["dof_damping"][:, env.obj_dofs].unflatten(1, (env.N, 6))[unused] == blocks.PARK_DAMPING).all())
+
+
+@pytest.mark.parametrize("counted", [True, False])
+def test_param_rows_launch_is_the_host_route_emul(emul_lib, counted):
+    _param_rows_against_host_route(EMUL, emul_lib, counted)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("counted", [True, False])
+def test_param_rows_launch_is_the_host_route_gpu(counted):
+    _param_rows_against_host_route(GPU, None, counted)
+
+
 def test_sync_reset_header_matches_the_library_and_the_binding():
     """include/rgstep_sync_reset.h (included by include/rgstep.h) under the rule tests/test_boundary.py applies to rgstep.h itself: the gfx950 build of the library
     exports what it declares, the binding lists the same names, and the argument structs have the library's sizes."""

@@ -1,6 +1,6 @@
 """Digests of the rearrange envs' device state over a fixed seeded matrix, for comparing two builds of the library bit for bit (a refactor of the ra_* kernels
 against its parent commit): one sha256 per reset / step / reset_goals call over the bytes of the packed observation row, the goal rows, the tracker, the recipe's rows
-and both worlds' qpos.
+and both worlds' qpos, and of the per-env parameter block where the env has one.
 
     python tools/ra_identity_digest.py --lib A/librgstep.so --tier gpu > a.txt          # one process per library
     python tools/ra_identity_digest.py --lib B/librgstep.so --tier gpu > b.txt
@@ -9,7 +9,8 @@ and both worlds' qpos.
 Tiers as tests/test_rearrange_sync_reset.py: emul (the emulation harness' library, B = 4, n_substeps = 1) and gpu (B = 64, n_substeps = 2), with its FAST recipe and a
 goal time-out of one step per object, so that episodes end and restart through the recipe inside the steps taken.  The matrix: the nine goal kinds through their tasks'
 make_env, rot_dist_type full / mod90 / mod180 and icp (ycb), object_groups single / sample, mixed per-env object counts, masked observations with soft_mask, control modes,
-wrapped and unwrapped, pipelined device resets, and the synchronous reset(mask) / reset_goals() on the device."""
+wrapped and unwrapped, pipelined device resets, the synchronous reset(mask) / reset_goals() on the device, and three rows of the host route (device_reset=False):
+pipelined resets, the synchronous reset(mask), and a recorded scene whose goals advance; last, the synchronous reset(mask) on the device of a wrapped env."""
 import argparse
 import hashlib
 import os
@@ -30,7 +31,8 @@ def digest(env):
     env.sync()
     h = hashlib.sha256()
     worlds = [env.sim.qpos] + ([env.solver_sim.qpos] if env.solver_sim is not None else [])
-    for ten in [getattr(env, name, None) for name in ROWS] + worlds:
+    params = [env.sim.params.block] if env.per_env_parameters else []
+    for ten in [getattr(env, name, None) for name in ROWS] + worlds + params:
         if ten is not None:
             h.update(ten.detach().cpu().contiguous().numpy().tobytes())
     return h.hexdigest()
@@ -61,6 +63,15 @@ def matrix(tier, lib):
         args = dict(kw, n_random_initial_steps=1, max_timesteps_per_goal_per_obj=1, pipelined_reset=True, goal_kind="fixed", relative_placements=rel, init_quats=quats)
         return blocks.BatchedBlockRearrangeEnv(args.pop("batch_size"), **args)
 
+    def recorded():
+        golden = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "rearrange_holdout_initial_state_4_blocks_stacked.npz")
+        base = blocks.load_state(golden, 4)
+        moved = lambda dx, dy: {"obj_pos": base[:, :3] + [dx, dy, 0.0], "obj_quat": base[:, 3:]}
+        args = dict(kw, device_reset=False, n_random_initial_steps=0, pipelined_reset=True, num_objects=4, initial_states=[moved(0.0, 0.0), moved(-0.3, 0.2)],
+                    goal_states=[[moved(-0.2, 0.1), moved(0.0, 0.0)], [moved(-0.1, 0.3)]], advance_goals=True, successes_needed=3,
+                    success_threshold={"obj_pos": 10.0, "obj_rot": 10.0, "rel_dist": 10.0})
+        return blocks.BatchedBlockRearrangeEnv(args.pop("batch_size"), **args)
+
     rot = lambda kind: {"goal_args": {"rot_dist_type": kind, "randomize_goal_rot": True}}
     rows = [("kind object_state", task(blocks), "steps"), ("kind pickandplace", task(blocks_pickandplace, sp={"num_objects": 2}), "steps"),
             ("kind stack", task(blocks_stack), "steps"), ("kind reach", task(blocks_reach), "steps"),
@@ -77,6 +88,10 @@ def matrix(tier, lib):
              ("sync reset(mask)", task(blocks, pipelined=False), "sync"),
              ("sync reset_goals", task(blocks, pipelined=False, constants={"success_threshold": {"obj_pos": 10.0, "obj_rot": 10.0}}), "regoal"),
              ("sync reset_goals reach", task(blocks_reach, pipelined=False, constants={"success_threshold": {"obj_pos": 10.0, "obj_rot": 10.0}}), "regoal")]
+    rows += [("host pipelined", task(blocks, device_reset=False), "steps"), ("host reset(mask)", task(blocks, pipelined=False, device_reset=False), "sync host"),
+             ("host recorded goals", recorded, "steps"),
+             # (a wrapped env's synchronous reset: its launches take the recipe's scripted actions, the steps around them bin indices through the filter)
+             ("sync reset(mask) wrapped", task(blocks, pipelined=False, wrapped=True), "sync")]
     return rows
 
 
@@ -96,9 +111,9 @@ def run(name, make, protocol):
     env.reset(); say("reset")
     for s in range(STEPS):
         env.step(actions(env, gen)); say("step")
-        if protocol == "sync" and s % 6 == 5:        # finished envs, then a fixed subset whatever its state
+        if protocol in ("sync", "sync host") and s % 6 == 5:        # finished envs, then a fixed subset whatever its state
             mask = env.done.clone() if s % 12 == 5 else torch.zeros(B, dtype=torch.bool, device=env.device).index_fill_(0, torch.tensor([0, B - 1], device=env.device), True)
-            env.reset(mask=mask, on_device=True); say("reset(mask)")
+            env.reset(mask=mask, on_device=protocol == "sync"); say("reset(mask)")
         if protocol == "regoal" and s % 3 == 0:
             env.reset_goals(on_device=True); say("reset_goals")
             if s >= 12:
