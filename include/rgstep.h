@@ -631,6 +631,12 @@ typedef struct ra_post_args {
    * threshold's keys, common/base.py:824-848); rel_threshold <= 0: rel_dist is reported only.  The observation row does not change. */
   float* rel_dist;                               /* [B][N] */
   float rel_threshold;
+  /* per-env object subsets drawn from the world's pool (appended; NULL = none, every path above as it is).  obj_perm [B][M], M = num_objects: a permutation of 0..M-1 per
+   * env; observation / goal SLOT i of env e is world object obj_perm[e][i].  Needs num_active (an error otherwise): slots i < num_active[e] are in use, the world
+   * objects of the other slots are parked and padded as above.  Indexed by slot: goal, goal_rot, static_obs, goal_in_area, icp_rel, obj_group, rel_dist and every
+   * per-object observation key; by world object: obj_body (pose, velocities, contacts, off-table test, the anchor of rel_dist, the matching's positions).  An entry
+   * outside 0..M-1 reads as the slot's own index.  ra_env_recipe_step latches and samples the rows (ra_recipe_args.obj_perm). */
+  const int* obj_perm;
 } ra_post_args;
 int ra_env_post_step(rb_batch* main, rb_batch* solver, const ra_post_args* args, void* stream);
 int ra_post_args_size(void);
@@ -771,6 +777,17 @@ typedef struct ra_recipe_args {
   int* scene;
   int* goal_cursor;
   int advance_goals;
+  /* per-env object subsets drawn from the world's pool (appended; NULL = none, every path above as it is).  obj_perm [B][M], M = num_objects, is ra_post_args' row and
+   * needs num_active / num_objects_next (the caller fills both with the batch's count n), obj_perm_next and goal kind RA_GOAL_OBJECT_STATE or RA_GOAL_PICKANDPLACE
+   * without recorded scenes: an error otherwise.  When an env's episode ends the kernel latches the row where it latches num_active: row obj_perm_next[e] is copied if it
+   * is a permutation of 0..M-1 (checked with a 16-bit mask of the entries seen; the kernel never indexes with an unchecked entry) -- a value written mid-episode waits
+   * for that --; if it is not, its first entry < 0 (the rows' default) among it, a permutation is SAMPLED: Fisher-Yates over the identity, for i = 0 .. M-2:
+   * j = i + min(M-1-i, floor(u (M-i))), swap i and j, draws (seed ^ 0x27D4EB2Fu, step, env, i): a stream of their own, no other draw changes its stream or index.
+   * Slot i of the env is then world object p = obj_perm[e][i]: obj_qposadr, obj_center, obj_half and park_pose are read at p -- the placement (grid cell sizes, rejection
+   * order, rest heights), the goal placement, qpos / qpos_goal (slot i's pose at object p's address; the objects of slots >= n at their OWN park_pose[p]) and the
+   * static observation's box --, while yaw, goal, goal_rot, static_obs, goal_in_area, the colour draws and the pick-and-place raise go by slot. */
+  int* obj_perm;
+  const int* obj_perm_next;
 } ra_recipe_args;
 /* The launch that follows it on the per-env parameter rows (ra_param_rows_args): declared and described in rgstep_sync_reset.h, which the end of this header includes. */
 int ra_env_recipe_step(rb_batch* main, rb_batch* solver, const ra_recipe_args* args, void* stream);

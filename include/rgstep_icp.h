@@ -28,6 +28,10 @@ typedef struct ra_icp_args {
   const int* obj_group;                          /* [B][N] or NULL */
   const int* num_active;                         /* [B] or NULL */
   const unsigned char* frozen;                   /* [B] or NULL */
+  /* per-env object subsets (appended; NULL = none, every path above as it is): ra_post_args' obj_perm [B][N], needs num_active.  The workgroup of (env, slot i) fits world
+   * object p = obj_perm[env][i]: obj_body, src / src_num and the target cloud (tgt_adr / tgt_num; with obj_group the world object of the matched goal's slot) are read
+   * at p, goal and icp_rel by slot. */
+  const int* obj_perm;
 } ra_icp_args;
 int ra_env_icp(rb_batch* main, const ra_icp_args* args, void* stream);
 int ra_icp_args_size(void);

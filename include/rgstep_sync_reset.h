@@ -29,6 +29,9 @@ typedef struct ra_param_rows_args {
   const int* num_active;                         /* [B] or NULL: no parking */
   float park_damping;
   int stages;                                    /* RA_ROWS_RESTORE | RA_ROWS_PARK */
+  /* per-env object subsets (appended; NULL = none, every path above as it is): ra_recipe_args' obj_perm [B][N] as the recipe launch left it, needs num_active.  The park
+   * stage then parks the WORLD objects of the slots >= num_active[env]: obj_body and obj_dofadr are read at obj_perm[env][slot]. */
+  const int* obj_perm;
 } ra_param_rows_args;
 int ra_env_param_rows(rb_batch* main, const ra_param_rows_args* args, void* stream);
 int ra_param_rows_args_size(void);

@@ -26,8 +26,16 @@ __host__ __device__ inline bool ra_kind_uses_grip_site(int kind) { return kind =
 __host__ __device__ inline bool ra_kind_places_on_grid(int kind) { return kind == RA_GOAL_OBJECT_STATE || kind == RA_GOAL_PICKANDPLACE; }
 __host__ __device__ inline bool ra_kind_is_counted(int kind) { return ra_kind_places_on_grid(kind) || kind == RA_GOAL_STACK || kind == RA_GOAL_TRAIN; }   // built for per-env object counts
 // the draw streams env_u01(seed ^ stream, step, env, k) (the recipe's own is the plain seed), and the first draw index k of the sections that share a stream
-enum : unsigned { RA_STREAM_GOAL = 0x9E3779B9u, RA_STREAM_GOAL_YAW = 0xC2B2AE35u, RA_STREAM_GROUPS = 0x85EBCA6Bu, RA_STREAM_OBJ_MASK = 0xA54FF53Au, RA_STREAM_GOAL_MASK = 0x3C6EF372u,
+enum : unsigned { RA_STREAM_GOAL = 0x9E3779B9u, RA_STREAM_GOAL_YAW = 0xC2B2AE35u, RA_STREAM_GROUPS = 0x85EBCA6Bu, RA_STREAM_OBJ_MASK = 0xA54FF53Au, RA_STREAM_GOAL_MASK = 0x3C6EF372u, RA_STREAM_OBJECT_SET = 0x27D4EB2Fu,
                   RA_DRAW_COLOURS = 500u, RA_DRAW_PLACEMENT = 1000u, RA_DRAW_GROUPS = 3000u };
+// per-env object subsets (ra_post_args.obj_perm, include/rgstep.h): the world object in slot `slot` < N of env e -- the slot itself without a row, and for an entry
+// that names no object.  One load per lane (or per workgroup into LDS: ra_recipe_kernel); every table of the WORLD's objects (body ids, addresses, boxes, parking
+// poses, clouds) is read at what this returns, every per-env row (goals, yaws, static observation, observation keys) at the slot.
+__device__ inline int ra_slot_object(const int* obj_perm, int e, int N, int slot) {
+  if (!obj_perm) return slot;
+  const int p = obj_perm[(size_t)e * N + slot];
+  return (unsigned)p < (unsigned)N ? p : slot;
+}
 // one env's draws from one stream, in order
 struct RaDraws { unsigned seed, step, e, k; __device__ float operator()() { return env_u01(seed, step, e, k++); } };
 
@@ -42,15 +50,17 @@ struct RaDraws { unsigned seed, step, e, k; __device__ float operator()() { retu
 // rows / columns are two 16-bit masks, the same on every lane.  A distance that is not finite is never picked: such an object keeps its own goal.
 // `n` <= N: the env's active objects (ra_post_args.num_active) -- a pair with an inactive member is at +inf like a pair across groups, so no active object is ever
 // measured against an inactive slot's goal; n = N is the matching above.
-__device__ inline int ra_group_match(const int* grp, const float* xpos, const int* obj_body, const float* goal, int N, int n, int lane) {
+// `pobj`: the world object of this lane's slot (ra_slot_object; the lane itself without object subsets), handed to the pair's lane by a shuffle every lane takes part in.
+__device__ inline int ra_group_match(const int* grp, const float* xpos, const int* obj_body, const float* goal, int N, int n, int lane, int pobj) {
   float d[4];
   for (int s = 0; s < 4; s++) {
     const int p = lane + 64 * s;
+    const int oi = __shfl(pobj, p < N * N ? p / N : 0);
     d[s] = INFINITY;
     if (p < N * N) {
       const int i = p / N, j = p - i * N;
       if (grp[i] == grp[j] && i < n && j < n) {
-        const float* x = xpos + 3 * obj_body[i]; const float* g = goal + 7 * j;
+        const float* x = xpos + 3 * obj_body[oi]; const float* g = goal + 7 * j;
         const float dx = x[0] - g[0], dy = x[1] - g[1], dz = x[2] - g[2];
         d[s] = dx * dx + dy * dy + dz * dz;
       }
@@ -166,12 +176,13 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
   float dpos = 0.f, drot = 0.f, dgrip = 0.f, grasp = 0.f;
   const int reach = ra_kind_is_reach(a.goal_kind);
   const float* grip = S + m.off[RB_O_SPOS] + 3 * a.grip_site;      // (ra_kind_uses_grip_site only)
+  const int pobj = lane < N ? ra_slot_object(a.obj_perm, e, N, lane) : lane;      // the world object of this lane's slot (object subsets; the lane itself without)
   int mgoal = lane;                              // the goal this lane's object is measured against: its own, or its match inside its group of duplicates
-  if (a.obj_group) mgoal = ra_group_match(a.obj_group + (size_t)e * N, xpos, a.obj_body, a.goal + (size_t)e * N * 7, N, n, lane);
+  if (a.obj_group) mgoal = ra_group_match(a.obj_group + (size_t)e * N, xpos, a.obj_body, a.goal + (size_t)e * N * 7, N, n, lane, pobj);
   RaObjVals v = {};                              // (a padded slot keeps the zeros: simulation/base.py:222-224, 1015-1024; goals/object_state.py:556-580)
   bool obj_in = true, goal_in = true;            // mask_obs: the two masks (a padded slot reads 1.0: the reference pads them with True, simulation/base.py:893-897)
   if (lane < n) {
-    const int b = a.obj_body[lane];
+    const int b = a.obj_body[pobj];
     float M[9], eul[3], vp[3], vr[3];
     rbc_quat2mat(xquat + 4 * b, M);
     rbc_mat2euler(M, eul);
@@ -263,10 +274,11 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
       if (oz < gz || (oz == gz && oa < anchor)) { gz = oz; anchor = oa; }
     }
     if (anchor >= n) anchor = 0;                                       // (no goal z compares: NaN rows; np.argmin would name the first)
+    const int panchor = __shfl(pobj, anchor);                          // (the anchor's world object, from its lane)
     float rd = 0.f;
     if (lane < n) {
       const float* ga = a.goal + ((size_t)e * N + anchor) * 7; const float* gi = a.goal + ((size_t)e * N + lane) * 7;
-      const float* pa = xpos + 3 * a.obj_body[anchor]; const float* pi = xpos + 3 * a.obj_body[lane];
+      const float* pa = xpos + 3 * a.obj_body[panchor]; const float* pi = xpos + 3 * a.obj_body[pobj];
       const float dx = pi[0] - (gi[0] - ga[0] + pa[0]), dy = pi[1] - (gi[1] - ga[1] + pa[1]), dz = pi[2] - (gi[2] - ga[2] + pa[2]);
       rd = sqrtf(dx * dx + dy * dy + dz * dz);
       if (a.rel_threshold > 0.f) ok_obj = ok_obj && rd < a.rel_threshold;
@@ -374,7 +386,8 @@ __global__ void __launch_bounds__(64) ra_post_step_kernel(const RbModelDev* mp, 
 // (recorded scenes, ra_recipe_args.scene_init / scene_goal: `init_scene` with the start's quaternions `iquat` and turned half extents `ihalf`; `recorded` with the
 //  goal's quaternion `gquat`, its normalised Euler angles `geul` and euler2quat of those, `gqe`)
 struct RaRecipeLds { int started, ended, regoal, moved; float pos[RA_MAXOBJ][3], gpos[RA_MAXOBJ][3], gyaw[RA_MAXOBJ], opos[3]; int n;
-                     int init_scene, recorded; float iquat[RA_MAXOBJ][4], ihalf[RA_MAXOBJ][3], gquat[RA_MAXOBJ][4], geul[RA_MAXOBJ][3], gqe[RA_MAXOBJ][4]; };
+                     int init_scene, recorded; float iquat[RA_MAXOBJ][4], ihalf[RA_MAXOBJ][3], gquat[RA_MAXOBJ][4], geul[RA_MAXOBJ][3], gqe[RA_MAXOBJ][4];
+                     int perm[RA_MAXOBJ]; };      // perm: slot -> world object of this env (ra_recipe_args.obj_perm; the identity without), loaded once per workgroup
 // the env's latched scene, inside the tables whatever the row holds
 __device__ inline int ra_scene_of(const RaRecipeArgs& a, int e) { const int s = a.scene[e]; return s < 0 ? 0 : (s >= a.num_scenes ? a.num_scenes - 1 : s); }
 // rotate_bounding_box: half extents in x and y of object i's box turned about z by `yaw`
@@ -389,11 +402,12 @@ __device__ inline float ra_rest_z(const RaRecipeArgs& a, int i) { return a.obj_h
 
 // One placement of the first N objects (rotated about z by yaw[i]) inside the placement area: body origins in world coordinates.  Returns false when the rejection
 // sampling ran out of restarts (out = its last proposal).  `U`: this env's draws, in order.  `no_grid`: place_objects_with_no_constraint even where the grid
-// has cells enough (the stack and reach goals' own placement).  `ar`: the env's placement area (ra_area).
-__device__ inline bool ra_place(const RaRecipeArgs& a, const RaArea& ar, int N, bool no_grid, const float* yaw, int ystride, RaDraws& U, float (*out)[3]) {
+// has cells enough (the stack and reach goals' own placement).  `ar`: the env's placement area (ra_area).  `pm`: slot -> world object (RaRecipeLds.perm): yaw and
+// out go by slot, the boxes by world object.
+__device__ inline bool ra_place(const RaRecipeArgs& a, const RaArea& ar, int N, bool no_grid, const float* yaw, int ystride, RaDraws& U, float (*out)[3], const int* pm) {
   float hx[RA_MAXOBJ], hy[RA_MAXOBJ], xy[RA_MAXOBJ][2];
   float mx = 0.f, my = 0.f;
-  for (int i = 0; i < N; i++) { ra_yawed_half(a, i, yaw[i * ystride], hx[i], hy[i]); mx = fmaxf(mx, hx[i]); my = fmaxf(my, hy[i]); }
+  for (int i = 0; i < N; i++) { ra_yawed_half(a, pm[i], yaw[i * ystride], hx[i], hy[i]); mx = fmaxf(mx, hx[i]); my = fmaxf(my, hy[i]); }
   const float width = ar.size[0], height = ar.size[1];
   const int ncol = (int)floorf(width / (2.f * mx)), nrow = (int)floorf(height / (2.f * my));
   const int M = ncol * nrow;
@@ -416,9 +430,9 @@ __device__ inline bool ra_place(const RaRecipeArgs& a, const RaArea& ar, int N, 
     int order[RA_MAXOBJ];
     for (int i = 0; i < N; i++) order[i] = i;
     for (int i = 1; i < N; i++) {      // stable insertion sort, area descending
-      const int v = order[i]; const float av = a.obj_half[v][0] * a.obj_half[v][1];
+      const int v = order[i]; const float av = a.obj_half[pm[v]][0] * a.obj_half[pm[v]][1];
       int j = i - 1;
-      while (j >= 0 && a.obj_half[order[j]][0] * a.obj_half[order[j]][1] < av) { order[j + 1] = order[j]; j--; }
+      while (j >= 0 && a.obj_half[pm[order[j]]][0] * a.obj_half[pm[order[j]]][1] < av) { order[j + 1] = order[j]; j--; }
       order[j + 1] = v;
     }
     ok = false;
@@ -440,8 +454,9 @@ __device__ inline bool ra_place(const RaRecipeArgs& a, const RaArea& ar, int N, 
   }
   for (int i = 0; i < N; i++) {      // the body origin, from the centre of its bounding box
     const float c = cosf(yaw[i * ystride]), s_ = sinf(yaw[i * ystride]);
-    const float ccx = c * a.obj_center[i][0] - s_ * a.obj_center[i][1], ccy = s_ * a.obj_center[i][0] + c * a.obj_center[i][1];
-    out[i][0] = ra_area_to_world(a, ar.off[0], 0, xy[i][0]) - ccx; out[i][1] = ra_area_to_world(a, ar.off[1], 1, xy[i][1]) - ccy; out[i][2] = ra_rest_z(a, i);
+    const int w = pm[i];
+    const float ccx = c * a.obj_center[w][0] - s_ * a.obj_center[w][1], ccy = s_ * a.obj_center[w][0] + c * a.obj_center[w][1];
+    out[i][0] = ra_area_to_world(a, ar.off[0], 0, xy[i][0]) - ccx; out[i][1] = ra_area_to_world(a, ar.off[1], 1, xy[i][1]) - ccy; out[i][2] = ra_rest_z(a, w);
   }
   return ok;
 }
@@ -600,16 +615,16 @@ __device__ inline void ra_sample_goal(const RaRecipeArgs& a, RaRecipeLds& F, int
   // (the kinds of ra_kind_is_counted place the env's n active objects; the others are built without per-env counts: n = N)
   switch (kind) {
     case RA_GOAL_OBJECT_STATE: case RA_GOAL_PICKANDPLACE:
-      ok = ra_place(a, ar, n, false, F.gyaw, 1, UG, F.gpos);
+      ok = ra_place(a, ar, n, false, F.gyaw, 1, UG, F.gpos, F.perm);
       if (kind == RA_GOAL_PICKANDPLACE) {                              // move_one_object_to_the_air: height first, then the object
         const float h = a.height_range[0] + UG() * (a.height_range[1] - a.height_range[0]);
-        int i = (int)(UG() * (float)n); i = i > n - 1 ? n - 1 : i;
+        int i = (int)(UG() * (float)n); i = i > n - 1 ? n - 1 : i;      // (a SLOT)
         F.gpos[i][2] += h;
       }
       break;
     case RA_GOAL_STACK: {                                              // ObjectStackGoal: object 0's box placed, the others on top of it in block order
       float bot[1][3];
-      ok = ra_place(a, ar, 1, true, F.gyaw, 1, UG, bot);
+      ok = ra_place(a, ar, 1, true, F.gyaw, 1, UG, bot, F.perm);
       int order[RA_MAXOBJ];
       for (int i = 0; i < n; i++) order[i] = i;
       if (!a.fixed_order)
@@ -648,7 +663,7 @@ __device__ inline void ra_sample_goal(const RaRecipeArgs& a, RaRecipeLds& F, int
       ra_place_fixed(a, N, a.fixed_xy, F.gpos); break;
     case RA_GOAL_REACH: case RA_GOAL_DET_REACH:                        // the object goes to the placement, the goal target_height above it
       if (kind == RA_GOAL_REACH) {
-        ok = ra_place(a, ar, 1, true, F.gyaw, 1, UG, F.gpos);
+        ok = ra_place(a, ar, 1, true, F.gyaw, 1, UG, F.gpos, F.perm);
       } else {
         const int gi = (a.goal_index[e] + 1) & 1;
         a.goal_index[e] = gi;
@@ -681,11 +696,34 @@ __device__ inline void ra_sample_groups(const RaRecipeArgs& a, int e, int n) {
     first += c;
   }
 }
+// Per-env object subsets: the permutation of the episode that begins, into F.perm and the env's row of a.obj_perm (ra_recipe_args.obj_perm, include/rgstep.h).  Row
+// obj_perm_next[e] is read ONCE into `row` and checked there with a 16-bit mask of the entries seen: nothing is indexed with an entry before it passed.  A row that is
+// no permutation (the default's -1 among them) is replaced by a sampled one: Fisher-Yates over the identity from a stream of its own, RA_STREAM_OBJECT_SET.
+__device__ inline void ra_latch_object_set(const RaRecipeArgs& a, RaRecipeLds& F, int e) {
+  const int N = a.num_objects;
+  int row[RA_MAXOBJ];
+  unsigned seen = 0u;
+  bool valid = true;
+  for (int i = 0; i < N; i++) {
+    row[i] = a.obj_perm_next[(size_t)e * N + i];
+    if ((unsigned)row[i] >= (unsigned)N || ((seen >> row[i]) & 1u)) valid = false; else seen |= 1u << row[i];
+  }
+  if (!valid) {
+    RaDraws U = {a.seed ^ RA_STREAM_OBJECT_SET, a.step, (unsigned)e, 0u};
+    for (int i = 0; i < N; i++) row[i] = i;
+    for (int i = 0; i < N - 1; i++) {
+      int j = (int)floorf(U() * (float)(N - i)); j = i + (j > N - 1 - i ? N - 1 - i : (j < 0 ? 0 : j));
+      const int tmp = row[i]; row[i] = row[j]; row[j] = tmp;
+    }
+  }
+  for (int i = 0; i < N; i++) { F.perm[i] = row[i]; a.obj_perm[(size_t)e * N + i] = row[i]; }
+}
 // An episode ended: its recipe begins.  The count of the episode that begins is latched (RearrangeEnv._reset re-creates the simulation with the current num_objects,
 // common/base.py:850-856, 904), the groups sampled, the objects' yaws and placement drawn into a.yaw / F.pos, and the rows that hold the env set.
 __device__ inline void ra_begin_recipe(const RaRecipeArgs& a, RaRecipeLds& F, int e, int& n, int& st, int& lf) {
   const int N = a.num_objects, AD = a.action_dim;
   if (a.num_active) { n = a.num_objects_next[e]; n = n < 1 ? 1 : (n > N ? N : n); a.num_active[e] = n; }
+  if (a.obj_perm) ra_latch_object_set(a, F, e);
   if (a.obj_group && a.group_mode == RA_GROUPS_SAMPLE) ra_sample_groups(a, e, n);
   if (a.scene) { const int s = a.scene_next[e]; a.scene[e] = s < 0 ? 0 : (s >= a.num_scenes ? a.num_scenes - 1 : s); }
   float* yw = a.yaw + (size_t)e * N;
@@ -703,7 +741,7 @@ __device__ inline void ra_begin_recipe(const RaRecipeArgs& a, RaRecipeLds& F, in
   } else {
     RaDraws U = {a.seed, a.step, (unsigned)e, RA_DRAW_PLACEMENT};
     for (int i = 0; i < N; i++) yw[i] = i < n ? 2.f * RBC_PI * U() : 0.f;
-    if (!ra_place(a, ra_area(a, n), n, false, yw, 1, U, F.pos)) a.placement_failed[e] += 1;
+    if (!ra_place(a, ra_area(a, n), n, false, yw, 1, U, F.pos, F.perm)) a.placement_failed[e] += 1;
   }
   st = RA_STAGE_STABILISE; lf = a.stabilize_steps > 0 ? a.stabilize_steps : 1;
   a.hold[e] = 1; a.hold_ctrl[e] = 1; a.frozen[e] = RA_OBS_IN_RECIPE; a.solver_active[e] = 0; a.resetting[e] = 1;
@@ -711,13 +749,14 @@ __device__ inline void ra_begin_recipe(const RaRecipeArgs& a, RaRecipeLds& F, in
 }
 // Entry i of a qpos row in which the env's n active objects sit at pos[o], turned about z by yaw[o] (`wrap`: normalised first), and the others at their parking
 // poses (ra_recipe_args.park_pose); `v` where no object lives.  `quat` (recorded scenes): the active objects' quaternions, in place of the yaws.
-__device__ inline float ra_qpos_with_objects(const RaRecipeArgs& a, int i, int n, float v, const float (*pos)[3], const float* yaw, bool wrap, const float (*quat)[4] = 0) {
-  for (int o = 0; o < a.num_objects; o++) {
-    const int d = i - a.obj_qposadr[o];
+// `pm`: slot -> world object (RaRecipeLds.perm): pos / yaw / quat and n go by slot, slot s's pose lands at world object pm[s]'s address, and an object is parked at its own pose.
+__device__ inline float ra_qpos_with_objects(const RaRecipeArgs& a, const int* pm, int i, int n, float v, const float (*pos)[3], const float* yaw, bool wrap, const float (*quat)[4] = 0) {
+  for (int s = 0; s < a.num_objects; s++) {
+    const int o = pm[s], d = i - a.obj_qposadr[o];
     if (d < 0 || d >= 7) continue;
-    if (quat) { v = o >= n ? a.park_pose[o][d] : (d < 3 ? pos[o][d] : quat[o][d - 3]); continue; }
-    const float ez = wrap ? rbc_wrap(yaw[o]) : yaw[o];
-    v = o >= n ? a.park_pose[o][d] : (d < 3 ? pos[o][d] : (d == 3 ? cosf(0.5f * ez) : (d == 6 ? sinf(0.5f * ez) : 0.f)));
+    if (quat) { v = s >= n ? a.park_pose[o][d] : (d < 3 ? pos[s][d] : quat[s][d - 3]); continue; }
+    const float ez = wrap ? rbc_wrap(yaw[s]) : yaw[s];
+    v = s >= n ? a.park_pose[o][d] : (d < 3 ? pos[s][d] : (d == 3 ? cosf(0.5f * ez) : (d == 6 ? sinf(0.5f * ez) : 0.f)));
   }
   return v;
 }
@@ -741,6 +780,7 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
     // per-env object counts: the env's first n objects are in use (latched by ra_begin_recipe when an episode ends); without them n = N and every line is the one it was
     int n = N;
     if (a.num_active) { n = a.num_active[e]; n = n < 1 ? 1 : (n > N ? N : n); }
+    for (int i = 0; i < N; i++) F.perm[i] = ra_slot_object(a.obj_perm, e, N, i);      // (the running episode's; ra_begin_recipe latches the next one's)
     if (!regoal_only) a.episode_started[e] = 0;
     if (st != RA_STAGE_LIVE && !regoal_only) ra_stage_step(a, e, st, lf, started, stabilised);      // an env inside the recipe: this step counted
     const float* gy = 0; int gstride = 1;                              // the yaws the new goal starts from, if this step makes one
@@ -790,7 +830,7 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
       const float u = a.soft_mask ? env_u01(a.seed ^ RA_STREAM_GOAL_MASK, a.step, (unsigned)e, 0u) : 0.f;
       a.goal_in_area[(size_t)e * N + lane] = lane < n ? ra_in_area(a, ra_area(a, n), F.gpos[lane], a.soft_mask != 0, u) : 1.f;
     }
-    for (int i = lane; i < nq; i += 64) a.qpos_goal[(size_t)e * nq + i] = ra_qpos_with_objects(a, i, n, bt.qpos[(size_t)e * nq + i], F.gpos, F.gyaw, true, F.recorded ? F.gqe : 0);
+    for (int i = lane; i < nq; i += 64) a.qpos_goal[(size_t)e * nq + i] = ra_qpos_with_objects(a, F.perm, i, n, bt.qpos[(size_t)e * nq + i], F.gpos, F.gyaw, true, F.recorded ? F.gqe : 0);
     if (lane == 0) a.prev_valid[e] = 0;
   }
   __syncthreads();
@@ -801,7 +841,7 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
     for (int i = lane; i < nq; i += 64) {
       float v = m.qpos0[i];
       for (int j = 0; j < 6; j++) if (i == a.arm_qposadr[j]) v = a.arm_start[j];
-      bt.qpos[(size_t)e * nq + i] = ra_qpos_with_objects(a, i, n, v, F.pos, yw, false, F.init_scene ? F.iquat : 0);      // (the parked objects are at rest: qvel is zeroed below)
+      bt.qpos[(size_t)e * nq + i] = ra_qpos_with_objects(a, F.perm, i, n, v, F.pos, yw, false, F.init_scene ? F.iquat : 0);      // (the parked objects are at rest: qvel is zeroed below)
     }
     for (int i = lane; i < m.nv; i += 64) { bt.qvel[(size_t)e * m.nv + i] = 0.f; bt.qacc_warmstart[(size_t)e * m.nv + i] = 0.f; }
     for (int i = lane; i < m.nu; i += 64) bt.ctrl[(size_t)e * m.nu + i] = i < 6 ? a.arm_start[i] : 0.f;
@@ -826,7 +866,7 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
       for (int q = 0; q < 3; q++) so[q] = F.ihalf[lane][q];
     } else if (lane < n) {      // the static observation: bounding box of the yawed object, a random colour
       float* so = a.static_obs + ((size_t)e * N + lane) * 7;
-      ra_yawed_half(a, lane, yw[lane], so[0], so[1]); so[2] = a.obj_half[lane][2];
+      ra_yawed_half(a, F.perm[lane], yw[lane], so[0], so[1]); so[2] = a.obj_half[F.perm[lane]][2];
       for (int q = 0; q < 3; q++) so[3 + q] = env_u01(a.seed, a.step, (unsigned)e, RA_DRAW_COLOURS + 3u * lane + q);
       so[6] = 1.f;
     }
@@ -861,12 +901,13 @@ __global__ void __launch_bounds__(64) ra_param_rows_kernel(RbBatchDev bt, int sc
   if ((a.stages & RA_ROWS_PARK) && a.num_active) {
     // per-env object counts: an unused object's weight cancelled by a force at its centre of mass, from THIS env's mass and gravity rows, and its dofs damped
     const int n = a.num_active[e];
+    // (object subsets: slot o holds world object ra_slot_object(.., o); it is the world objects of the unused SLOTS that are parked)
     for (int i = lane; i < 3 * N; i += 64) {
-      const int o = i / 3, c = i % 3, b = a.obj_body[o];
-      if (o >= n) row[xfrc + 6 * b + c] = -row[mass + b] * row[grav + c];
+      const int o = i / 3, c = i % 3;
+      if (o >= n) { const int b = a.obj_body[ra_slot_object(a.obj_perm, e, N, o)]; row[xfrc + 6 * b + c] = -row[mass + b] * row[grav + c]; }
     }
     for (int i = lane; i < 6 * N; i += 64)
-      if (i / 6 >= n) row[damp + a.obj_dofadr[i / 6] + i % 6] = a.park_damping;
+      if (i / 6 >= n) row[damp + a.obj_dofadr[ra_slot_object(a.obj_perm, e, N, i / 6)] + i % 6] = a.park_damping;
   }
 }
 

@@ -131,10 +131,11 @@ __global__ void __launch_bounds__(RA_ICP_THREADS, 4) ra_icp_kernel(const RbModel
   const float* S = bt.scratch + (size_t)e * m.scratch_words;
   const float *xpos = S + m.off[RB_O_XPOS], *xquat = S + m.off[RB_O_XQUAT];
   const float* goal = a.goal + (size_t)e * N * 7;
+  const int pobj = ra_slot_object(a.obj_perm, e, N, obj);      // object subsets: the world object in this slot (body id, clouds); goal and icp_rel go by slot
   int mgoal = obj;                               // the goal the object is measured against (duplicated-object groups: the post-step kernel's own matching)
   if (a.obj_group) {
     if (tid < 64) {
-      const int mine = ra_group_match(a.obj_group + (size_t)e * N, xpos, a.obj_body, goal, N, n, tid);
+      const int mine = ra_group_match(a.obj_group + (size_t)e * N, xpos, a.obj_body, goal, N, n, tid, tid < N ? ra_slot_object(a.obj_perm, e, N, tid) : tid);
       if (tid < N) F.match[tid] = mine;
     }
     __syncthreads();
@@ -143,15 +144,16 @@ __global__ void __launch_bounds__(RA_ICP_THREADS, 4) ra_icp_kernel(const RbModel
   }
   float* out = a.icp_rel + ((size_t)e * N + obj) * 3;
   // the clouds: capacities are enforced here, whatever the arrays say
-  int ps = a.src_num[obj]; ps = ps > a.src_stride ? a.src_stride : ps; ps = ps > RA_ICP_MAXSRC ? RA_ICP_MAXSRC : ps;
-  int tadr = a.tgt_adr[mgoal], pt = a.tgt_num[mgoal];
+  const int pgoal = mgoal == obj ? pobj : ra_slot_object(a.obj_perm, e, N, mgoal);      // the world object whose cloud the matched goal shows
+  int ps = a.src_num[pobj]; ps = ps > a.src_stride ? a.src_stride : ps; ps = ps > RA_ICP_MAXSRC ? RA_ICP_MAXSRC : ps;
+  int tadr = a.tgt_adr[pgoal], pt = a.tgt_num[pgoal];
   if (tadr < 0 || pt < 1 || ps < 1 || (long long)tadr + pt > (long long)a.tgt_total) {
     if (tid < 3) out[tid] = 0.5f * RBC_PI;
     return;
   }
   const float* tgt = a.tgt + 3 * (size_t)tadr;
   float Ro[9], Rg[9], Q[9];
-  rbc_quat2mat(xquat + 4 * a.obj_body[obj], Ro);
+  rbc_quat2mat(xquat + 4 * a.obj_body[pobj], Ro);
   rbc_quat2mat(goal + 7 * mgoal + 3, Rg);
   for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) Q[3 * i + j] = Rg[i] * Ro[j] + Rg[3 + i] * Ro[3 + j] + Rg[6 + i] * Ro[6 + j];      // R_g^T R_o
   // the thread's two source points in the goal's body frame: as given (orig) and as moved so far (cur)
@@ -161,7 +163,7 @@ __global__ void __launch_bounds__(RA_ICP_THREADS, 4) ra_icp_kernel(const RbModel
     const int p = tid + RA_ICP_THREADS * j;
     have[j] = p < ps;
     float s[3] = {0.f, 0.f, 0.f};
-    if (have[j]) { const float* sp = a.src + 3 * ((size_t)obj * a.src_stride + p); s[0] = sp[0]; s[1] = sp[1]; s[2] = sp[2]; }
+    if (have[j]) { const float* sp = a.src + 3 * ((size_t)pobj * a.src_stride + p); s[0] = sp[0]; s[1] = sp[1]; s[2] = sp[2]; }
     for (int k = 0; k < 3; k++) { orig[j][k] = Q[3 * k] * s[0] + Q[3 * k + 1] * s[1] + Q[3 * k + 2] * s[2]; cur[j][k] = orig[j][k]; nb[j][k] = 0.f; }
   }
   const float inv_n = 1.f / (float)ps;

@@ -1566,6 +1566,7 @@ int ra_env_post_step(rb_batch* b, rb_batch* solver, const ra_post_args* args, vo
   if (a.num_active && a.max_timesteps_per_goal_per_obj < 0) return fail("ra_env_post_step: negative max_timesteps_per_goal_per_obj");
   if (a.rel_dist && (a.obj_group || rgb::ra_kind_is_reach(a.goal_kind))) return fail("ra_env_post_step: rel_dist is computed for distinct objects only (no obj_group, no reach goal)");
   if (a.rel_threshold > 0.f && !a.rel_dist) return fail("ra_env_post_step: rel_threshold needs rel_dist");
+  if (a.obj_perm && !a.num_active) return fail("ra_env_post_step: obj_perm needs num_active (num_objects is the world's count, num_active the slots in use)");
   if (solver) {
     if (solver->dev.B != b->dev.B || solver->device != b->device) return fail("ra_env_post_step: the two batches must have the same size and device");
     const RbModelDev& ds = solver->model->dev;
@@ -1588,6 +1589,7 @@ int ra_env_icp(rb_batch* b, const ra_icp_args* args, void* stream) {
   if (a.tgt_total < 1) return fail("ra_env_icp: empty target cloud");
   if (!(a.error_threshold > 0.f)) return fail("ra_env_icp: error_threshold must be positive");
   if ((long long)b->dev.B * a.num_objects > 0x7fffffffLL) return fail("ra_env_icp: batch x objects exceeds the grid");
+  if (a.obj_perm && !a.num_active) return fail("ra_env_icp: obj_perm needs num_active (num_objects is the world's count, num_active the slots in use)");
   DeviceGuard g(b->device);
   return launch(rgb::ra_icp_kernel, b->dev.B * a.num_objects, RA_ICP_THREADS, 0, sizeof(rgb::RaIcpLds), stream, b->model->dev_copy, b->dev, a);
 }
@@ -1656,6 +1658,12 @@ int ra_env_recipe_step(rb_batch* b, rb_batch* solver, const ra_recipe_args* args
     if (!a.scene_goal && (a.scene_num_goals || a.max_scene_goals || a.advance_goals)) return fail("ra_env_recipe_step: scene_num_goals, max_scene_goals and advance_goals belong to scene_goal");
     if (a.advance_goals < 0 || a.advance_goals > 1) return fail("ra_env_recipe_step: advance_goals is 0 or 1");
   }
+  if (a.obj_perm || a.obj_perm_next) {      // per-env object subsets
+    if (!a.obj_perm || !a.obj_perm_next) return fail("ra_env_recipe_step: obj_perm and obj_perm_next come together");
+    if (!a.num_active) return fail("ra_env_recipe_step: obj_perm needs num_active and num_objects_next (num_objects is the world's count, num_active the slots in use)");
+    if (!rgb::ra_kind_places_on_grid(a.goal_kind)) return fail("ra_env_recipe_step: per-env object subsets (obj_perm) are built for goal kinds 0 and 1");
+    if (a.scene || a.scene_init || a.scene_goal) return fail("ra_env_recipe_step: obj_perm with recorded scenes (a recorded state names world objects)");
+  }
   RbBatchDev sb; memset(&sb, 0, sizeof sb);
   const RbModelDev* ms = nullptr;
   if (solver) {
@@ -1681,6 +1689,7 @@ int ra_env_param_rows(rb_batch* b, const ra_param_rows_args* args, void* stream)
     if (a.obj_body[k] <= 0 || a.obj_body[k] >= d.nbody) return fail("ra_env_param_rows: object body id out of range");
   }
   if (!(fabsf(a.stabilize_damping) <= 3.0e38f) || !(fabsf(a.park_damping) <= 3.0e38f)) return fail("ra_env_param_rows: damping is not finite");
+  if (a.obj_perm && !a.num_active) return fail("ra_env_param_rows: obj_perm needs num_active (the park stage parks the objects of the slots beyond it)");
   // the block and its fields inside the scratch row: every store of the kernel lands inside [blk, blk + words) of the env's own row
   const int blk = d.off[RB_O_PRM], words = d.prm_words;
   const int damp = d.prm_off[RB_P_DOF_DAMPING], xfrc = d.prm_off[RB_P_XFRC], mass = d.prm_off[RB_P_BODY_MASS], grav = d.prm_off[RB_P_GRAVITY];

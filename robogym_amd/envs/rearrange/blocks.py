@@ -39,6 +39,9 @@ Masks of the placement area (`mask_obs_outside_placement_area`; the reference's 
 `goal_placement_mask` and the twelve `masked_*` keys to the packed row (MASK_OBS_KEYS), the goal's mask is written with the goal and stays until the next one
 (DESIGN.md section 3.6c).
 
+Per-env object subsets (`object_pool`): an env uses n of its world's M objects, drawn per env and per episode on the device (`object_perm`: slot -> world object; the
+others parked) -- what lets one compiled mesh world serve 8!/(8-n)! ordered object sets.
+
 Not built for this env: vision, `teleport_to_goal`, per-group materials / colours / scales.
 """
 import ctypes
@@ -69,6 +72,8 @@ REACH_KINDS = ("reach", "det-reach")
 OWN_YAW_KINDS = ("dominos", "attached", "fixed")
 #: the kinds built for per-env object counts (max_num_objects)
 COUNTED_KINDS = ("object_state", "pickandplace", "stack", "train")
+#: the kinds built for per-env object subsets (object_pool)
+POOL_KINDS = ("object_state", "pickandplace")
 #: the kinds the post kernel knows by number (ra_post_args.goal_kind); the others differ in how a goal is made only and are scored as object_state
 POST_KINDS = ("object_state", "pickandplace", "stack", "reach", "det-reach")
 #: AttachedBlockStateGoal's cells (goals/attached_block_state.py:34-49), in steps of one block: a row of 2, a row of 4, a row of 2
@@ -408,6 +413,21 @@ def parking_poses(table_pos, num_objects):
     return out
 
 
+def object_perm_rows(perm, M):
+    """`set_object_perm_next`'s argument, checked, as int32 [M] or [R, M]: every row a permutation of 0..M-1 or all -1 (= sampled by the recipe kernel); `None` or -1:
+    one row of -1.  Anything else raises ValueError."""
+    if perm is None or (np.ndim(perm) == 0 and perm == -1):
+        return np.full(M, -1, dtype=np.int32)
+    c = np.asarray(perm)
+    ok = c.ndim in (1, 2) and c.size > 0 and c.shape[-1] == M and c.dtype.kind in "iuf" and bool(np.all(c == np.round(c)))
+    if ok:
+        r = c.reshape(-1, M).astype(np.int64)
+        ok = bool(np.all(np.all(r == -1, axis=1) | np.all(np.sort(r, axis=1) == np.arange(M), axis=1)))
+    if not ok:
+        raise ValueError("object_pool: object_perm_next %r is not a permutation of 0..%d per row (or a row of -1: sampled)" % (np.asarray(perm).tolist(), M - 1))
+    return c.astype(np.int32)
+
+
 class BatchedBlockRearrangeEnv:
     #: whether the class takes rot_dist_type "icp".  The block envs keep refusing it (boxes: mod90 / mod180 are their exact distances); the mesh envs of
     #: envs/rearrange/ycb.py, the same class on another model, switch it on
@@ -425,7 +445,7 @@ class BatchedBlockRearrangeEnv:
                  stacking_proba: float = 0.0, rot_dist_type: str = "full", randomize_goal_rot: bool = False, model=None, domino_distance_mul: float = 4.0,
                  relative_placements=None, init_quats=None, max_num_objects: Optional[int] = None, icp_max_num_vertices: int = 500, icp_error_threshold: float = 0.15,
                  icp_use_bbox_precheck: bool = False, mask_obs_outside_placement_area: bool = False, soft_mask: bool = False, mask_margin: float = 0.02, initial_states=None, goal_states=None,
-                 advance_goals: bool = False):
+                 advance_goals: bool = False, object_pool: bool = False):
         """`per_env_parameters`: every env carries its own copy of the randomisable model fields (`self.sim.params`, LargeModelSimulation(env_params=True)) -- what
         the reference's simulation randomizers and `stabilize_objects` write into `sim.model`.  On by default (measured cost: 0.7 % of the step,
         profiles/r05_ab_rb_env_params.txt); off: the model's own arrays, no randomizers, no damping change while the objects stabilise.
@@ -482,7 +502,17 @@ class BatchedBlockRearrangeEnv:
         reference's holdout reset sets the objects, not the targets.  `success_threshold` may name `rel_dist` (HoldoutObjectStateGoal.goal_distance: each object's
         distance from where the goal puts it relative to the object with the lowest goal z): `self.rel_dist` [B, N] and `info()["goal_dist"]["rel_dist"]` exist
         whenever there are no duplicate groups, and with the threshold an object counts as achieved only below it too.  Block worlds, goal_kind object_state, no
-        `max_num_objects`."""
+        `max_num_objects`.
+        `object_pool`: every env uses a SUBSET of its world's M objects, drawn per env and per episode -- `num_objects` = n objects, the same
+        count for the whole batch, out of the M of the world (`model` / `main_model`; without one the n-block world, M = n).  `self.object_perm` (int32 [B, M], a
+        permutation of 0..M-1 per env) says which: observation / goal slot i of env e is world object `object_perm[e, i]`, slots i < n are in use, the world objects of
+        the other slots are parked at their own `park_pose` as `max_num_objects` parks unused blocks.  `self.object_perm_next` ([B, M]; `set_object_perm_next` is the
+        checked host setter) is latched when an env's episode begins; a row of -1 (the default) asks the recipe kernel to SAMPLE a permutation (Fisher-Yates, a draw
+        stream of its own), without replacement inside the world's pool.  `object_set()` -> [B, n] world indices (a readback).  `observe()` / `step()` / `reset()`
+        return every per-object key with n slots, the reference's shapes for `num_objects` = n; `qpos` / `qpos_goal` keep the world's nq, and `self.packed` keeps the
+        world's width, M slots per key with zeros behind the n in use.  Needs `device_reset=True` (pipelined, or the synchronous `reset(mask)` / `reset_goals()`, which
+        then run on the device by default; the host route refuses) and per-env parameter rows; goal kinds object_state and pickandplace, object_groups "distinct", no
+        recorded scenes, no `max_num_objects`, no mocap arm."""
         self.B, self.N = int(batch_size), int(num_objects)
         if (initial_states is not None or goal_states is not None) and max_num_objects is not None:
             raise NotImplementedError("max_num_objects (per-env object counts) is not implemented together with initial_states / goal_states (recorded scenes) by the batched rearrange env")
@@ -510,6 +540,31 @@ class BatchedBlockRearrangeEnv:
             if not 1 <= self.N <= M:
                 raise ValueError("num_objects=%d is outside 1..max_num_objects=%d" % (self.N, M))
             self.num_objects_initial, self.N = self.N, M            # (self.N: the world's count, the width of every per-object array)
+        self.object_pool = bool(object_pool)
+        if self.object_pool:
+            refuse = lambda what: NotImplementedError("object_pool (per-env object subsets) is not implemented for %s by the batched rearrange env" % what)
+            if max_num_objects is not None:
+                raise refuse("max_num_objects (per-env object counts: with the pool `num_objects` is the count of the whole batch)")
+            if initial_states is not None or goal_states is not None:
+                raise refuse("initial_states / goal_states (a recorded scene names the world's objects)")
+            if goal_kind not in POOL_KINDS:
+                raise refuse("goal_kind %r (%s)" % (goal_kind, ", ".join(POOL_KINDS)))
+            if not (object_groups is None or (isinstance(object_groups, str) and object_groups == "distinct")):
+                raise refuse("object_groups %r (\"distinct\")" % (object_groups,))
+            if _solver_mode_name(tcp_solver_mode) == "mocap" and _control_mode_name(control_mode) != "joint":
+                raise refuse("tcp_solver_mode=\"mocap\"")
+            if not per_env_parameters:
+                raise refuse("per_env_parameters=False (a parked object is held by its env's xfrc_applied and dof_damping rows)")
+            if not device_reset:
+                raise refuse("device_reset=False (the permutation is latched and sampled by the recipe kernel; the host reset route has no twin of it)")
+            world = model if model is not None else main_model
+            M = self.N if world is None else sum(1 for i in range(_native.RA_MAXOBJ + 1) if "object%d:joint" % i in world.names["joint"])
+            if not 1 <= M <= _native.RA_MAXOBJ:
+                raise ValueError("object_pool: the world has %d objects, outside 1..%d" % (M, _native.RA_MAXOBJ))
+            if not 1 <= self.N <= M:
+                raise ValueError("object_pool: num_objects=%d is outside 1..%d, the world's object count" % (self.N, M))
+            # (the rows and launches of per-env object counts carry the pool: `num_active` holds n for every env, self.N is the world's count)
+            self.num_objects_initial, self.N, self.max_num_objects = self.N, M, M
         if goal_kind not in GOAL_KINDS:
             raise ValueError("goal_kind %r is not one of %s" % (goal_kind, ", ".join(GOAL_KINDS)))
         self.goal_kind_name, self.goal_kind = goal_kind, GOAL_KINDS[goal_kind]
@@ -631,6 +686,11 @@ class BatchedBlockRearrangeEnv:
             self.park_pose = parking_poses(self.table_pos, N)
             self._obj_bodies = torch.tensor([main.name2id("body", "object%d" % i) for i in range(N)], device=dev, dtype=torch.long)
             self._slot = torch.arange(N, device=dev, dtype=torch.int32)
+        # per-env object subsets (object_pool): slot -> world object of the running episode, and the row the next episode latches (-1: sampled by the recipe kernel)
+        self.object_perm = self.object_perm_next = None
+        if self.object_pool:
+            self.object_perm = torch.arange(N, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
+            self.object_perm_next = torch.full((B, N), -1, dtype=torch.int32, device=dev)
         # pipelined resets: an env whose episode ended runs the reset recipe INSIDE the following step calls (the stepper's launches take everybody
         # along; a synchronous reset of a few envs costs ~210 launch pairs at the latency of a full batch).  The recipe's bookkeeping is host numpy (one
         # readback of the flags per step -- a step is 70 ms of GPU work), its physics goes through the same three launches as the live envs': `hold` /
@@ -851,6 +911,8 @@ class BatchedBlockRearrangeEnv:
             a.obj_group = _ptr(self.obj_group)
         if self.max_num_objects is not None:
             a.num_active, a.max_timesteps_per_goal_per_obj = _ptr(self.num_active), int(max_timesteps_per_goal_per_obj)
+        if self.object_pool:
+            a.obj_perm = _ptr(self.object_perm)
         if self.wrapped:
             a.reward_clip = float(reward_clip)
         if self.pipelined:
@@ -886,7 +948,7 @@ class BatchedBlockRearrangeEnv:
         c.src, c.src_stride, c.src_num = _ptr(self.icp_clouds[0]), int(src.shape[1]), _ptr(self.icp_clouds[1])
         c.tgt, c.tgt_total, c.tgt_adr, c.tgt_num = _ptr(self.icp_clouds[2]), int(tgt.shape[0]), _ptr(self.icp_clouds[3]), _ptr(self.icp_clouds[4])
         c.error_threshold = self.icp_error_threshold
-        c.obj_group, c.num_active = a.obj_group, a.num_active
+        c.obj_group, c.num_active, c.obj_perm = a.obj_group, a.num_active, a.obj_perm
         a.icp_rel = _ptr(self.icp_rel)
 
     def _fill_recipe_args(self, starting_seed):
@@ -930,6 +992,8 @@ class BatchedBlockRearrangeEnv:
             for i in range(N):
                 for k in range(7):
                     r.park_pose[i][k] = float(self.park_pose[i, k])
+        if self.object_pool:
+            r.obj_perm, r.obj_perm_next = _ptr(self.object_perm), _ptr(self.object_perm_next)
         if self.num_scenes:
             r.num_scenes, r.scene_next, r.scene = self.num_scenes, _ptr(self.scene_next), _ptr(self.scene)
             if self.scene_init is not None:
@@ -953,6 +1017,8 @@ class BatchedBlockRearrangeEnv:
             a.stabilize_damping, a.park_damping = self.stabilize_object_damping, PARK_DAMPING
             if self.max_num_objects is not None:
                 a.num_active = _ptr(self.num_active)
+            if self.object_pool:
+                a.obj_perm = _ptr(self.object_perm)
         for rz in self.randomizers:      # (their index tables: uploaded here, not inside a reset that must not wait for the device)
             rz.prepare(self.sim)
 
@@ -1090,6 +1156,8 @@ class BatchedBlockRearrangeEnv:
         return lo, lo + np.asarray(size, dtype=np.float64)
 
     def _step_finish(self):
+        if self.object_pool and self.pipelined:      # (the recipe launch below latches the next episode's row where an episode ended: the step's own row, for `info`)
+            self._perm_of_step = self.object_perm.clone()
         if self.pipelined and self.device_reset:
             self._advance_recipes_device()
         elif self.pipelined:
@@ -1110,12 +1178,13 @@ class BatchedBlockRearrangeEnv:
         """Views into the packed row, keys / shapes of `RearrangeEnv._observe_simple` (common/base.py:376-421), with `mask_obs_outside_placement_area` followed by
         MASK_OBS_KEYS (the two masks as [B, N, 1]).  (`packed` / `action_ema`: rows of several envs put together by the caller, envs/rearrange/ycb.py.)"""
         out, o, N = {}, 0, self.N
+        used = self.num_objects_initial if self.object_pool else N      # object_pool: the n slots in use (the row keeps the world's width, zeros behind them)
         packed = self.packed if packed is None else packed
         for k, w in self.obs_keys:
             if isinstance(w, str):
                 n = self.nq if w == "nq" else N * int(w[1])
                 v = packed[:, o:o + n]
-                out[k] = v if w == "nq" else v.view(packed.shape[0], N, int(w[1]))
+                out[k] = v if w == "nq" else v.view(packed.shape[0], N, int(w[1]))[:, :used]
             else:
                 n = w
                 out[k] = packed[:, o:o + n]
@@ -1446,7 +1515,10 @@ class BatchedBlockRearrangeEnv:
         """Which recipe `reset` / `reset_goals` run: None = the device recipe exactly when the env was built with `device_reset` and without `pipelined_reset` (every
         other env keeps the path it had), True needs `device_reset`, False = the host recipe."""
         if on_device is None:
-            return self.device_reset and not self.pipelined
+            return self.device_reset and (not self.pipelined or self.object_pool)
+        if not on_device and self.object_pool:
+            raise NotImplementedError("object_pool (per-env object subsets): the host reset route is not built for it (the permutation is latched and sampled by the "
+                                      "recipe kernel); on_device=None or True")
         if on_device and not self.device_reset:
             raise ValueError("on_device=True needs an env built with device_reset=True (the recipe kernel's rows and arguments are made by the constructor)")
         return bool(on_device)
@@ -1710,9 +1782,31 @@ class BatchedBlockRearrangeEnv:
         dc = d[:, self.obj_dofs]
         d[:, self.obj_dofs] = torch.where(unused.repeat_interleave(6, dim=1), torch.full_like(dc, PARK_DAMPING), dc)
 
+    def set_object_perm_next(self, perm, rows=None):
+        """object_pool: the permutation of the NEXT episode of the envs `rows` (default: every env), checked: [M] or one row per env, each a permutation of 0..M-1 --
+        slot i of the env will be world object perm[i], the first `num_objects` slots in use -- or all -1 = sampled by the recipe kernel; `None` or -1: sample
+        everywhere.  Anything else raises ValueError.  (A row written to `self.object_perm_next` directly, as a curriculum on the device does, is checked where it is
+        latched: one that is no permutation is replaced by a sampled one.)"""
+        if not self.object_pool:
+            raise ValueError("set_object_perm_next: the env was built without object_pool")
+        M = self.N
+        t = torch.as_tensor(object_perm_rows(perm, M), device=self.device)
+        if rows is None:
+            self.object_perm_next.copy_(t.expand(self.B, M) if t.dim() == 1 else t)
+        else:
+            self.object_perm_next[torch.as_tensor(rows, device=self.device, dtype=torch.long)] = t
+
+    def object_set(self):
+        """object_pool: [B, num_objects] the world objects on every env's table, in slot order (a host query: a readback)"""
+        if not self.object_pool:
+            raise ValueError("object_set: the env was built without object_pool")
+        return self.object_perm[:, :self.num_objects_initial].cpu().numpy().astype(np.int64)
+
     def set_num_objects_next(self, counts, rows=None):
         """The object count of the NEXT episode of the envs `rows` (default: every env), checked: an int or one per env, each in 1..max_num_objects.  (Writing
         `self.num_objects_next` directly, as a curriculum on the device does, is clamped to that range where it is latched.)"""
+        if self.object_pool:
+            raise NotImplementedError("set_num_objects_next: object_pool (per-env object subsets) keeps one count for the whole batch; per-env counts together with subsets are not built")
         if self.max_num_objects is None:
             raise ValueError("set_num_objects_next: the env was built without max_num_objects")
         c = np.asarray(counts)

@@ -7,7 +7,9 @@ tracker, contact scans, safety stop -- is the same code here as there, so this e
 the stepper runs it on `rb_step_kernel`'s medium configuration (one wave per env, 56 dofs, 10 envs per CU).
 
 Built: the world with a FIXED set of objects per compiled model (`load_ycb_model`: the reference's `_sample_object_meshes` draw with seed 0 + set index); a new
-object set per episode out of the shipped sets by moving envs between the groups' slots (`GroupedYcbRearrangeEnv`).
+object set per episode out of the shipped sets by moving envs between the groups' slots (`GroupedYcbRearrangeEnv`); with `object_pool=True` an env uses `num_objects`
+= n of its 8-object world's objects, a subset drawn per env and per episode on the device (BatchedBlockRearrangeEnv's `object_perm`) -- 8!/(8-n)!
+ordered sets per shipped world, sampled WITHOUT replacement inside that world (the reference samples with replacement from the whole catalogue).
 Not built: a set sampled from the whole YCB catalogue per episode (the reference re-creates the simulation at every reset, common/base.py:850-856:
 needs per-env geometry rows in the stepper); `normalize_mesh`, object-scale randomisation, the mesh envs' damping change while objects settle."""
 from robogym_amd import _native
@@ -19,14 +21,53 @@ class BatchedYcbRearrangeEnv(BatchedBlockRearrangeEnv):
     ICP_ROT_DIST = True      # rot_dist_type "icp" (envs/rearrange/icp.py, csrc/ra_icp_kernel.h): the distance that sees a mesh object's own symmetries
 
     def __init__(self, batch_size: int, device="cuda:0", num_objects: int = 8, **kw):
-        model = kw.pop("main_model", None) or load_ycb_model(num_objects)
+        # (object_pool: `num_objects` of the shipped 8-object world's objects per env)
+        model = kw.pop("main_model", None) or load_ycb_model(POOL_WORLD_OBJECTS if kw.get("object_pool") else num_objects)
         super().__init__(batch_size, device=device, num_objects=num_objects, main_model=model, **kw)
         self.object_names = list(model.names.get("object_mesh", []))
 
     def info(self):
         out = super().info()
         out["object_names"] = self.object_names       # YcbRearrangeEnv._get_simulation_info (ycb.py:86-90): the mesh name of every object
+        if self.object_pool:      # per env: the objects on its table, in slot order, of the step this follows (resolved when looked at: a readback)
+            perm = getattr(self, "_perm_of_step", None)
+            out["object_names"] = _LazyPoolNames([self.object_names], None, (self.object_perm.clone() if perm is None else perm)[:, :self.num_objects_initial], self.B)
         return out
+
+    def _reset_device(self, mask):
+        self._perm_of_step = None      # (the rows of a step before the reset: `info` names the new episodes' objects)
+        return super()._reset_device(mask)
+
+
+#: the object count of the shipped worlds an `object_pool` env draws its subsets from
+POOL_WORLD_OBJECTS = 8
+
+
+class _LazyPoolNames:
+    """info["object_names"] with object_pool: per env the mesh names of the objects on its table, in slot order -- names_of_group[group][perm[slot row][i]] --, resolved
+    (one readback) when it is looked at.  `slot_dev`: env -> physics slot (None: env i is row i of the one group), `perm_dev` [slots, n] in slot order, `b` rows per group."""
+
+    def __init__(self, names_of_group, slot_dev, perm_dev, b):
+        self._g, self._s, self._p, self._b, self._v = names_of_group, slot_dev, perm_dev, b, None
+
+    def _list(self):
+        if self._v is None:
+            perm = self._p.cpu().numpy()
+            slots = range(perm.shape[0]) if self._s is None else [int(x) for x in self._s.cpu().numpy()]
+            self._v = [[self._g[s // self._b][int(p)] for p in perm[s]] for s in slots]
+        return self._v
+
+    def __len__(self):
+        return int(self._p.shape[0])
+
+    def __getitem__(self, i):
+        return self._list()[i]
+
+    def __iter__(self):
+        return iter(self._list())
+
+    def __eq__(self, other):
+        return list(self) == [list(x) for x in other]
 
 
 class _LazyNames:
@@ -77,7 +118,11 @@ class GroupedYcbRearrangeEnv:
         assert batch_size % K == 0, "batch_size must be a multiple of the number of object sets"
         self.B, self.K, self.b = int(batch_size), K, int(batch_size) // K
         self.object_sets = tuple(int(k) for k in object_sets)
-        self.groups = [BatchedYcbRearrangeEnv(self.b, device=device, main_model=load_ycb_model(kw.get("num_objects", 8), set_index=k), starting_seed=starting_seed + 1000 * i, **kw)
+        # object_pool: every group draws per-env subsets of `num_objects` objects out of its own 8-object set; a permutation belongs to the physics SLOT (it is latched
+        # and sampled when that slot's recipe begins), the slots are traded as they are
+        self.object_pool = bool(kw.get("object_pool"))
+        world_objects = POOL_WORLD_OBJECTS if self.object_pool else kw.get("num_objects", 8)
+        self.groups = [BatchedYcbRearrangeEnv(self.b, device=device, main_model=load_ycb_model(world_objects, set_index=k), starting_seed=starting_seed + 1000 * i, **kw)
                        for i, k in enumerate(self.object_sets)]
         g0 = self.groups[0]
         # every group's physics phase as ONE launch when the groups' kernels match (same batch size by construction; same one-wave configuration) and there are <= 8
@@ -183,6 +228,37 @@ class GroupedYcbRearrangeEnv:
     def _names(self):
         return [self.object_names[s // self.b] for s in self._slot]
 
+    def _pool_names(self, slot_dev, perm=None):
+        """object_pool: the per-env names (lazy) for the env -> slot table `slot_dev` and the groups' rows `perm` (default: as they are now)"""
+        import torch
+
+        perm = torch.cat([g.object_perm for g in self.groups]) if perm is None else perm
+        return _LazyPoolNames(self.object_names, slot_dev, perm[:, :self.groups[0].num_objects_initial], self.b)
+
+    def set_object_perm_next(self, perm, rows=None):
+        """object_pool: `BatchedBlockRearrangeEnv.set_object_perm_next` for the envs `rows` of the batch (default: all): the rows go to the physics slots those envs
+        hold NOW (a permutation belongs to the slot: it is latched when that slot's recipe begins, whichever env the slot then serves).  Checked; no readback."""
+        import torch
+
+        if not self.object_pool:
+            raise ValueError("set_object_perm_next: the env was built without object_pool")
+        from robogym_amd.envs.rearrange.blocks import object_perm_rows
+
+        t = torch.as_tensor(object_perm_rows(perm, self.N), device=self.device)
+        idx = torch.arange(self.B, device=self.device) if rows is None else torch.as_tensor(rows, device=self.device, dtype=torch.long)
+        full = torch.cat([g.object_perm_next for g in self.groups])
+        full[self._slot_dev[idx]] = t          # ([M] goes to every row, [R, M] row by row)
+        for i, g in enumerate(self.groups):
+            g.object_perm_next.copy_(full[i * self.b:(i + 1) * self.b])
+
+    def object_set(self):
+        """object_pool: [B, num_objects] the objects on every env's table as indices into its set's eight (`object_set_of_env()` names the set); a readback"""
+        import torch
+
+        if not self.object_pool:
+            raise ValueError("object_set: the env was built without object_pool")
+        return self._to_envs(torch.cat([g.object_perm for g in self.groups]))[:, :self.groups[0].num_objects_initial].cpu().numpy().astype("int64")
+
     def reset(self, mask=None, on_device=None):
         """The groups' host recipe (`on_device` None / False).  The synchronous device recipe of the groups (BatchedBlockRearrangeEnv.reset(on_device=True)) is not
         built for this env: handing the slots out again reads the mask back."""
@@ -194,7 +270,8 @@ class GroupedYcbRearrangeEnv:
         envs = np.arange(self.B) if mask is None else np.nonzero(mask.cpu().numpy())[0]
         self._reassign(envs)                                          # a reset is a new episode: a new object set with it
         smask = None if mask is None else self._to_slots(mask)
-        self._each(lambda i, g: g.reset(None if smask is None else smask[i * self.b:(i + 1) * self.b], on_device=False))
+        # (object_pool: the groups' device recipe -- the permutation is latched and sampled by the recipe kernel, the host route has no twin of it)
+        self._each(lambda i, g: g.reset(None if smask is None else smask[i * self.b:(i + 1) * self.b], on_device=True if self.object_pool else False))
         return self._observation()
 
     def step(self, actions):
@@ -216,21 +293,26 @@ class GroupedYcbRearrangeEnv:
                     _native.check(L, L.rb_multi_launch(st), "rb_multi_launch")
             for g in self.groups:
                 g._step_launch(None, phase="post")
+            perm_of_step = torch.cat([g.object_perm for g in self.groups]) if self.object_pool else None      # (a copy: the recipe launches latch the next episodes' rows)
             outs = [g._step_finish() for g in self.groups]
         else:
             self._each(lambda i, g: g._step_launch(sact[i * b:(i + 1) * b].contiguous()))           # every group's three launches are queued ...
+            perm_of_step = None
             outs = self._each(lambda i, g: g._step_finish())                                        # ... before any group's flags are read back
+            if self.object_pool:
+                perm_of_step = torch.cat([g._perm_of_step for g in self.groups])
         obs = self._observation()
         reward, done = self._to_envs(torch.cat([o[1] for o in outs])), self._to_envs(torch.cat([o[2] for o in outs]))
         info = {k: self._to_envs(torch.cat([o[3][k] for o in outs])) for k in outs[0][3] if torch.is_tensor(outs[0][3][k])}
         if self._device_trade:
             # the names and the table of THIS step are resolved on request (a readback); nothing in a step call waits for the GPU
             snap = self._slot_dev.clone()
-            info["object_names"] = _LazyNames(self.object_names, snap, self.b)
+            info["object_names"] = self._pool_names(snap, perm_of_step) if self.object_pool else _LazyNames(self.object_names, snap, self.b)
             self._slot_of_step_dev = snap
             self._trade_slots_device()
         else:
-            info["object_names"] = self._names()            # (of the episode this step belonged to: the terminal step still names the set that just ended)
+            # (of the episode this step belonged to: the terminal step still names the set that just ended)
+            info["object_names"] = self._pool_names(self._slot_dev.clone(), perm_of_step) if self.object_pool else self._names()
             self._slot_of_step = self._slot.copy()
             self._trade_slots()
         return obs, reward, done, info
@@ -294,12 +376,17 @@ class GroupedYcbRearrangeEnv:
 
 
 def make_env(batch_size: int = 4096, device="cuda:0", parameters=None, constants=None, starting_seed: int = 0, apply_wrappers: bool = True, **kw):
-    """`YcbRearrangeEnv.build` surface (ycb.py:96) for the batched env; accepts what envs/rearrange/blocks.py `make_env` accepts."""
+    """`YcbRearrangeEnv.build` surface (ycb.py:96) for the batched env; accepts what envs/rearrange/blocks.py `make_env` accepts.  `object_pool=True` (with
+    `device_reset=True`): `simulation_params.num_objects` = n objects per env, a subset of the shipped 8-object world's drawn per env and episode (DESIGN.md §3.7a);
+    `info()["object_names"]` is then per env, the n names in slot order."""
     from robogym_amd.envs.rearrange.blocks import make_env_args
 
     parameters, constants = dict(parameters or {}), dict(constants or {})
     if parameters.pop("mesh_names", None) is not None or constants.get("normalize_mesh"):
         raise NotImplementedError("mesh_names / normalize_mesh: the shipped models hold fixed object sets")
+    if "max_num_objects" in parameters.get("simulation_params", {}) and kw.get("object_pool"):
+        raise NotImplementedError("object_pool (per-env object subsets) is not implemented together with parameters.simulation_params.max_num_objects: with the pool "
+                                  "`num_objects` is the count of the whole batch")
     if "max_num_objects" in parameters.get("simulation_params", {}):
         raise NotImplementedError("parameters.simulation_params.max_num_objects (per-env object counts) is not implemented for the ycb worlds (their objects differ: "
                                   "a prefix of a set is no set of its own); rearrange/blocks and its tasks take it")
