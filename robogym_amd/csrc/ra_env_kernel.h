@@ -26,8 +26,8 @@ __host__ __device__ inline bool ra_kind_uses_grip_site(int kind) { return kind =
 __host__ __device__ inline bool ra_kind_places_on_grid(int kind) { return kind == RA_GOAL_OBJECT_STATE || kind == RA_GOAL_PICKANDPLACE; }
 __host__ __device__ inline bool ra_kind_is_counted(int kind) { return ra_kind_places_on_grid(kind) || kind == RA_GOAL_STACK || kind == RA_GOAL_TRAIN; }   // built for per-env object counts
 // the draw streams env_u01(seed ^ stream, step, env, k) (the recipe's own is the plain seed), and the first draw index k of the sections that share a stream
-enum : unsigned { RA_STREAM_GOAL = 0x9E3779B9u, RA_STREAM_GOAL_YAW = 0xC2B2AE35u, RA_STREAM_GROUPS = 0x85EBCA6Bu, RA_STREAM_OBJ_MASK = 0xA54FF53Au, RA_STREAM_GOAL_MASK = 0x3C6EF372u, RA_STREAM_OBJECT_SET = 0x27D4EB2Fu,
-                  RA_DRAW_COLOURS = 500u, RA_DRAW_PLACEMENT = 1000u, RA_DRAW_GROUPS = 3000u };
+enum : unsigned { RA_STREAM_GOAL = 0x9E3779B9u, RA_STREAM_GOAL_YAW = 0xC2B2AE35u, RA_STREAM_GROUPS = 0x85EBCA6Bu, RA_STREAM_OBJ_MASK = 0xA54FF53Au, RA_STREAM_GOAL_MASK = 0x3C6EF372u, RA_STREAM_OBJECT_SET = 0x27D4EB2Fu, RA_STREAM_MATERIAL = 0x165667B1u,
+                  RA_DRAW_COLOURS = 500u, RA_DRAW_PLACEMENT = 1000u, RA_DRAW_GROUPS = 3000u, RA_DRAW_MATERIAL = 4000u };
 // per-env object subsets (ra_post_args.obj_perm, include/rgstep.h): the world object in slot `slot` < N of env e -- the slot itself without a row, and for an entry
 // that names no object.  One load per lane (or per workgroup into LDS: ra_recipe_kernel); every table of the WORLD's objects (body ids, addresses, boxes, parking
 // poses, clouds) is read at what this returns, every per-env row (goals, yaws, static observation, observation keys) at the slot.
@@ -873,11 +873,75 @@ __global__ void __launch_bounds__(64) ra_recipe_kernel(const RbModelDev* mp, RbB
   }
 }
 
+// Stage RA_ROWS_MATERIAL of ra_param_rows_kernel for an env whose episode ended (every lane of its wave calls it): the reference's per-episode material of every
+// object group (RearrangeEnv._sample_object_materials, common/base.py:575-585: random_state.choice(material_names, size=num_groups); the rebuilt world then carries
+// the material's attributes on the object's geoms and free joint, simulation/base.py set_objects_attrs) as writes to the env's parameter rows, which hold
+// block_default at this point.  Lane s < N settles slot s -- the pin, or a draw of RA_STREAM_MATERIAL from RA_DRAW_MATERIAL + s, a stream nothing else reads --;
+// the slots of a group take their lowest member's; then slot after slot (uniform over the wave) the first lanes write the words of that slot's world object: in
+// both phases a word belongs to one (geom | body | dof, component) and so to one lane.  A table row of zeros writes nothing.
+// _invweight0: the object is a free body and a kinematic tree of its own, so mj_setConst's inverse of the inertia matrix is the 6 x 6 one of that body alone.  With
+// principal inertias I_k, mass m, armature arm and the centre of mass at r from the joint: body_invweight0 = (1 / (m + arm), mean_k 1 / (I_k + arm)), the
+// rotational dofs the latter, the translational dofs 1 / (m + arm) + (1 / 3) sum_k |r x axis_k|^2 / (I_k + arm) -- exact where arm = 0 (every shipped material
+// that writes the joint) or r = 0 (boxes); obj_lever2 carries |r x axis_k|^2.
+__device__ inline void ra_material_rows(const RaParamRowsArgs& a, float* row, int blk, int e, int lane) {
+  const int N = a.num_objects;
+  int m = 0;
+  if (lane < N) {
+    const int pin = a.obj_material_next[(size_t)e * N + lane];
+    if ((unsigned)pin < (unsigned)a.num_materials) m = pin;
+    else {
+      const float u = env_u01(a.mat_seed ^ RA_STREAM_MATERIAL, a.mat_step, (unsigned)e, RA_DRAW_MATERIAL + (unsigned)lane);
+      int c = (int)(u * (float)a.num_choice);
+      m = a.mat_choice[c < a.num_choice ? c : a.num_choice - 1];
+    }
+  }
+  int lead = lane;      // the lowest slot of this slot's group (an unused slot, id -1, is its own)
+  if (a.obj_group && lane < N) {
+    const int* grp = a.obj_group + (size_t)e * N;
+    const int g = grp[lane];
+    if (g >= 0) for (int j = lane - 1; j >= 0; j--) if (grp[j] == g) lead = j;
+  }
+  m = __shfl(m, lead);
+  if (lane < N) a.obj_material[(size_t)e * N + lane] = m;
+  const int* off = a.mat_off;      // friction, solref, solimp, mass, inertia, armature, dof_invweight0, body_invweight0
+  for (int s = 0; s < N; s++) {
+    const int ms = __shfl(m, s);
+    const float* t = a.mat_table + (size_t)ms * RA_MAT_WORDS;
+    const int bits = (int)t[0];
+    if (!bits) continue;                                               // (uniform: the compiled world's own material, the rows stay as the restore left them)
+    const int w = ra_slot_object(a.obj_perm, e, N, s), body = a.obj_body[w], dof = a.obj_dofadr[w];
+    for (int i = lane; i < 8 * a.obj_geomnum[w]; i += 64) {            // the object's geoms: friction 3 | solref 2 | solimp 3 words each
+      const int g = a.obj_geomadr[w] + i / 8, c = i % 8;
+      if (c < 3) { if (bits & RA_MAT_FRICTION) row[off[0] + 3 * g + c] = t[2 + c]; }
+      else if (c < 5) { if (bits & RA_MAT_SOLREF) row[off[1] + 2 * g + c - 3] = t[5 + c - 3]; }
+      else if (bits & RA_MAT_SOLIMP) row[off[2] + 5 * g + c - 5] = t[7 + c - 5];
+    }
+    if (lane < 18) {                                                   // the body: mass | inertia 3 | armature 6 | dof_invweight0 6 | body_invweight0 2
+      const float* def = a.block_default - blk;
+      const float k = (bits & RA_MAT_MASS) ? t[1] : 1.f;
+      const float arm = (bits & RA_MAT_JOINT) ? t[11] : def[off[5] + dof];
+      const float mass = def[off[3] + body] * k;
+      float I[3], rot = 0.f, lev = 0.f;
+      for (int q = 0; q < 3; q++) { I[q] = def[off[4] + 3 * body + q] * k; const float inv = 1.f / (I[q] + arm); rot += inv; lev += a.obj_lever2[w][q] * inv; }
+      rot *= 1.f / 3.f;
+      const float tra = 1.f / (mass + arm);
+      const bool weights = bits & (RA_MAT_MASS | RA_MAT_JOINT);
+      if (lane == 0) { if (bits & RA_MAT_MASS) row[off[3] + body] = mass; }
+      else if (lane < 4) { if (bits & RA_MAT_MASS) row[off[4] + 3 * body + lane - 1] = I[lane - 1]; }
+      else if (lane < 10) { if (bits & RA_MAT_JOINT) row[off[5] + dof + lane - 4] = arm; }
+      else if (lane < 16) { if (weights) row[off[6] + dof + lane - 10] = lane < 13 ? tra + lev * (1.f / 3.f) : rot; }
+      else if (weights) row[off[7] + 2 * body + lane - 16] = lane == 16 ? tra : rot;
+    }
+  }
+  __syncthreads();
+}
+
 // The per-env parameter rows after a recipe launch, on the rows of its masks only (ra_param_rows_args, include/rgstep_sync_reset.h): the device route's only
 // implementation, pipelined and synchronous alike.  Its twin on the host route: BatchedBlockRearrangeEnv's `_param_defaults` restore (_begin_episode_state),
 // _set_object_damping and _apply_parking, in that order (tests/test_rearrange_sync_reset.py compares the two).  One wave per env; an env outside `active`, or with none of its three mask
 // bytes set, is left after three byte loads.  `blk`: word offset of the parameter block in the scratch row, `words` its length; `damp` / `xfrc` / `mass` / `grav`: the
 // fields' word offsets in the row (RbModelDev.prm_off).  Plain vector stores; every store of a phase goes to a word no other lane writes in that phase.
+// Order: RESTORE, MATERIAL (ra_material_rows above, requested with its table only), PARK -- which reads the env's own mass row and so cancels the material's weight.
 __global__ void __launch_bounds__(64) ra_param_rows_kernel(RbBatchDev bt, int scratch_words, int blk, int words, int damp, int xfrc, int mass, int grav, RaParamRowsArgs a) {
   const int e = blockIdx.x, lane = threadIdx.x;
   if (e >= bt.B) return;
@@ -886,18 +950,27 @@ __global__ void __launch_bounds__(64) ra_param_rows_kernel(RbBatchDev bt, int sc
   if (!(ended | stabilised | started)) return;                         // (all three uniform over the workgroup)
   float* row = bt.scratch + (size_t)e * scratch_words;
   const int N = a.num_objects;
+  const bool materials = (a.stages & RA_ROWS_MATERIAL) && a.mat_table;
   if (a.stages & RA_ROWS_RESTORE) {
     // _recreate_sim's fresh model for an episode that ended: the whole block (xfrc_applied among it: zero) back at the model's values
     if (ended) for (int i = lane; i < words; i += 64) row[blk + i] = a.block_default[i];
     __syncthreads();
-    // stabilize_objects (common/utils.py:76-92): the objects' dof damping lowered while they settle, the model's own again afterwards
+    // stabilize_objects (common/utils.py:76-92): the objects' dof damping lowered while they settle, the model's own again afterwards -- with materials the
+    // damping of the object's material (set_object_damping saves and restores what the rebuilt world holds): slot by slot then, obj_material being a row of slots
     if (ended || stabilised)
       for (int i = lane; i < 6 * N; i += 64) {
-        const int dof = a.obj_dofadr[i / 6] + i % 6;
-        row[damp + dof] = ended ? a.stabilize_damping : a.block_default[damp - blk + dof];
+        const int w = materials ? ra_slot_object(a.obj_perm, e, N, i / 6) : i / 6;
+        const int dof = a.obj_dofadr[w] + i % 6;
+        float own = a.block_default[damp - blk + dof];
+        if (materials && !ended) {
+          const int m = a.obj_material[(size_t)e * N + i / 6];
+          if ((unsigned)m < (unsigned)a.num_materials && ((int)a.mat_table[m * RA_MAT_WORDS] & RA_MAT_JOINT)) own = a.mat_table[m * RA_MAT_WORDS + 10];
+        }
+        row[damp + dof] = ended ? a.stabilize_damping : own;
       }
     __syncthreads();
   }
+  if (materials && ended) ra_material_rows(a, row, blk, e, lane);
   if ((a.stages & RA_ROWS_PARK) && a.num_active) {
     // per-env object counts: an unused object's weight cancelled by a force at its centre of mass, from THIS env's mass and gravity rows, and its dofs damped
     const int n = a.num_active[e];

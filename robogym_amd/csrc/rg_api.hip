@@ -1683,7 +1683,7 @@ int ra_env_param_rows(rb_batch* b, const ra_param_rows_args* args, void* stream)
   if (!d.prm_on) return fail("ra_env_param_rows: the batch has no per-env parameter rows (rb_model_enable_env_params)");
   if (!a.ended || !a.stabilised || !a.episode_started || !a.block_default) return fail("ra_env_param_rows: a required array is NULL");
   if (a.num_objects < 1 || a.num_objects > RA_MAXOBJ) return fail("ra_env_param_rows: num_objects out of range");
-  if (a.stages < 1 || a.stages > (RA_ROWS_RESTORE | RA_ROWS_PARK)) return fail("ra_env_param_rows: stages is RA_ROWS_RESTORE, RA_ROWS_PARK or both");
+  if (a.stages < 1 || a.stages > (RA_ROWS_RESTORE | RA_ROWS_PARK | RA_ROWS_MATERIAL)) return fail("ra_env_param_rows: stages is a sum of RA_ROWS_RESTORE, RA_ROWS_PARK and RA_ROWS_MATERIAL");
   for (int k = 0; k < a.num_objects; k++) {
     if (a.obj_dofadr[k] < 0 || a.obj_dofadr[k] + 6 > d.nv) return fail("ra_env_param_rows: object dof address out of range");
     if (a.obj_body[k] <= 0 || a.obj_body[k] >= d.nbody) return fail("ra_env_param_rows: object body id out of range");
@@ -1696,6 +1696,24 @@ int ra_env_param_rows(rb_batch* b, const ra_param_rows_args* args, void* stream)
   if (blk < 0 || words < 1 || blk + words > d.scratch_words) return fail("ra_env_param_rows: parameter block outside the scratch row");
   if (damp < blk || damp + d.nv > blk + words || xfrc < blk || xfrc + 6 * d.nbody > blk + words || mass < blk || mass + d.nbody > blk + words || grav < blk || grav + 3 > blk + words)
     return fail("ra_env_param_rows: a parameter field lies outside the block");
+  if ((a.stages & RA_ROWS_MATERIAL) && !a.mat_table) return fail("ra_env_param_rows: RA_ROWS_MATERIAL needs mat_table (the material stage without its table)");
+  if (a.mat_table) {      // per-object materials: every index the stage reads, every word it writes
+    if (a.num_materials < 1 || a.num_materials > 65536) return fail("ra_env_param_rows: num_materials out of range (1..65536)");
+    if (a.num_choice < 1 || a.num_choice > RA_MAT_MAXCHOICE) return fail("ra_env_param_rows: num_choice out of range (1..RA_MAT_MAXCHOICE)");
+    for (int k = 0; k < a.num_choice; k++)
+      if (a.mat_choice[k] < 0 || a.mat_choice[k] >= a.num_materials) return fail("ra_env_param_rows: mat_choice names a material index out of range");
+    if (!a.obj_material || !a.obj_material_next) return fail("ra_env_param_rows: mat_table needs obj_material and obj_material_next");
+    for (int k = 0; k < a.num_objects; k++) {
+      if (a.obj_geomadr[k] < 0 || a.obj_geomnum[k] < 0 || a.obj_geomnum[k] > d.ngeom || a.obj_geomadr[k] > d.ngeom - a.obj_geomnum[k]) return fail("ra_env_param_rows: an object's geom range lies outside the model's geoms");
+      for (int c = 0; c < 3; c++) if (!(a.obj_lever2[k][c] >= 0.f) || !(a.obj_lever2[k][c] <= 3.0e38f)) return fail("ra_env_param_rows: obj_lever2 is not a finite square");
+    }
+    // the fields' offsets are the model's own (rb_prm_layout), which the block's construction places inside [blk, blk + words) with the lengths the stage assumes
+    static const int field[RA_MAT_NOFF] = {RB_P_GEOM_FRICTION, RB_P_GEOM_SOLREF, RB_P_GEOM_SOLIMP, RB_P_BODY_MASS, RB_P_BODY_INERTIA, RB_P_DOF_ARMATURE, RB_P_DOF_INVWEIGHT0, RB_P_BODY_INVWEIGHT0};
+    const int len[RA_MAT_NOFF] = {3 * d.ngeom, 2 * d.ngeom, 5 * d.ngeom, d.nbody, 3 * d.nbody, d.nv, d.nv, 2 * d.nbody};
+    for (int k = 0; k < RA_MAT_NOFF; k++)
+      if (a.mat_off[k] != d.prm_off[field[k]] || b->model->prm_len[field[k]] != len[k] || a.mat_off[k] < blk || a.mat_off[k] + len[k] > blk + words)
+        return fail("ra_env_param_rows: mat_off is not the model's layout of geom_friction, geom_solref, geom_solimp, body_mass, body_inertia, dof_armature, dof_invweight0, body_invweight0 (rb_prm_layout)");
+  }
   DeviceGuard g(b->device);
   return launch(rgb::ra_param_rows_kernel, b->dev.B, 64, 0, 0, stream, b->dev, d.scratch_words, blk, words, damp, xfrc, mass, grav, a);
 }

@@ -42,7 +42,11 @@ Masks of the placement area (`mask_obs_outside_placement_area`; the reference's 
 Per-env object subsets (`object_pool`): an env uses n of its world's M objects, drawn per env and per episode on the device (`object_perm`: slot -> world object; the
 others parked) -- what lets one compiled mesh world serve 8!/(8-n)! ordered object sets.
 
-Not built for this env: vision, `teleport_to_goal`, per-group materials / colours / scales.
+Per-object materials (`material_names`; the reference's `RearrangeEnvParameters.material_names`, common/base.py:206-210, 575-585): every episode draws one of the
+named materials (envs/rearrange/materials.py) per object -- per group with `object_groups` -- on the device and writes its density, friction, solref, solimp and
+joint armature / damping into the env's parameter rows (`object_material`).  The default list, `["default"]`, is the compiled worlds' own material.
+
+Not built for this env: vision, `teleport_to_goal`, per-group `material_args` dictionaries / colours / scales.
 """
 import ctypes
 import os
@@ -52,6 +56,7 @@ import numpy as np
 import torch
 
 from robogym_amd import _native
+from robogym_amd.envs.rearrange import materials
 from robogym_amd.envs.rearrange.xml import load_blocks_model, load_solver_model, object_bounding_boxes
 from robogym_amd.mujoco.large_simulation import LargeModelSimulation
 
@@ -445,7 +450,7 @@ class BatchedBlockRearrangeEnv:
                  stacking_proba: float = 0.0, rot_dist_type: str = "full", randomize_goal_rot: bool = False, model=None, domino_distance_mul: float = 4.0,
                  relative_placements=None, init_quats=None, max_num_objects: Optional[int] = None, icp_max_num_vertices: int = 500, icp_error_threshold: float = 0.15,
                  icp_use_bbox_precheck: bool = False, mask_obs_outside_placement_area: bool = False, soft_mask: bool = False, mask_margin: float = 0.02, initial_states=None, goal_states=None,
-                 advance_goals: bool = False, object_pool: bool = False):
+                 advance_goals: bool = False, object_pool: bool = False, material_names=("default",)):
         """`per_env_parameters`: every env carries its own copy of the randomisable model fields (`self.sim.params`, LargeModelSimulation(env_params=True)) -- what
         the reference's simulation randomizers and `stabilize_objects` write into `sim.model`.  On by default (measured cost: 0.7 % of the step,
         profiles/r05_ab_rb_env_params.txt); off: the model's own arrays, no randomizers, no damping change while the objects stabilise.
@@ -512,8 +517,26 @@ class BatchedBlockRearrangeEnv:
         return every per-object key with n slots, the reference's shapes for `num_objects` = n; `qpos` / `qpos_goal` keep the world's nq, and `self.packed` keeps the
         world's width, M slots per key with zeros behind the n in use.  Needs `device_reset=True` (pipelined, or the synchronous `reset(mask)` / `reset_goals()`, which
         then run on the device by default; the host route refuses) and per-env parameter rows; goal kinds object_state and pickandplace, object_groups "distinct", no
-        recorded scenes, no `max_num_objects`, no mocap arm."""
+        recorded scenes, no `max_num_objects`, no mocap arm.
+        `material_names`: the materials an object may have, with multiplicity (`None` or an empty list: all five of
+        envs/rearrange/materials.py).  A list of nothing but "default" (the default) is the compiled worlds' own material: no row, no pointer, no stage.  Any other
+        list: where an env's episode ends, ra_param_rows_kernel draws one material per slot (per group with `object_groups`; a stream of its own) or takes the
+        pin `self.object_material_next` ([B, N] int32 indices into materials.MATERIAL_NAMES, -1 = drawn; `set_object_material_next` is the checked host setter; read
+        at every episode start, never cleared), writes `self.object_material` ([B, N] int32, device) and the material's rows on top of the restored block: the
+        friction / solref / solimp of the object's geoms, body mass and inertia times density / 1000, the six dofs' armature and both `_invweight0` rows;
+        `stabilize_objects` restores the material's damping.  The randomizers of geom_friction, geom_solref, geom_solimp, body_mass and body_inertia then start from
+        the env's rows as they stand (block + material) instead of the model's.  Needs per-env parameter rows and `device_reset=True` (the host route refuses)."""
         self.B, self.N = int(batch_size), int(num_objects)
+        self.material_names = materials.material_list(material_names)
+        self.materials_on = not materials.is_default_only(self.material_names)
+        if self.materials_on:
+            if not per_env_parameters:
+                raise ValueError("material_names=%r needs per_env_parameters=True (a material is written into the env's parameter rows)" % (self.material_names,))
+            if not device_reset:
+                raise NotImplementedError("material_names=%r needs device_reset=True: the materials are drawn and written by the device route's parameter-row launch; the host "
+                                          "reset route is not built for them" % (self.material_names,))
+            if len(self.material_names) > _native.RA_MAT_MAXCHOICE:
+                raise ValueError("material_names: %d entries, at most %d (multiplicity is weight)" % (len(self.material_names), _native.RA_MAT_MAXCHOICE))
         if (initial_states is not None or goal_states is not None) and max_num_objects is not None:
             raise NotImplementedError("max_num_objects (per-env object counts) is not implemented together with initial_states / goal_states (recorded scenes) by the batched rearrange env")
         if (initial_states is not None or goal_states is not None) and (model is not None or main_model is not None or self.ICP_ROT_DIST):
@@ -687,6 +710,7 @@ class BatchedBlockRearrangeEnv:
             self._obj_bodies = torch.tensor([main.name2id("body", "object%d" % i) for i in range(N)], device=dev, dtype=torch.long)
             self._slot = torch.arange(N, device=dev, dtype=torch.int32)
         # per-env object subsets (object_pool): slot -> world object of the running episode, and the row the next episode latches (-1: sampled by the recipe kernel)
+        self.object_material = self.object_material_next = None      # per-object materials: made with the parameter-row launch's arguments (_fill_material_args)
         self.object_perm = self.object_perm_next = None
         if self.object_pool:
             self.object_perm = torch.arange(N, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
@@ -1019,8 +1043,39 @@ class BatchedBlockRearrangeEnv:
                 a.num_active = _ptr(self.num_active)
             if self.object_pool:
                 a.obj_perm = _ptr(self.object_perm)
+            if self.materials_on:
+                self._fill_material_args(a)
         for rz in self.randomizers:      # (their index tables: uploaded here, not inside a reset that must not wait for the device)
             rz.prepare(self.sim)
+
+    def _fill_material_args(self, a):
+        """Per-object materials: the table, the list a draw picks from, the rows `object_material` / `object_material_next`, and what the stage needs of the model --
+        every object's geoms, the lever of its centre of mass, the offsets of the fields it writes (ra_param_rows_args, include/rgstep_sync_reset.h)."""
+        dev, B, N, A = self.device, self.B, self.N, self.model.arrays
+        self.material_table = torch.tensor(materials.material_table(), device=dev).contiguous()
+        self.object_material = torch.full((B, N), materials.MATERIAL_NAMES.index("default"), dtype=torch.int32, device=dev)
+        self.object_material_next = torch.full((B, N), -1, dtype=torch.int32, device=dev)
+        a.mat_table, a.num_materials, a.num_choice = _ptr(self.material_table), len(materials.MATERIAL_NAMES), len(self.material_names)
+        for k, name in enumerate(self.material_names):
+            a.mat_choice[k] = materials.MATERIAL_NAMES.index(name)
+        a.obj_material, a.obj_material_next, a.mat_seed = _ptr(self.object_material), _ptr(self.object_material_next), int(self.recipe.seed)
+        if self.obj_group is not None:
+            a.obj_group = _ptr(self.obj_group)
+        parents, gb = np.asarray(A["body_parentid"]), np.asarray(A["geom_bodyid"])
+        for i in range(N):
+            body = int(a.obj_body[i])
+            geoms = np.nonzero(gb == body)[0]
+            if len(geoms) == 0 or not np.array_equal(geoms, np.arange(geoms[0], geoms[0] + len(geoms))) or np.any(parents == body) or int(parents[body]) != 0:
+                raise NotImplementedError("material_names: object%d is not one free body with one run of geoms (its _invweight0 rows are written in closed form)" % i)
+            a.obj_geomadr[i], a.obj_geomnum[i] = int(geoms[0]), len(geoms)
+            axes, r = quat2mat(np.asarray(A["body_iquat"][body], dtype=np.float64)), np.asarray(A["body_ipos"][body], dtype=np.float64)
+            for k in range(3):
+                a.obj_lever2[i][k] = float(np.sum(np.cross(r, axes[:, k]) ** 2))
+        rows, P = self.sim.view(_native.RG_F_DEBUG), self.sim.params
+        for k, name in enumerate(("geom_friction", "geom_solref", "geom_solimp", "body_mass", "body_inertia", "dof_armature", "dof_invweight0", "body_invweight0")):
+            a.mat_off[k] = (P[name].data_ptr() - rows.data_ptr()) // 4
+        #: the randomizers that would put the model's row in place of the material's: they start from the env's own rows (`_randomize`)
+        self._material_fields = ("geom_friction", "geom_solref", "geom_solimp", "body_mass", "body_inertia")
 
     # ------------------------------------------------------------------ launches
     def _stream(self):
@@ -1515,7 +1570,10 @@ class BatchedBlockRearrangeEnv:
         """Which recipe `reset` / `reset_goals` run: None = the device recipe exactly when the env was built with `device_reset` and without `pipelined_reset` (every
         other env keeps the path it had), True needs `device_reset`, False = the host recipe."""
         if on_device is None:
-            return self.device_reset and (not self.pipelined or self.object_pool)
+            return self.device_reset and (not self.pipelined or self.object_pool or self.materials_on)
+        if not on_device and self.materials_on:
+            raise NotImplementedError("material_names=%r: the host reset route is not built for materials (they are drawn and written by the device route's "
+                                      "parameter-row launch); on_device=None or True" % (self.material_names,))
         if not on_device and self.object_pool:
             raise NotImplementedError("object_pool (per-env object subsets): the host reset route is not built for it (the permutation is latched and sampled by the "
                                       "recipe kernel); on_device=None or True")
@@ -1540,7 +1598,23 @@ class BatchedBlockRearrangeEnv:
         """The per-env parameter rows of the device route on the masks the last recipe launch left (ra_param_rows_kernel, csrc/ra_env_kernel.h; the host route's twin:
         the `_param_defaults` restore, `_set_object_damping`, `_apply_parking`).  `active`: the [B] uint8 row of a synchronous reset; None = every env."""
         self.param_rows.stages, self.param_rows.active = stages, None if active is None else _ptr(active)
+        if self.materials_on:      # (the draw of an episode that ended: the counter of the recipe launch whose masks these are)
+            self.param_rows.mat_step = int(self.recipe.step)
         _native.check(self._L, self._L.ra_env_param_rows(self.sim._bh, ctypes.byref(self.param_rows), self._stream()), "ra_env_param_rows")
+
+    def _row_stages(self):
+        """the stages of the parameter-row launch that follows a recipe launch: the material stage with `material_names` only"""
+        return _native.RA_ROWS_RESTORE | _native.RA_ROWS_PARK | (_native.RA_ROWS_MATERIAL if self.materials_on else 0)
+
+    def _randomize(self, mask):
+        """The simulation randomizers for the envs `mask` ([B] bool, device).  With materials the randomizers of the fields a material writes start from the env's
+        rows as they stand -- the restored block plus the material, as the reference's start from the rebuilt world -- instead of the model's row."""
+        for rz in self.randomizers:
+            field = getattr(rz, "field_name", rz.name)
+            if self.materials_on and field in self._material_fields:      # (`randomize` makes the new values before it writes the field: no copy needed)
+                rz.randomize(self.sim, self._rand_gen, mask, initial=self.sim.params[field])
+            else:
+                rz.randomize(self.sim, self._rand_gen, mask)
 
     def _finish_recipe_launch(self, active=None, started=True):
         """What follows the last recipe launch of a step, of a synchronous reset (`active`: its [B] uint8 row, the envs outside it are left alone) or of a regoal-only
@@ -1551,8 +1625,7 @@ class BatchedBlockRearrangeEnv:
         act = None if active is None else active != 0
         if started and self.randomizers:
             mask = self.episode_started if act is None else self.episode_started & act
-            for rz in self.randomizers:
-                rz.randomize(self.sim, self._rand_gen, mask)
+            self._randomize(mask)
             if self.max_num_objects is not None:
                 self._param_rows_launch(_native.RA_ROWS_PARK, active)
         codes = self.reobserve if act is None else torch.where(act, self.reobserve, torch.full_like(self.reobserve, _native.RA_OBS_SKIP))
@@ -1578,7 +1651,7 @@ class BatchedBlockRearrangeEnv:
         self.active_row.copy_(act)
         r = self.recipe
         r.active, r.sync_mode = _ptr(self.active_row), _native.RA_SYNC_FORCED_END
-        both = _native.RA_ROWS_RESTORE | _native.RA_ROWS_PARK
+        both = self._row_stages()
         try:
             self._recipe_launch()
             r.sync_mode = _native.RA_SYNC_PIPELINED
@@ -1746,7 +1819,7 @@ class BatchedBlockRearrangeEnv:
         once more over the `reobserve` codes."""
         self._recipe_launch()
         if self.param_rows is not None:
-            self._param_rows_launch(_native.RA_ROWS_RESTORE | _native.RA_ROWS_PARK)
+            self._param_rows_launch(self._row_stages())
         self._finish_recipe_launch()
         self.ended_rows = np.zeros(0, dtype=np.int64)
 
@@ -1796,6 +1869,19 @@ class BatchedBlockRearrangeEnv:
         else:
             self.object_perm_next[torch.as_tensor(rows, device=self.device, dtype=torch.long)] = t
 
+    def set_object_material_next(self, names_or_indices, rows=None):
+        """material_names: the material of every slot in the NEXT episodes of the envs `rows` (default: every env), checked: names of envs/rearrange/materials.py or
+        indices into its MATERIAL_NAMES, -1 / None = drawn from `material_names`; one entry, [N], or one row per env.  The pin stays until it is written again.  With
+        `object_groups` the slots of a group take the material of the group's lowest slot.  Anything else raises ValueError.  (A value written to
+        `self.object_material_next` directly that names no material is drawn.)"""
+        if not self.materials_on:
+            raise ValueError("set_object_material_next: the env was built with material_names=%r (the compiled world's own material only)" % (self.material_names,))
+        t = torch.as_tensor(materials.material_indices(names_or_indices, self.N), device=self.device)
+        if rows is None:
+            self.object_material_next.copy_(t.expand(self.B, self.N) if t.dim() == 1 else t)
+        else:
+            self.object_material_next[torch.as_tensor(rows, device=self.device, dtype=torch.long)] = t
+
     def object_set(self):
         """object_pool: [B, num_objects] the world objects on every env's table, in slot order (a host query: a readback)"""
         if not self.object_pool:
@@ -1824,8 +1910,7 @@ class BatchedBlockRearrangeEnv:
         if not self.randomizers:
             return
         mask = self._mask_of(idx)
-        for r in self.randomizers:
-            r.randomize(self.sim, self._rand_gen, mask)
+        self._randomize(mask)
         if self.max_num_objects is not None:      # (gravity and body masses may have changed: the cancelling force follows them)
             self._apply_parking(mask)
 
@@ -1916,7 +2001,7 @@ def action_bin_array(lower_bound, upper_bound, n_bins, spacing="linear"):
     return np.concatenate([half, [0.0], -half[::-1]])
 
 
-SUPPORTED_PARAMETERS = {"simulation_params", "robot_control_params", "n_random_initial_steps"}
+SUPPORTED_PARAMETERS = {"simulation_params", "robot_control_params", "n_random_initial_steps", "material_names"}
 SUPPORTED_SIMULATION_PARAMS = {"num_objects", "max_num_objects", "penalty", "used_table_portion", "object_groups", "goal_distance_ratio", "goal_distance_min"}
 SUPPORTED_ROBOT_CONTROL_PARAMS = {"max_position_change", "arm_reset_controller_error", "control_mode", "tcp_solver_mode"}
 SUPPORTED_CONSTANTS = {"success_threshold", "successes_needed", "success_reward", "max_timesteps_per_goal_per_obj", "n_action_bins", "action_spacing", "use_goal_distance_reward",
@@ -2012,6 +2097,8 @@ def make_env_args(parameters, constants, starting_seed, apply_wrappers, num_obje
                 n_action_bins=constants.get("n_action_bins", 11), control_mode=rc.get("control_mode", "tcp+roll+yaw"), tcp_solver_mode=rc.get("tcp_solver_mode", "mocap_ik"))      # (+ pipelined_reset=True through **kw: episodes restart inside the step calls)
     if "action_spacing" in constants:
         args["action_spacing"] = constants["action_spacing"]
+    if "material_names" in parameters:      # (None or an empty list: all five, as the reference's code loads them)
+        args["material_names"] = parameters["material_names"]
     for k in ("success_threshold", "successes_needed", "success_reward", "max_timesteps_per_goal_per_obj", "use_goal_distance_reward", "goal_reward_per_object"):
         if k in constants:
             args[k] = constants[k]

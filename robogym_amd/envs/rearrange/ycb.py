@@ -13,6 +13,7 @@ ordered sets per shipped world, sampled WITHOUT replacement inside that world (t
 Not built: a set sampled from the whole YCB catalogue per episode (the reference re-creates the simulation at every reset, common/base.py:850-856:
 needs per-env geometry rows in the stepper); `normalize_mesh`, object-scale randomisation, the mesh envs' damping change while objects settle."""
 from robogym_amd import _native
+from robogym_amd.envs.rearrange import materials
 from robogym_amd.envs.rearrange.blocks import BatchedBlockRearrangeEnv
 from robogym_amd.envs.rearrange.xml import load_ycb_model
 
@@ -113,6 +114,9 @@ class GroupedYcbRearrangeEnv:
         import torch
 
         K = len(object_sets)
+        if "material_names" in kw and not materials.is_default_only(materials.material_list(kw["material_names"])):
+            raise NotImplementedError("material_names=%r is not implemented by the grouped ycb env (the slots are traded between the groups; `object_material` belongs to "
+                                      "a slot): BatchedYcbRearrangeEnv takes it" % (kw["material_names"],))
         # device_reset (the recipe kernel): the slot trading runs on the device too (round 6, _trade_slots_device): no readback of the ended episodes in a step call
         self._device_trade = bool(kw.get("device_reset")) and bool(resample_object_sets)
         assert batch_size % K == 0, "batch_size must be a multiple of the number of object sets"

@@ -35,12 +35,13 @@ class SimulationRandomizer:
     def _sample(self, init: torch.Tensor, gen: torch.Generator) -> torch.Tensor:
         raise NotImplementedError
 
-    def randomize(self, sim, gen: torch.Generator, mask: Optional[torch.Tensor] = None):
-        """Draw new values for the envs in `mask` (default: all) from the model's initial values."""
+    def randomize(self, sim, gen: torch.Generator, mask: Optional[torch.Tensor] = None, initial: Optional[torch.Tensor] = None):
+        """Draw new values for the envs in `mask` (default: all) from the model's initial values -- or from `initial`, per-env values of the field's own shape
+        (the rearrange envs' per-object materials: the rows of a world rebuilt with the episode's materials)."""
         f = self._field(sim)
         if self._initial is None:
             self._initial = f[0].clone()          # every row starts as the model's own values
-        new = self._sample(self._initial.expand_as(f), gen)
+        new = self._sample(self._initial.expand_as(f) if initial is None else initial, gen)
         if mask is None:
             f.copy_(new)
         else:
@@ -105,11 +106,11 @@ class GenericSimRandomizer(SimulationRandomizer):
         f = sim.params[self.field_name]
         return f if self.ids is None else _RowSubset(f, self.ids)
 
-    def randomize(self, sim, gen, mask=None):
+    def randomize(self, sim, gen, mask=None, initial=None):
         f = sim.params[self.field_name]
         if self._initial is None:
             self._initial = f[0].clone()
-        init = self._initial.expand_as(f)
+        init = self._initial.expand_as(f) if initial is None else initial
         new = self._sample(init, gen)
         if self.positive_only:
             new = new.clamp(min=0.0)
